@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — MD steps/s and atom-updates/s of the hot path on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of the hot path (velocity-Verlet kick/drift, LJ+Coulomb tile kernel, bonded
@@ -10,21 +10,38 @@ terms, rebuild trigger; neighbour rebuilds included at their natural cadence) ov
 state resident in HBM before the timed region.  For N > 1 the SAME box is spatially decomposed
 across the ranks (strong scaling) with ghost-atom halo exchange over RCCL.
 
-Prints ONE JSON line on rank 0: the contract keys plus
+A plain run does only what the headline needs: it prepares the box, settles and warms up the timed handle, times the K
+steps, writes the timed path's outputs if --dump-outputs is given, and prints ONE JSON line on rank 0: the contract keys
+plus
   roofline     — dominant kernel (nb_cluster_kernel): algorithmic bytes (32 B per atom)
                  x atoms per launch / mean launch duration from HIP events on the library's stream
+--full adds everything that takes runs of its own, after the timed region:
+  tail         — the driver's command times 20 steps (10 ms: zero or one list rebuild, no energy evaluation falls into it),
+                 so an UNTIMED-for-`value` tail of 1000 steps runs with rebuilds at their natural cadence and energies every
+                 100 steps; its rate is reported beside `value` as `steps_per_s_1000`
+  kernel_ms, roofline_streaming — bonded / integrate kernel times from a 48-step tail with every kernel bracketed
+  multi_gpu    — decomposed runs: per-rank phase times from 48 more bracketed steps
+  classes, default_operating_point — BASELINE configs 2-4 and the reference's own operating point (N = 1, water1M)
   cpu_baseline — oracle/cpu_production.c (fp32, half Verlet list reused across steps, OpenMP over all host cores,
                  built -O3 -march=native on the machine it runs on) on a bounded sample of the same box
-The driver's command times 20 steps (10 ms: zero or one list rebuild, no energy evaluation falls into it), so after the
-timed region an UNTIMED-for-`value` tail of 1000 steps runs with rebuilds at their natural cadence and energies every 100
-steps; its rate is reported beside `value` as `steps_per_s_1000`.  The handle that is timed is created from the prepared
-state just before the run; --settle-steps (300, untimed, reported in config.untimed_preparation) let its step loop reach
-its steady state (rebuild cadence -> chunk lengths, dual-list buffer, decomposed: the split's A/B over 16 chunks) before
-the W warm-up steps - with --warmup 5 alone the window measured the start-up of a new handle (tools/window_warmup.sh).
+The handle that is timed is created from the prepared state just before the run; --settle-steps (300, untimed, reported
+in config.untimed_preparation) let its step loop reach its steady state (rebuild cadence -> chunk lengths, dual-list
+buffer, decomposed: the split's A/B over 16 chunks) before the W warm-up steps - with --warmup 5 alone the window
+measured the start-up of a new handle (tools/window_warmup.sh).
+
+--dump-outputs DIR writes what two steps of the timed path compute - positions.npy, velocities.npy, forces.npy (float32,
+[n_atoms, 3], caller order; 37 MB at water1M) - so that two builds can be compared output for output.  Their inputs are the
+same bits from run to run: the preparation runs the deterministic full-list pair kernel (nb_variant 2), so the prepared
+state does not depend on the summation order of f32 atomics, and after the timed steps the handle that was timed goes back
+to that state and takes DUMP_STEPS = 2 more steps - the kernel sequence of a chunk: opening step, one fused bonded + kick +
+drift pass, closing kick.  Two runs at water1M: forces within 1.0e-5 kcal/mol/A rms (max 0.008).  The end state of the timed
+steps is not what is written: the default kernel adds its j-forces as f32 atomics in a different order every run, and the
+shifted cutoff's force step at rc grows those last bits apart beyond rounding (16 steps: 9.4e-4 rms, max 0.93).
 """
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import os
 import sys
@@ -43,6 +60,9 @@ B_ALG_BONDED_WATER = 52.0      # 36 + 16 t, t = 1 bonded term per atom in flexib
 B_ALG_FUSED_WATER = 116.0      # bonded gather + kick + drift as one pass: the two figures above together
 B_ALG_STEP_WATER = 170.0       # whole step, water box
 FLOP_PER_PAIR = 45.0
+# --dump-outputs: steps of the timed path from the prepared state.  Two runs the kernel sequence of a step loop's chunk: the
+# opening step (pair call with the bonded gather deferred), one fused bonded + kick + drift pass, the closing kick.
+DUMP_STEPS = 2
 def _nb_kernel_rev():
     """Revision of the default pair kernel's code (molchanica_amd/_build_info.py: comment- and white-space-insensitive hash of the
     two headers that hold the kernel + the parameter structs it reads): the cached PMC traffic figure (profiles/nb_traffic.json,
@@ -70,8 +90,14 @@ def parse():
                          "the same workload on the host CPU (e.g. a headless build of the reference's md loop); it is timed as a "
                          "child process and reported as cpu_baseline.kind = 'reference' instead of this repo's CPU port")
     ap.add_argument("--reference-steps", type=int, default=100, help="steps the --reference-cmd run performs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what takes runs of its own: the tail, the bracketed kernel tails, "
+                         "the decomposed phase times, the classes / default operating point and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the positions, velocities and forces of two steps of the timed path from the prepared state to DIR/<name>.npy")
     ap.add_argument("--tail-steps", type=int, default=-1,
-                    help="untimed-for-value tail with natural rebuilds and energies every 100 steps; -1 = 1000 when --steps < 1000, else 0")
+                    help="untimed-for-value tail with natural rebuilds and energies every 100 steps; "
+                         "-1 = 1000 with --full when --steps < 1000, else 0")
     ap.add_argument("--settle-steps", type=int, default=300,
                     help="untimed NVE steps on the handle that is timed, in front of the --warmup steps: the preparation above runs on a "
                          "handle of its own, and a new handle's step loop learns its rebuild cadence (chunk lengths), its dual-list buffer "
@@ -94,7 +120,7 @@ def parse():
     ap.add_argument("--inner-skin", type=float, default=0.0,
                     help="dual pair list: buffer of the rolling-pruned inner list in A (0 = library default 0.5, < 0 = off)")
     ap.add_argument("--no-extras", dest="extras", action="store_false",
-                    help="skip the extra keys of the default run (N = 1, water1M): `classes` = steps/s of BASELINE configs 2-4 (dhfr23k, "
+                    help="skip the extra keys of a --full run (N = 1, water1M): `classes` = steps/s of BASELINE configs 2-4 (dhfr23k, "
                          "complex50k, dna100k) and `default_operating_point` = the reference's own configuration (rigid OPC, SPME, dt 2 fs)")
     ap.add_argument("--pme", action="store_true", help="Ewald Coulomb with the SPME reciprocal sum (not the headline config)")
     return ap.parse_args()
@@ -312,12 +338,14 @@ def main():
     # generator places waters on a jittered lattice with random orientations, and run as-is that
     # potential energy heats the box to ~1300 K.  So: steepest-descent relaxation, velocities drawn at
     # 300 K, a short Berendsen-coupled run, thermostat off.  The timed region is plain NVE.  Rank 0
-    # prepares, everyone receives the same state.
+    # prepares, everyone receives the same state.  The preparation runs the deterministic full-list pair kernel
+    # (nb_variant 2): with the default half-list kernel the f32 atomics of its Newton-3 write-back make every run start the
+    # timed region from a different state, and --dump-outputs needs the same inputs from run to run.
     prep = None
     if args.equilibrate and system.periodic:
         t_prep = time.perf_counter()
         if rank == 0:
-            with MdState(system, cfg, device=local_rank) as eq:
+            with MdState(system, dataclasses.replace(cfg, nb_variant=2), device=local_rank) as eq:
                 eq.minimize_energy(args.eq_min_iters)
                 eq.initialize_velocities(300.0, True, seed=105)
                 eq.set_thermostat(1, 300.0, 0.02, 1)
@@ -447,9 +475,9 @@ def main():
     sync()
     el = max_over_ranks(time.perf_counter() - t0)
     st = stats()
-    # Untimed-for-`value` tail: the driver's 20-step window holds no list rebuild and no energy evaluation, so the
+    # Untimed-for-`value` tail (--full): the driver's 20-step window holds no list rebuild and no energy evaluation, so the
     # representative rate (natural rebuild cadence, energies every 100 steps) is measured here and reported beside it.
-    tail_steps = args.tail_steps if args.tail_steps >= 0 else (1000 if args.steps < 1000 else 0)
+    tail_steps = args.tail_steps if args.tail_steps >= 0 else (1000 if args.full and args.steps < 1000 else 0)
     tail = None
     if tail_steps > 0:
         sync()
@@ -465,25 +493,29 @@ def main():
         st_nb = st_t                       # pair-kernel launch statistics: timed region + tail
     else:
         st_nb = st
-    # bonded / integrate kernel times: a short tail outside the timed region with every kernel bracketed
-    prof(1)
-    st_pre = stats()
-    stepper(48)
-    sync()
-    st_tail = stats()
-    prof(0)
-    # the large classes run bonded gather + kick + drift as ONE pass on 15 steps of a 16-step chunk: its own timer
-    fused_n = st_tail.get("fused_launches", 0) - st_pre.get("fused_launches", 0)
-    fused_ms = (st_tail.get("fused_ms_sum", 0.0) - st_pre.get("fused_ms_sum", 0.0)) / fused_n if fused_n else None
-    streaming_ms_per_step = ((st_tail["bonded_ms_sum"] - st_pre["bonded_ms_sum"]) + (st_tail["integ_ms_sum"] - st_pre["integ_ms_sum"])
-                             + (st_tail.get("fused_ms_sum", 0.0) - st_pre.get("fused_ms_sum", 0.0))) / 48.0
-    if args.profile_level == 0:
-        st_nb = st_tail
+    # bonded / integrate kernel times (--full): a short tail outside the timed region with every kernel bracketed
+    fused_n = fused_ms = streaming_ms_per_step = bonded_ms = integ_ms = None
+    if args.full:
+        prof(1)
+        st_pre = stats()
+        stepper(48)
+        sync()
+        st_tail = stats()
+        prof(0)
+        # the large classes run bonded gather + kick + drift as ONE pass on 15 steps of a 16-step chunk: its own timer
+        fused_n = st_tail.get("fused_launches", 0) - st_pre.get("fused_launches", 0)
+        fused_ms = (st_tail.get("fused_ms_sum", 0.0) - st_pre.get("fused_ms_sum", 0.0)) / fused_n if fused_n else None
+        streaming_ms_per_step = ((st_tail["bonded_ms_sum"] - st_pre["bonded_ms_sum"]) + (st_tail["integ_ms_sum"] - st_pre["integ_ms_sum"])
+                                 + (st_tail.get("fused_ms_sum", 0.0) - st_pre.get("fused_ms_sum", 0.0))) / 48.0
+        bonded_ms = st_tail["bonded_ms_sum"] / max(st_tail["bonded_launches"], 1)
+        integ_ms = st_tail["integ_ms_sum"] / max(st_tail["integ_launches"], 1)
+        if args.profile_level == 0:
+            st_nb = st_tail
 
-    # Decomposed runs: where the step time goes, rank by rank (mdx_comm_diag): 48 more steps with every phase of the step
-    # bracketed in its production arrangement (profile level 3), outside the timed region.
+    # Decomposed runs (--full): where the step time goes, rank by rank (mdx_comm_diag): 48 more steps with every phase of the
+    # step bracketed in its production arrangement (profile level 3), outside the timed region.
     multi = None
-    if world > 1 or args.decomposed:
+    if args.full and (world > 1 or args.decomposed):
         prof(3)
         t_d = time.perf_counter()
         stepper(48)
@@ -516,6 +548,21 @@ def main():
                  "note": "GPU time between HIP events per phase, 48 untimed steps at profile level 3 (production arrangement); "
                          "halo_wire / force_wire = the ncclSend/ncclRecv group incl. waiting for the peers; pair = whole launch or interior half"}
 
+    if args.dump_outputs:
+        # What a caller of the timed path reads after DUMP_STEPS steps of it, from inputs that are the same bits in every run: the
+        # handle that was timed goes back to the prepared state and takes DUMP_STEPS more steps.  The state after the timed steps
+        # themselves differs from run to run by far more than rounding: the pair kernel's j-forces land as f32 atomics in a
+        # different order every run, and the shifted cutoff's force step at rc turns those last bits into O(0.1) force
+        # differences within ~20 steps.  Last, so nothing above sees the reset; a collective on a decomposed handle: every rank
+        # steps and downloads, rank 0 writes.
+        md.set_positions(system.pos); md.set_velocities(system.vel)
+        stepper(DUMP_STEPS)
+        outputs = {"positions": md.positions(), "velocities": md.velocities(), "forces": md.forces()}
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
     steps_per_s = args.steps / el
     value = n_atoms * steps_per_s
     # Whether one of the ~0.6 ms list rebuilds (one per ~25 steps) lands in a 20-step timed window is a coin flip worth 5 % of
@@ -525,11 +572,11 @@ def main():
     ms_no_rb = (1e3 * el - rb_ms_timed) / args.steps
     nb_launches = st_nb["nb_launches"]
     nb_ms = st_nb["nb_ms_sum"] / max(nb_launches, 1)
-    bonded_ms = st_tail["bonded_ms_sum"] / max(st_tail["bonded_launches"], 1)
-    integ_ms = st_tail["integ_ms_sum"] / max(st_tail["integ_launches"], 1)
     atoms_per_launch = st["n_atoms"]                 # owned + ghost atoms of this rank's launch
     gbs = lambda b_per_atom, ms: b_per_atom * atoms_per_launch / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    achieved = gbs(B_ALG_NONBONDED, nb_ms)
+    if nb_launches == 0:
+        nb_ms = None                                 # no pair launch was bracketed (--profile-level 0 without --full)
+    achieved = gbs(B_ALG_NONBONDED, nb_ms) if nb_ms is not None else None
     # (i-cluster, j-cluster) pairs x 8 x 8 lanes.  With the dual list most step-loop launches walk the inner list (mean
     # over the pruning passes) and a fraction `prune_frac` walks the Verlet list while it re-prunes.
     n_steps_nb = max(int(st_nb["step_count"] - st0["step_count"]), 1)
@@ -544,7 +591,7 @@ def main():
     if system.periodic and not args.pme and world == 1:
         vol = float(np.prod(np.asarray(system.box_hi, np.float64) - np.asarray(system.box_lo, np.float64)))
         half_pairs_per_atom = 0.5 * (4.0 / 3.0) * np.pi * max(cfg.lj_cutoff, cfg.coulomb_cutoff) ** 3 * n_atoms / vol
-        alg_tflops = FLOP_PER_PAIR * half_pairs_per_atom * n_atoms / (nb_ms * 1e-3) / 1e12 if nb_ms > 0 else 0.0
+        alg_tflops = FLOP_PER_PAIR * half_pairs_per_atom * n_atoms / (nb_ms * 1e-3) / 1e12 if nb_ms else None
     traffic, traffic_source = None, None
     tfile = os.path.join(ROOT, "profiles", "nb_traffic.json")
     if os.path.exists(tfile):
@@ -591,14 +638,22 @@ def main():
                    "rebuild_fallbacks": int(st_nb.get("rebuild_fallbacks", 0)),
                    "n_owned_rank0": int(st_nb["n_owned"]), "n_ghost_rank0": int(st_nb["n_ghost"])},
         "roofline": {"kernel": kernel, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS if achieved is not None else None, "traffic": traffic, "traffic_source": traffic_source,
                      "launch_ms": nb_ms, "launches": nb_launches,
-                     "launch_sampling": ("HIP events around every %s-th executed pair launch of the timed region + tail (MDX_PROF_SAMPLE; a bracket on "
-                                         "every launch costs 10-14 us of a step: 2 %% at water1M, 28 %% at dhfr23k)" % os.environ.get("MDX_PROF_SAMPLE", "8")),
+                     "launch_sampling": ("HIP events around every %s-th executed pair launch of the timed region%s (MDX_PROF_SAMPLE; a bracket on "
+                                         "every launch costs 10-14 us of a step: 2 %% at water1M, 28 %% at dhfr23k)"
+                                         % (os.environ.get("MDX_PROF_SAMPLE", "8"), " + tail" if tail else "")),
                      "algorithmic_bytes_per_launch": B_ALG_NONBONDED * atoms_per_launch,
                      "note": "pair loop is fp32-VALU bound, see valu.frac; HBM fraction is low by physics"},
+        "valu": {"pair_evals_per_launch": pair_evals,
+                 "pair_evals_per_s": pair_evals / (nb_ms * 1e-3) if nb_ms else None,
+                 "algorithmic_tflops": alg_tflops, "peak_tflops": FP32_PEAK_TFLOPS,
+                 "frac": alg_tflops / FP32_PEAK_TFLOPS if alg_tflops is not None else None},
+        "step_hbm_frac": B_ALG_STEP_WATER * value / (world * HBM_PEAK_GBS * 1e9) if args.workload == "water1M" else None,
+    }
+    if args.full:
         # the streaming kernels, in SURVEY 8d's algorithmic bytes (profiled 48-step tail, every kernel bracketed)
-        "roofline_streaming": {
+        out["roofline_streaming"] = {
             "integrate_kernel": {"bound": "hbm", "bytes_per_atom": B_ALG_INTEGRATE, "launch_ms": integ_ms,
                                  "achieved": gbs(B_ALG_INTEGRATE, integ_ms), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                  "frac": gbs(B_ALG_INTEGRATE, integ_ms) / HBM_PEAK_GBS},
@@ -611,18 +666,12 @@ def main():
             "bonded_integrate_kernel": ({"bound": "hbm", "bytes_per_atom": B_ALG_FUSED_WATER, "launch_ms": fused_ms,
                                          "achieved": gbs(B_ALG_FUSED_WATER, fused_ms), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                          "frac": gbs(B_ALG_FUSED_WATER, fused_ms) / HBM_PEAK_GBS, "launches_of_48_steps": fused_n}
-                                        if (fused_ms and args.workload == "water1M") else ({"launch_ms": fused_ms} if fused_ms else None))},
-        "valu": {"pair_evals_per_launch": pair_evals,
-                 "pair_evals_per_s": pair_evals / (nb_ms * 1e-3) if nb_ms > 0 else 0.0,
-                 "algorithmic_tflops": alg_tflops, "peak_tflops": FP32_PEAK_TFLOPS,
-                 "frac": alg_tflops / FP32_PEAK_TFLOPS if alg_tflops is not None else None},
-        "step_hbm_frac": B_ALG_STEP_WATER * value / (world * HBM_PEAK_GBS * 1e9) if args.workload == "water1M" else None,
-        "multi_gpu": multi,
-        "kernel_ms": {"nonbonded": nb_ms, "bonded": bonded_ms, "integrate": integ_ms, "bonded_integrate_fused": fused_ms,
-                      "bonded_plus_integrate_per_step": streaming_ms_per_step,
-                      "rebuild_total": st_nb["rebuild_ms_sum"] - st0["rebuild_ms_sum"]},
-    }
-    if rank == 0 and world == 1 and args.extras and args.workload == "water1M" and not args.pme and not args.decomposed:
+                                        if (fused_ms and args.workload == "water1M") else ({"launch_ms": fused_ms} if fused_ms else None))}
+        out["multi_gpu"] = multi
+        out["kernel_ms"] = {"nonbonded": nb_ms, "bonded": bonded_ms, "integrate": integ_ms, "bonded_integrate_fused": fused_ms,
+                            "bonded_plus_integrate_per_step": streaming_ms_per_step,
+                            "rebuild_total": st_nb["rebuild_ms_sum"] - st0["rebuild_ms_sum"]}
+    if args.full and rank == 0 and world == 1 and args.extras and args.workload == "water1M" and not args.pme and not args.decomposed:
         # BASELINE configs 2-4 and the reference's own operating point, measured by whoever runs this command (the driver), on this
         # GPU, after the headline numbers are in hand; a failure is reported inside the line, never instead of it
         md.close()
@@ -636,7 +685,7 @@ def main():
             out["default_operating_point"] = default_operating_point_rate(local_rank)
         except Exception as e:  # noqa: BLE001
             out["default_operating_point"] = {"steps_per_s": None, "error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the GPU measurement above must reach the driver whatever happens to the CPU leg (a failed -march=native build,
         # a missing compiler on the box): its failure is reported inside the JSON line, not instead of it
         try:

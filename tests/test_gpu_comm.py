@@ -642,7 +642,7 @@ def test_bench_process_per_rank_flow_on_one_gpu(n):
     env = dict(os.environ, MDX_BENCH_SAME_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "40", "--warmup", "8",
-           "--workload", "dna100k", "--no-cpu-baseline", "--energy-every", "20", "--tail-steps", "60"]
+           "--workload", "dna100k", "--no-cpu-baseline", "--energy-every", "20", "--tail-steps", "60", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -673,7 +673,7 @@ def _torchrun_bench(n, extra_env, extra_args=(), timeout=600):
     env = dict(os.environ, MDX_BENCH_SAME_GPU="1", MASTER_ADDR="127.0.0.1", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "4",
-           "--workload", "dna100k", "--no-cpu-baseline", "--tail-steps", "0", *extra_args]
+           "--workload", "dna100k", "--no-cpu-baseline", "--tail-steps", "0", "--full", *extra_args]
     return subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=timeout)
 
 

@@ -2,6 +2,7 @@
 # A/B of builds of the library on the headline workload: tools/ab_lib.sh <tag> libA.so libB.so ...   (names under molchanica_amd/)
 # Each build runs twice, interleaved; prints steps/s and the HIP-event kernel times of bench.py.
 TAG=$1; shift
+AB_ARGS="--full $AB_ARGS"      # kernel_ms comes from the bracketed tail of a --full run
 mkdir -p gpurun_out/$TAG
 for rep in 1 2; do
   for L in "$@"; do

@@ -2,8 +2,8 @@
 # The driver's own bench command (20 timed steps behind 5 warm-up steps), repeated: how much the headline `value` moves with
 # where the list rebuilds fall in the 20-step window.  bash tools/driver_bench_repeat.sh [N]
 N=${1:-5}; O=$PWD/gpurun_out/drv; mkdir -p "$O"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/b1.json" 2>/dev/null
-for i in $(seq 2 $N); do python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$O/b$i.json" 2>/dev/null; done
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$O/b1.json" 2>/dev/null
+for i in $(seq 2 $N); do python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$O/b$i.json" 2>/dev/null; done
 python3 - "$O" <<'PY'
 import json, glob, sys
 for f in sorted(glob.glob(sys.argv[1] + "/b*.json")):

@@ -3,6 +3,7 @@
 #   bash tools/env_ab.sh MDX_ROLE_HEADS "1 0" [rounds] [bench args]
 # prints: KNOB=v steps/s ms/step fused-pass-ms pair-ms rebuild-ms-per-step rebuilds
 K=$1; VALS=${2:-"1 0"}; R=${3:-2}; shift 3 2>/dev/null
+set -- --full "$@"      # kernel_ms comes from the bracketed tail of a --full run
 mkdir -p gpurun_out/ab
 for r in $(seq 1 $R); do for v in $VALS; do
   env $K=$v python3 bench.py --steps 1000 --warmup 100 --no-cpu-baseline --no-extras "$@" > gpurun_out/ab/bench_${K}_$v.json 2>/dev/null

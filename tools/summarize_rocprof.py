@@ -39,7 +39,7 @@ if kt:
         dur = (en - st) / 1e3
         d[0] += 1; d[1] += dur; d[2] = min(d[2], dur); d[3] = max(d[3], dur)
     total = sum(v[1] for v in stats.values())
-    lines.append(f"# rocprofv3 --kernel-trace --stats  ({tag}; python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline)")
+    lines.append(f"# rocprofv3 --kernel-trace --stats  ({tag}; python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline)")
     lines.append("# includes the untimed preparation of the box (minimiser = energy-flavour kernels, 600 thermostatted steps)")
     lines.append(f"{'kernel':58s} {'calls':>7s} {'total_us':>12s} {'avg_us':>10s} {'min_us':>10s} {'max_us':>10s} {'pct':>6s}")
     for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1]):
