@@ -160,7 +160,7 @@ typedef struct mdx_energies {
     double kinetic;             /* kcal/mol */
     double potential;           /* = potential_nonbonded + potential_bonded */
     double potential_nonbonded; /* lj + coulomb + lj14 + coulomb14 */
-    double potential_bonded;    /* bond + angle + dihedral */
+    double potential_bonded;    /* bond + angle + dihedral (+ position restraints: mdx_restraint_energy) */
     double lj, coulomb, lj14, coulomb14;
     double bond, angle, dihedral;
     double temperature;         /* K, 2 KE / (dof kB), dof = 3 N_mobile - 3 (>=1) */
@@ -228,6 +228,30 @@ void mdx_destroy(mdx_handle* h);
  * [ref: src/md/mod.rs:716,748 (10-step GUI burst :737); src/mol_alignment.rs:346 (ext forces)].
  * ext_forces: [3N] kcal/mol/Å in caller atom order, held constant over the burst, or NULL. */
 int mdx_step(mdx_handle* h, float dt, const float* ext_forces, uint32_t n_steps);
+
+/* Position restraints: hold atoms near reference positions (restrained minimisation, equilibration with heavy atoms
+ * restrained, a framework shell held softly instead of frozen with MDX_ATOM_STATIC).  For restrained atom i with reference r0_i,
+ * constant k_i (kcal/mol/Å²) and flat-bottom radius b_i >= 0 (Å):
+ *     d   = x_i - r0_i, minimum image along the periodic axes
+ *     E_i = k_i max(0, |d| - b_i)²                      (the bond form E = k (r - r0)², no 1/2; Amber's restraint_wt)
+ *     F_i = -2 k_i (|d| - b_i) d / |d|  when |d| > b_i, else 0
+ *     W_i = d . F_i                                       (in `virial`)
+ * On a periodic axis the reference is kept in box-fractional coordinates, so it follows every box change (barostat,
+ * mdx_shrink_cell_towards, mdx_set_box) as an affinely scaled atom would; W is then -dE/dlambda of a uniform scaling and the
+ * pressure stays consistent.  Along a non-periodic axis the reference is absolute.  The energy counts in `potential` and
+ * `potential_bonded`; the MDX_OVR_* switches do not disable restraints.  Virtual sites and the atoms of rigid waters stepped by
+ * the one-pass water kernel cannot be restrained.
+ *
+ * mdx_set_position_restraints replaces the handle's whole restraint set; n = 0 clears it.  ref: [3n] Å, or NULL = the atoms'
+ * current positions; k: [n] kcal/mol/Å² (> 0, finite); flat_bottom: [n] Å (>= 0) or NULL = 0.  Same global table on every rank
+ * of a decomposed handle, before or after mdx_comm_init (ext_forces' convention; not collective - after mdx_comm_init ref must
+ * be given). */
+int      mdx_set_position_restraints(mdx_handle* h, uint32_t n, const uint32_t* idx, const float* ref, const float* k,
+                                     const float* flat_bottom);
+/* current references in Cartesian Å (i.e. after any box change), caller order of the last set; returns the count */
+uint32_t mdx_position_restraints_read(mdx_handle* h, uint32_t capacity, uint32_t* idx, float* ref, float* k, float* flat_bottom);
+/* restraint share of the evaluation mdx_energy last reported: energy (kcal/mol) and its virial W */
+int      mdx_restraint_energy(mdx_handle* h, double* energy, double* virial);
 
 /* Forces + per-term energies of the current state without stepping (the per-snapshot
  * energy_data, src/md/viewer.rs:378-394). */

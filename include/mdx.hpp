@@ -183,6 +183,32 @@ public:
         check(mdx_minimize_energy(h_, max_iters, external_forces, f_tol, &e, iters_done));
         return e;
     }
+    /// Position restraints (mdx.h): replaces the whole set; an empty `idx` clears it.  `ref` [3n] or null = current positions,
+    /// `flat_bottom` [n] or null = 0.
+    void set_position_restraints(const std::vector<uint32_t>& idx, const float* ref, const std::vector<float>& k,
+                                 const float* flat_bottom = nullptr) {
+        if (k.size() != idx.size()) throw ParamError("set_position_restraints: k must have one entry per index");
+        check(mdx_set_position_restraints(h_, (uint32_t)idx.size(), idx.data(), ref, k.data(), flat_bottom));
+    }
+    void clear_position_restraints() { check(mdx_set_position_restraints(h_, 0, nullptr, nullptr, nullptr, nullptr)); }
+    /// current references in Cartesian Å (after any box change)
+    uint32_t position_restraints(std::vector<uint32_t>* idx, std::vector<float>* ref, std::vector<float>* k,
+                                 std::vector<float>* flat_bottom) {
+        const uint32_t n = mdx_position_restraints_read(h_, 0, nullptr, nullptr, nullptr, nullptr);
+        if (idx) idx->resize(n);
+        if (ref) ref->resize(3 * (size_t)n);
+        if (k) k->resize(n);
+        if (flat_bottom) flat_bottom->resize(n);
+        mdx_position_restraints_read(h_, n, idx ? idx->data() : nullptr, ref ? ref->data() : nullptr, k ? k->data() : nullptr,
+                                     flat_bottom ? flat_bottom->data() : nullptr);
+        return n;
+    }
+    /// restraint share of the evaluation `energy()` last reported: {energy, virial}
+    std::pair<double, double> restraint_energy() {
+        double e = 0.0, w = 0.0;
+        check(mdx_restraint_energy(h_, &e, &w));
+        return {e, w};
+    }
     /// `md.initialize_velocities(temperature, zero_com_drift)` (sol_shrinking_box.rs:965).
     void initialize_velocities(float temperature, bool zero_com_drift = true, uint64_t seed = 0) {
         check(mdx_initialize_velocities(h_, temperature, zero_com_drift ? 1 : 0, seed));

@@ -176,6 +176,7 @@ static int create_impl(const mdx_system* s, const mdx_config* c, int device, mdx
     if (h->cfg.chunk_steps > MDX_MAX_CHUNK) h->cfg.chunk_steps = MDX_MAX_CHUNK;
     decode_periodic(s->periodic, h->per);
     h->periodic = h->per[0] || h->per[1] || h->per[2];
+    for (int d = 0; d < 3; ++d) h->posre_per[d] = h->per[d];
     for (int d = 0; d < 3; ++d) { h->box_lo[d] = s->box_lo[d]; h->box_hi[d] = s->box_hi[d]; }
     MDX_TRY(check_box(h->per, h->box_lo, h->box_hi, c));
     h->n_local = N; h->cap_local = N;
@@ -347,6 +348,7 @@ static int create_impl(const mdx_system* s, const mdx_config* c, int device, mdx
         h->n_roles_dih = 0;
         for (const RoleRec& r : recs) h->n_roles_dih += ((r.meta & 0xFu) != ROLE_BOND && (r.meta & 0xFu) != ROLE_ANGLE) ? 1u : 0u;
         if (prm_overflow) FAIL(MDX_EPARAM, "more than 16.7 M distinct bonded parameter sets");
+        h->n_prm_base = (uint32_t)prm_tab.size();
         MDX_TRY(upload_vec(&d.role_prm, prm_tab, st));
         MDX_TRY(upload_vec(&d.role_off_o, cnt, st)); MDX_TRY(upload_vec(&d.role_rec_o, recs, st));
         MDX_TRY(alloc_n(&d.role_rec_s, R));
@@ -1060,7 +1062,8 @@ static int energy_tail(mdx_handle* h, mdx_energies* out) {
     out->bond = e[EN_BOND]; out->angle = e[EN_ANGLE]; out->dihedral = e[EN_DIHEDRAL];
     out->lj = e[EN_LJ]; out->coulomb = e[EN_COUL]; out->lj14 = e[EN_LJ14]; out->coulomb14 = e[EN_COUL14];
     out->kinetic = e[EN_KIN];
-    out->potential_bonded = out->bond + out->angle + out->dihedral;
+    out->potential_bonded = out->bond + out->angle + out->dihedral + e[EN_POSRE];   // (position restraints: booked with the bonded terms)
+    h->posre_e = e[EN_POSRE]; h->posre_w = e[EN_POSRE_VIR];
     out->coulomb_recip = h->pme_on ? e[EN_RECIP] + h->ewald_self + h->ewald_background : 0.0;
     out->potential_nonbonded = out->lj + out->coulomb + out->lj14 + out->coulomb14 + out->coulomb_recip;
     out->potential = out->potential_bonded + out->potential_nonbonded;
@@ -1699,5 +1702,119 @@ extern "C" void* mdx_stream(mdx_handle* h) { return h ? (void*)h->stream : nullp
 extern "C" int mdx_debug_half_stats(mdx_handle* h, unsigned long long out[6]) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(out, h->d.inner_count + MDX_EPART, sizeof(unsigned long long) * 6, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+// ---- position restraints (include/mdx.h) -----------------------------------------------------------------------------
+// One ROLE_POSRE record per restrained atom, last in its caller-order role list, and one parameter set per restraint behind the
+// force field's.  A new set rebuilds the caller-order tables from the ones on the device with the old restraint records taken out,
+// so that clearing leaves exactly the tables mdx_create made; the slot-order lists are then refilled for the current slot order.
+static int posre_install(mdx_handle* h) {
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t N = h->N, R_old = h->n_roles, n = h->n_posre;
+    std::vector<uint32_t> off_old(N + 1);
+    std::vector<RoleRec> rec_old(R_old);
+    std::vector<float4> prm(h->n_prm_base);
+    HIP_TRY(hipMemcpyAsync(off_old.data(), d.role_off_o, sizeof(uint32_t) * (N + 1), hipMemcpyDeviceToHost, st));
+    if (R_old) HIP_TRY(hipMemcpyAsync(rec_old.data(), d.role_rec_o, sizeof(RoleRec) * R_old, hipMemcpyDeviceToHost, st));
+    if (!prm.empty()) HIP_TRY(hipMemcpyAsync(prm.data(), d.role_prm, sizeof(float4) * prm.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((size_t)h->n_prm_base + n >= ((size_t)1 << 24)) FAIL(MDX_EPARAM, "more than 16.7 M distinct bonded parameter sets with the restraints");
+    std::vector<uint32_t> which(N, MDX_INVALID);      // atom -> its restraint
+    for (uint32_t k = 0; k < n; ++k) which[h->posre_idx[k]] = k;
+    std::vector<uint32_t> off(N + 1, 0);
+    std::vector<RoleRec> rec;
+    rec.reserve((size_t)R_old + n);
+    for (uint32_t i = 0; i < N; ++i) {
+        for (uint32_t k = off_old[i]; k < off_old[i + 1]; ++k)
+            if ((rec_old[k].meta & 0xFu) != ROLE_POSRE) rec.push_back(rec_old[k]);
+        if (which[i] != MDX_INVALID) {      // last: the cheapest kind (mdx_create orders an atom's roles by cost)
+            const uint32_t k = which[i];
+            RoleRec r{};
+            r.p[0] = i; r.p[1] = 0u; r.p[2] = f2u(h->posre_b[k]);
+            r.meta = ROLE_POSRE | ((h->n_prm_base + k) << 8);
+            rec.push_back(r);
+        }
+        off[i + 1] = (uint32_t)rec.size();
+    }
+    for (uint32_t k = 0; k < n; ++k)
+        prm.push_back(make_float4(h->posre_ref[3 * k], h->posre_ref[3 * k + 1], h->posre_ref[3 * k + 2], h->posre_k[k]));
+    const uint32_t R = (uint32_t)rec.size();
+    h->n_roles = R;
+    h->n_roles_excl = 0; h->n_roles_dih = 0;
+    for (const RoleRec& r : rec) {
+        h->n_roles_excl += (r.meta & 0xFu) == ROLE_EWALD_EXCL ? 1u : 0u;
+        h->n_roles_dih += ((r.meta & 0xFu) != ROLE_BOND && (r.meta & 0xFu) != ROLE_ANGLE) ? 1u : 0u;
+    }
+    MDX_TRY(upload_vec(&d.role_prm, prm, st));
+    MDX_TRY(upload_vec(&d.role_off_o, off, st)); MDX_TRY(upload_vec(&d.role_rec_o, rec, st));
+    MDX_TRY(alloc_n(&d.role_rec_s, R));
+    HIP_TRY(hipStreamSynchronize(st));
+    h->forces_valid = false; h->e_cache_valid = false; h->e_pending = false;
+    return mdx_refill_roles(h);
+}
+
+extern "C" int mdx_set_position_restraints(mdx_handle* h, uint32_t n, const uint32_t* idx, const float* ref, const float* k,
+                                           const float* flat_bottom) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n && (!idx || !k)) FAIL(MDX_EPARAM, "position restraints: missing idx or k");
+    HIP_TRY(hipSetDevice(h->device));
+    const uint32_t N = h->N;
+    std::vector<uint8_t> seen(N, 0), refused(N, 0);      // refused: 1 virtual site, 2 atom of a rigid water stepped by water_step_kernel
+    for (const VSite& v : h->h_vsites) refused[v.site] = 1;
+    for (const ConsGroup& g : h->h_groups)
+        if (g.wstep) for (uint32_t a = 0; a < g.natoms && a < 4; ++a) if (g.atom[a] < N) refused[g.atom[a]] = 2;
+    for (uint32_t q = 0; q < n; ++q) {
+        const uint32_t i = idx[q];
+        if (i >= N) FAIL(MDX_EPARAM, "position restraints: atom index out of range");
+        if (seen[i]) FAIL(MDX_EPARAM, "position restraints: duplicate atom index");
+        seen[i] = 1;
+        if (!(k[q] > 0.f) || !std::isfinite(k[q])) FAIL(MDX_EPARAM, "position restraints: k must be finite and > 0");
+        if (ref) for (int c = 0; c < 3; ++c) if (!std::isfinite(ref[3 * (size_t)q + c])) FAIL(MDX_EPARAM, "position restraints: non-finite reference");
+        if (flat_bottom && !(flat_bottom[q] >= 0.f && std::isfinite(flat_bottom[q]))) FAIL(MDX_EPARAM, "position restraints: flat-bottom radius must be finite and >= 0");
+        if (refused[i] == 1) FAIL(MDX_EPARAM, "position restraints: atom is a virtual site");
+        if (refused[i] == 2) FAIL(MDX_EPARAM, "position restraints: atom of a rigid water stepped by the one-pass water kernel");
+    }
+    std::vector<float> cur;
+    if (n && !ref) {      // the atoms' current positions (between mdx_step calls the state is complete)
+        if (h->dd) FAIL(MDX_EPARAM, "position restraints: a decomposed handle needs explicit references (ref = NULL would be a collective read)");
+        cur.resize(3 * (size_t)N);
+        MDX_TRY(mdx_download(h, MDX_POS, cur.data()));
+    }
+    h->posre_idx.assign(idx, idx + n);
+    h->posre_ref.resize(3 * (size_t)n); h->posre_k.assign(k, k + n); h->posre_b.assign(n, 0.f);
+    for (uint32_t q = 0; q < n; ++q) {
+        if (flat_bottom) h->posre_b[q] = flat_bottom[q];
+        for (int c = 0; c < 3; ++c) {
+            const double r0 = ref ? ref[3 * (size_t)q + c] : cur[3 * (size_t)idx[q] + c];
+            // periodic axis: box-fractional, so the reference follows every box change the way an affinely scaled atom does
+            h->posre_ref[3 * q + c] = h->posre_per[c] ? (float)((r0 - (double)h->box_lo[c]) / ((double)h->box_hi[c] - (double)h->box_lo[c])) : (float)r0;
+        }
+    }
+    h->n_posre = n;
+    return posre_install(h);
+}
+
+extern "C" uint32_t mdx_position_restraints_read(mdx_handle* h, uint32_t capacity, uint32_t* idx, float* ref, float* k, float* flat_bottom) {
+    if (!h) return 0;
+    const uint32_t m = std::min(capacity, h->n_posre);
+    for (uint32_t q = 0; q < m; ++q) {
+        if (idx) idx[q] = h->posre_idx[q];
+        if (k) k[q] = h->posre_k[q];
+        if (flat_bottom) flat_bottom[q] = h->posre_b[q];
+        if (ref)
+            for (int c = 0; c < 3; ++c) {
+                const float f = h->posre_ref[3 * q + c];      // the form the kernels use: box_lo + f L
+                ref[3 * q + c] = h->posre_per[c] ? std::fma(f, h->box_hi[c] - h->box_lo[c], h->box_lo[c]) : f;
+            }
+    }
+    return h->n_posre;
+}
+
+extern "C" int mdx_restraint_energy(mdx_handle* h, double* energy, double* virial) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (energy) *energy = h->posre_e;
+    if (virial) *virial = h->posre_w;
     return MDX_OK;
 }

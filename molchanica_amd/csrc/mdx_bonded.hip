@@ -37,7 +37,8 @@ __device__ __forceinline__ float quad_xadd(float v) {
 // BONDED_LPA lanes per atom: 4 when the system has chains (above), 2 for mixed and 1 for pure-solvent systems - a flexible
 // water atom has 2.3 roles, so with four lanes per atom most of them only read the offsets and leave (1 M-atom water:
 // 36.6 us with 4 lanes, 30.7 with 2, 27.8 with 1).
-template <bool ENERGY, int BONDED_LPA>
+// POSRE: the handle has position restraints (mdx_bonded_dev.h; an eighth and ninth reduced value in the energy flavour)
+template <bool ENERGY, int BONDED_LPA, bool POSRE = false>
 __global__ __launch_bounds__(256) void bonded_gather_kernel(BondedArgs a) {
     if (a.gate && *a.gate > a.thr_bits) return;
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(256) void bonded_gather_kernel(BondedArgs a) {
             float fx = 0.f, fy = 0.f, fz = 0.f;
             for (uint32_t k = rb + q4; k < re; k += BONDED_LPA) {
                 const RoleRec r = a.roles[k];
-                role_eval<ENERGY>(r, a.prm, self, a.posq, a.p, fx, fy, fz, en);
+                role_eval<ENERGY, false, POSRE>(r, a.prm, self, a.posq, a.p, fx, fy, fz, en);
             }
             if (BONDED_LPA >= 2) { fx = quad_xadd<0xB1>(fx); fy = quad_xadd<0xB1>(fy); fz = quad_xadd<0xB1>(fz); }   // lane ^ 1
             if (BONDED_LPA == 4) { fx = quad_xadd<0x4E>(fx); fy = quad_xadd<0x4E>(fy); fz = quad_xadd<0x4E>(fz); }   // lane ^ 2
@@ -64,18 +65,19 @@ __global__ __launch_bounds__(256) void bonded_gather_kernel(BondedArgs a) {
     if (ENERGY) {
         // wave shuffle, then the block's four waves through LDS: one atomic per term and block (one per wave
         // was 7 x 16 k contended atomics at 1 M atoms: 0.42 ms for a 0.04 ms kernel)
-        __shared__ double s_e[4][7];
-        double v[7] = {en.bond, en.angle, en.dih, en.lj14, en.c14, en.rec, en.vir};
-        const int slot[7] = {EN_BOND, EN_ANGLE, EN_DIHEDRAL, EN_LJ14, EN_COUL14, EN_RECIP, EN_VIRIAL};
+        constexpr int NV = POSRE ? 9 : 7;
+        __shared__ double s_e[4][NV];
+        double v[9] = {en.bond, en.angle, en.dih, en.lj14, en.c14, en.rec, en.vir, en.posre, en.posre_vir};
+        const int slot[9] = {EN_BOND, EN_ANGLE, EN_DIHEDRAL, EN_LJ14, EN_COUL14, EN_RECIP, EN_VIRIAL, EN_POSRE, EN_POSRE_VIR};
 #pragma unroll
-        for (int q = 0; q < 7; ++q) {
+        for (int q = 0; q < NV; ++q) {
             double t = v[q];
 #pragma unroll
             for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
             if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6][q] = t;
         }
         __syncthreads();
-        if (threadIdx.x < 7) {
+        if (threadIdx.x < NV) {
             const double t = s_e[0][threadIdx.x] + s_e[1][threadIdx.x] + s_e[2][threadIdx.x] + s_e[3][threadIdx.x];
             if (t != 0.0) atomicAdd(&a.energy[slot[threadIdx.x]], t);
         }
@@ -99,7 +101,7 @@ __global__ void add_ext_kernel(uint32_t S, const uint32_t* __restrict__ orig_of,
 
 bool mdx_bonded_wanted(const mdx_handle* h) {
     const bool skip_bonded = (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) != 0;
-    return h->n_roles && !(skip_bonded && !h->pme_on);
+    return h->n_roles && (!(skip_bonded && !h->pme_on) || h->n_posre);     // (restraints are no force-field term: the overrides keep them)
 }
 void mdx_fill_bonded_params(const mdx_handle* h, BondedParams& p) {
     for (int d = 0; d < 3; ++d) {
@@ -108,6 +110,11 @@ void mdx_fill_bonded_params(const mdx_handle* h, BondedParams& p) {
     }
     p.ewald_beta = h->cfg.ewald_alpha;
     p.skip_bonded = (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) ? 1 : 0;
+    for (int d = 0; d < 3; ++d) {
+        p.box_lo[d] = h->box_lo[d];
+        p.gbox[d] = h->posre_per[d] ? (h->box_hi[d] - h->box_lo[d]) : 0.f;
+        p.inv_gbox[d] = h->posre_per[d] ? 1.0f / p.gbox[d] : 0.f;
+    }
 }
 
 int mdx_launch_bonded(mdx_handle* h, bool energy, const uint32_t* d_gate, uint32_t thr_bits) {
@@ -125,7 +132,18 @@ int mdx_launch_bonded(mdx_handle* h, bool energy, const uint32_t* d_gate, uint32
     const double roles_here = (double)h->n_roles * ((h->n_local != h->N && h->N) ? (double)h->n_local / (double)h->N : 1.0);
     const int lpa = (lpa_env == 1 || lpa_env == 2 || lpa_env == 4) ? lpa_env : (roles_here < 2.6 * (double)h->S ? 1 : (roles_here < 6.0 * (double)h->S ? 2 : 4));
     const dim3 g((uint32_t)(((size_t)h->S * lpa + 255) / 256)), b(256);
-    if (lpa == 1) {
+    if (h->n_posre) {      // restrained handle: the flavours with the ROLE_POSRE branch
+        if (lpa == 1) {
+            if (energy) hipLaunchKernelGGL((bonded_gather_kernel<true, 1, true>), g, b, 0, h->stream, a);
+            else hipLaunchKernelGGL((bonded_gather_kernel<false, 1, true>), g, b, 0, h->stream, a);
+        } else if (lpa == 2) {
+            if (energy) hipLaunchKernelGGL((bonded_gather_kernel<true, 2, true>), g, b, 0, h->stream, a);
+            else hipLaunchKernelGGL((bonded_gather_kernel<false, 2, true>), g, b, 0, h->stream, a);
+        } else {
+            if (energy) hipLaunchKernelGGL((bonded_gather_kernel<true, 4, true>), g, b, 0, h->stream, a);
+            else hipLaunchKernelGGL((bonded_gather_kernel<false, 4, true>), g, b, 0, h->stream, a);
+        }
+    } else if (lpa == 1) {
         if (energy) hipLaunchKernelGGL((bonded_gather_kernel<true, 1>), g, b, 0, h->stream, a);
         else hipLaunchKernelGGL((bonded_gather_kernel<false, 1>), g, b, 0, h->stream, a);
     } else if (lpa == 2) {

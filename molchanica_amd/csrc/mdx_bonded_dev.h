@@ -25,7 +25,7 @@ __device__ __forceinline__ float4 step_pos(const float4 y, const float4 f) {
     return make_float4(fmaf(f.w, f.x, y.x), fmaf(f.w, f.y, y.y), fmaf(f.w, f.z, y.z), y.w);
 }
 
-struct RoleEnergies { double bond = 0.0, angle = 0.0, dih = 0.0, lj14 = 0.0, c14 = 0.0, rec = 0.0, vir = 0.0; };
+struct RoleEnergies { double bond = 0.0, angle = 0.0, dih = 0.0, lj14 = 0.0, c14 = 0.0, rec = 0.0, vir = 0.0, posre = 0.0, posre_vir = 0.0; };
 
 // Adds to (fx, fy, fz) the force of role `r` on its own atom (position `self`).  ENERGY: the term's energy and
 // virial are credited once, by the atom in role 0.
@@ -34,20 +34,22 @@ struct RoleEnergies { double bond = 0.0, angle = 0.0, dih = 0.0, lj14 = 0.0, c14
 // NODIH: the caller knows the system has bond and angle roles only (a box of flexible water): the dihedral branch - a third of the
 // function's registers -, the 1-4 pairs and the Ewald exclusion corrections are compiled out (the fused bonded + kick + drift pass:
 // 93 -> 67 VGPRs, five -> seven waves per SIMD)
-template <bool ENERGY, bool NODIH = false>
+// POSRE: the handle has position restraints (ROLE_POSRE records); without it a kind-5 record would take the dihedral branch, and the
+// flavours of unrestrained handles keep exactly their code
+template <bool ENERGY, bool NODIH = false, bool POSRE = false>
 __device__ __forceinline__ void role_compute(const RoleRec& r, const float4 prm4, const float4 self, const float4 q0, const float4 q1,
                                              const float4* __restrict__ posq,
                                              const BondedParams& p, float& fx, float& fy, float& fz, RoleEnergies& en,
                                              const float4* __restrict__ fstep = nullptr);
 
-template <bool ENERGY, bool NODIH = false>
+template <bool ENERGY, bool NODIH = false, bool POSRE = false>
 __device__ __forceinline__ void role_eval(const RoleRec& r, const float4* __restrict__ prm_tab, const float4 self,
                                           const float4* __restrict__ posq,
                                           const BondedParams& p, float& fx, float& fy, float& fz, RoleEnergies& en) {
     const uint32_t kind = r.meta & 0xFu;
     const float4 q0 = posq[r.p[0]];
     const float4 q1 = (kind == ROLE_ANGLE || kind == ROLE_DIHEDRAL) ? posq[r.p[1]] : q0;
-    role_compute<ENERGY, NODIH>(r, prm_tab[r.meta >> 8], self, q0, q1, posq, p, fx, fy, fz, en);
+    role_compute<ENERGY, NODIH, POSRE>(r, prm_tab[r.meta >> 8], self, q0, q1, posq, p, fx, fy, fz, en);
 }
 
 // (positions in the step form - posq = Y, fstep = the force rows beside it: role_eval_step)
@@ -61,7 +63,7 @@ __device__ __forceinline__ void role_eval_step(const RoleRec& r, const float4* _
     role_compute<ENERGY>(r, prm_tab[r.meta >> 8], self, q0, q1, y, p, fx, fy, fz, en, fstep);
 }
 
-template <bool ENERGY, bool NODIH>
+template <bool ENERGY, bool NODIH, bool POSRE>
 __device__ __forceinline__ void role_compute(const RoleRec& r, const float4 prm4, const float4 self, const float4 q0, const float4 q1,
                                              const float4* __restrict__ posq,
                                              const BondedParams& p, float& fx, float& fy, float& fz, RoleEnergies& en,
@@ -78,6 +80,27 @@ __device__ __forceinline__ void role_compute(const RoleRec& r, const float4 prm4
         const float fs = -prm[0] * (er * rinv - 1.1283791671f * p.ewald_beta * __expf(-br * br)) * rinv * rinv;
         fx += fs * d.x; fy += fs * d.y; fz += fs * d.z;
         if (ENERGY && role == 0) { e_rec -= (double)(prm[0] * er * rinv); e_vir += (double)(fs * r2); }
+        return;
+    }
+    if (POSRE && kind == ROLE_POSRE) {
+        // position restraint E = k max(0, |d| - b)^2, d = x - r0 (minimum image on the periodic axes, where r0 = box_lo + f L follows
+        // the box); prm4 = (f or r0, k), b = the float bits of p[2].  Not a force-field term: the overrides leave it alone
+        const float b = __uint_as_float(r.p[2]);
+        float3 d = make_float3(self.x - (p.gbox[0] > 0.f ? fmaf(prm4.x, p.gbox[0], p.box_lo[0]) : prm4.x),
+                               self.y - (p.gbox[1] > 0.f ? fmaf(prm4.y, p.gbox[1], p.box_lo[1]) : prm4.y),
+                               self.z - (p.gbox[2] > 0.f ? fmaf(prm4.z, p.gbox[2], p.box_lo[2]) : prm4.z));
+        if (p.gbox[0] > 0.f) d.x -= rintf(d.x * p.inv_gbox[0]) * p.gbox[0];
+        if (p.gbox[1] > 0.f) d.y -= rintf(d.y * p.inv_gbox[1]) * p.gbox[1];
+        if (p.gbox[2] > 0.f) d.z -= rintf(d.z * p.inv_gbox[2]) * p.gbox[2];
+        const float r2 = dot3(d, d), rr = sqrtf(r2), ex = rr - b;
+        if (ex > 0.f) {      // (b >= 0: rr > 0 here)
+            const float fs = -2.0f * prm4.w * ex / rr;
+            fx += fs * d.x; fy += fs * d.y; fz += fs * d.z;
+            if (ENERGY) {      // virial d . F: with references that scale with the box, -dE/dlambda of a uniform scaling
+                en.posre += (double)prm4.w * ex * ex;
+                en.posre_vir += (double)(fs * r2); e_vir += (double)(fs * r2);
+            }
+        }
         return;
     }
     if (p.skip_bonded) return;

@@ -2463,3 +2463,21 @@ int mdx_extract_neighbors(mdx_handle* h, uint32_t* offsets, uint32_t* idx) {
     std::copy(new_off.begin(), new_off.end(), offsets);
     return MDX_OK;
 }
+
+// The caller-order role tables changed (mdx_set_position_restraints): the slot-order lists of the current slot order are filled
+// again - the count / scan / fill of a rebuild without the rest of it.  The slot order, the pair list and (decomposed) the owned and
+// ghost sets stay as they are: a restraint role has no partner, so no atom has to join the halo.
+int mdx_refill_roles(mdx_handle* h) {
+    if (!h->in_slot_space || !h->list_valid || !h->n_roles) return MDX_OK;      // (the next rebuild fills them)
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t S = h->S;
+    hipLaunchKernelGGL(role_count_kernel, dim3(div_up(S + 1, 256)), dim3(256), 0, st, S, d.orig_of, d.gid,
+                       d.lflag, d.role_off_o, d.role_cnt_s);
+    MDX_TRY(mdx_exclusive_scan_u32(h, d.role_cnt_s, d.role_off_s, S + 1));
+    hipLaunchKernelGGL(role_fill_kernel, dim3(div_up(S, 256)), dim3(256), 0, st, S, d.orig_of, d.gid, d.lflag,
+                       d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return MDX_OK;
+}

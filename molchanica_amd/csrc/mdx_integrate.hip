@@ -123,7 +123,8 @@ __device__ __forceinline__ void pipe_publish(const FusedArgs& a, uint32_t word) 
     for (uint32_t q = 0; q < a.n_flag; ++q) a.send_buf[a.flag_rows[q]] = make_float4(__uint_as_float(word), 0.f, 0.f, 0.f);
     for (int k = 0; k < 9; ++k) a.pc->m1_shard[k] = 0u;
 }
-template <bool DUAL, bool PIPE, bool NODIH = false>
+// POSRE: a restrained handle (ROLE_POSRE records; they count as neither bond nor angle roles, so NODIH is off there)
+template <bool DUAL, bool PIPE, bool NODIH = false, bool POSRE = false>
 __global__ __launch_bounds__(256) void bonded_integrate_kernel(FusedArgs a) {
     uint32_t gate = a.gate_in ? *a.gate_in : 0u;
     if (PIPE && (a.pipe_flags & 1u))       // what the ranks below this one found during the last drift came back with their ghost forces
@@ -165,10 +166,10 @@ __global__ __launch_bounds__(256) void bonded_integrate_kernel(FusedArgs a) {
             }
 #pragma unroll
             for (int i = 0; i < FUSED_PRE; ++i)
-                if (rb + (uint32_t)i < re) role_compute<false, NODIH>(rr[i], prm[i], p, q0[i], q1[i], a.posq_in, a.p, f.x, f.y, f.z, en);
+                if (rb + (uint32_t)i < re) role_compute<false, NODIH, POSRE>(rr[i], prm[i], p, q0[i], q1[i], a.posq_in, a.p, f.x, f.y, f.z, en);
             for (uint32_t k = rb + FUSED_PRE; k < re; ++k) {
                 const RoleRec r = a.roles[k];
-                role_eval<false, NODIH>(r, a.prm, p, a.posq_in, a.p, f.x, f.y, f.z, en);
+                role_eval<false, NODIH, POSRE>(r, a.prm, p, a.posq_in, a.p, f.x, f.y, f.z, en);
             }
             const float kdt = a.dt * v.w;
             v.x += kdt * f.x; v.y += kdt * f.y; v.z += kdt * f.z;
@@ -427,7 +428,15 @@ int mdx_launch_bonded_integrate(mdx_handle* h, float dt, const uint32_t* d_gate_
     // SIMD instead of five for a pass that lives on loads in flight.  MDX_FUSED_NODIH=0: A/B (read per launch)
     const char* nd_env = std::getenv("MDX_FUSED_NODIH");
     const bool nodih = h->n_roles_dih == 0 && !(nd_env && nd_env[0] == '0');
-    if (pipe) {
+    if (h->n_posre) {      // restrained handle: the generic flavour with the ROLE_POSRE branch
+        if (pipe) {
+            if (dual) hipLaunchKernelGGL((bonded_integrate_kernel<true, true, false, true>), g, b, 0, h->stream, a);
+            else hipLaunchKernelGGL((bonded_integrate_kernel<false, true, false, true>), g, b, 0, h->stream, a);
+        } else {
+            if (dual) hipLaunchKernelGGL((bonded_integrate_kernel<true, false, false, true>), g, b, 0, h->stream, a);
+            else hipLaunchKernelGGL((bonded_integrate_kernel<false, false, false, true>), g, b, 0, h->stream, a);
+        }
+    } else if (pipe) {
         if (dual) { if (nodih) hipLaunchKernelGGL((bonded_integrate_kernel<true, true, true>), g, b, 0, h->stream, a); else hipLaunchKernelGGL((bonded_integrate_kernel<true, true>), g, b, 0, h->stream, a); }
         else hipLaunchKernelGGL((bonded_integrate_kernel<false, true>), g, b, 0, h->stream, a);
     } else {

@@ -35,7 +35,8 @@
 
 #define MDX_ESTRIDE 5   // {lj, coulomb, virial, cross (alchemical: unscaled energy of the coupled pairs), dU/dlambda} per slot
 #define MDX_EPART 256   // the pair kernel spreads its energy atomics over this many slots (contended f64 atomics cost ~10 ns each)
-enum { EN_BOND = 0, EN_ANGLE, EN_DIHEDRAL, EN_LJ, EN_COUL, EN_LJ14, EN_COUL14, EN_KIN, EN_RECIP, EN_VIRIAL, EN_COUNT };
+// EN_POSRE / EN_POSRE_VIR: the position restraints' energy and their share of EN_VIRIAL (mdx_set_position_restraints)
+enum { EN_BOND = 0, EN_ANGLE, EN_DIHEDRAL, EN_LJ, EN_COUL, EN_LJ14, EN_COUL14, EN_KIN, EN_RECIP, EN_VIRIAL, EN_POSRE, EN_POSRE_VIR, EN_COUNT };
 
 struct GridParams {
     float lo[3];       // origin of the column grid (box_lo, or bounding box in vacuum)
@@ -97,6 +98,9 @@ struct BondedParams {
     int geometric, lj_on, coul_on;
     float ewald_beta;    // ROLE_EWALD_EXCL: remove erf(beta r)/r of pairs the real-space sum skips
     int skip_bonded;     // MdOverrides.bonded_disabled: keep only the Ewald exclusion corrections
+    // ROLE_POSRE (last: the fields above keep their offsets): origin and edges of the GLOBAL box (0: an axis the system is not periodic
+    // along) - a rank of a decomposed box is not periodic locally in a cut dimension, its restraints still are
+    float box_lo[3], gbox[3], inv_gbox[3];
 };
 
 // Control block in device memory: the rebuild trigger.  disp2[s] holds, as the bit pattern of a
@@ -133,7 +137,7 @@ struct OnePassNow {      // what mdx_launch_nonbonded adds to the argument block
 struct __attribute__((aligned(128))) PipeCtl { uint32_t m1_shard[16]; uint32_t rows_overflow; uint32_t pad[15]; };
 
 // One (term, atom-of-that-term) record of the atom-owned bonded gather (mdx_bonded.hip).
-enum { ROLE_BOND = 0, ROLE_ANGLE = 1, ROLE_DIHEDRAL = 2, ROLE_PAIR14 = 3, ROLE_EWALD_EXCL = 4 };
+enum { ROLE_BOND = 0, ROLE_ANGLE = 1, ROLE_DIHEDRAL = 2, ROLE_PAIR14 = 3, ROLE_EWALD_EXCL = 4, ROLE_POSRE = 5 };
 // 16 bytes: the parameters live in a table of DISTINCT parameter sets (role_prm: a force field has a few hundred; the
 // two of a water box sit in L1), which halves the record stream the gather reads - 2.33 roles per water atom.
 struct __attribute__((aligned(16))) RoleRec {
@@ -141,6 +145,9 @@ struct __attribute__((aligned(16))) RoleRec {
     uint32_t meta;   // kind | role << 4 | parameter-set index << 8   (role = this atom's position in the term)
 };
 // role_prm[index] (float4): bond: k, r0 | angle: k, theta0 | dihedral: v, phase, n | 1-4: sigma, 4 s eps, s ke qq | Ewald exclusion: ke qq
+// | position restraint: reference x, y, z (box-fractional on a periodic axis, A on the others), k - one set per restraint, behind
+// the force field's sets; its record keeps p[0] = the atom itself, p[1] = 0 (a valid slot: the fused pass prefetches it) and the
+// flat-bottom radius as the float bits of p[2] (translated for dihedrals only)
 
 // A cluster of atoms tied by distance constraints (rigid water: 3 atoms / 3 constraints; X-H3: 4 / 3).
 struct __attribute__((aligned(16))) ConsGroup {
@@ -295,6 +302,13 @@ struct mdx_handle {
     uint32_t n_roles = 0;
     uint32_t n_roles_excl = 0;        // ... of which Ewald exclusion corrections (ROLE_EWALD_EXCL)
     uint32_t n_roles_dih = 0;         // ... of which neither bond nor angle roles (none: the fused bonded + kick + drift pass runs a flavour without the other branches)
+    // position restraints (mdx_set_position_restraints): one ROLE_POSRE record each, last in its atom's list, counted in n_roles and
+    // n_roles_dih.  The host keeps the caller's table (references in the stored form: box-fractional on a periodic axis); n_prm_base:
+    // parameter sets of the force field, the restraints' sets follow them
+    uint32_t n_posre = 0, n_prm_base = 0;
+    int posre_per[3] = {0, 0, 0};          // periodicity of the system as created (mdx_set_local_atoms narrows per[] to the local region)
+    std::vector<uint32_t> posre_idx; std::vector<float> posre_ref, posre_k, posre_b;
+    double posre_e = 0.0, posre_w = 0.0;   // the restraints' share of the evaluation mdx_energy last reported
     bool excl_inside_rigid = false;   // every excluded pair lies inside ONE rigid three-site cluster (its virtual site included)
     uint32_t n_groups = 0, n_cons = 0, n_vsites = 0;   // constraint clusters of up to four atoms / constraints / virtual sites
     uint32_t n_star5 = 0; std::vector<ConsStar5> h_star5;   // X-H4 clusters (caller order)
@@ -470,6 +484,7 @@ int mdx_unsort_state(mdx_handle* h);  // slot space -> pos_orig / vel_orig
 int mdx_gather_to_orig(mdx_handle* h, const float4* slot_arr, float4* orig_arr);
 int mdx_extract_neighbors(mdx_handle* h, uint32_t* offsets, uint32_t* idx);
 int mdx_classify_tiles(mdx_handle* h, bool by_length);
+int mdx_refill_roles(mdx_handle* h);   // caller-order role tables changed: refill the slot-order lists for the current slot order
 int mdx_order_tiles_by_length(mdx_handle* h, bool grouped);   // tile_lpt: longest lists first
 // forces
 // part: 0 = every tile; 1 = the interior tiles of a decomposed handle (no ghost in their lists: they run while the halo

@@ -131,7 +131,7 @@ bool mdx_onepass_ok(const mdx_handle* h) {
                           (int)h->dual_on, (int)h->path_split, h->d.force_b != nullptr, (int)mdx_bonded_integrate_ok(h), mdx_nb_variant(h), mdx_nb_wpt_half(h, h->T), h->T);
     if (h->onepass_refused || h->dd || !h->dual_on || !h->path_split || !h->d.force_b) return false;
     if (mdx_nb_variant(h) != 5 || h->integrator != MDX_INTEGRATOR_VERLET_VELOCITY || mdx_has_constraints(h) || h->n_vsites != 0 || h->pme_on ||
-        h->have_ext || h->n_local != h->N || h->alch_on || h->d.posq_alt == nullptr) return false;
+        h->have_ext || h->n_posre || h->n_local != h->N || h->alch_on || h->d.posq_alt == nullptr) return false;      // (restraint roles in the pair launch's role walk: not built)
     if (wpt == 1 && !mdx_bonded_integrate_ok(h)) return false;
     if (h->profile && h->profile_level < 2) return false;      // (event brackets around every kernel count launches per kind: they keep the separate passes)
     // the pair kernel's flavours that exist in this form (mdx_nonbonded_impl.h NB_STEP): orthorhombic periodic cells, not the softened Coulomb
@@ -182,7 +182,7 @@ int mdx_launch_nonbonded(mdx_handle* h, bool energy, const uint32_t* d_gate, uin
     // decides; mdx_launch_bonded then finds bonded_fused set).  MDX_FUSE_BONDED=0: A/B knob.
     static const bool fuse_bonded = [] { const char* e = std::getenv("MDX_FUSE_BONDED"); return !(e && e[0] == '0'); }();
     h->bonded_fused = false;
-    if (fuse_bonded && a.inner && part == 0 && mdx_bonded_wanted(h) && !h->bonded_deferred && (!h->profile || h->profile_level >= 2)) {
+    if (fuse_bonded && a.inner && part == 0 && mdx_bonded_wanted(h) && !h->n_posre && !h->bonded_deferred && (!h->profile || h->profile_level >= 2)) {
         a.b_S = h->S; a.b_role_off = h->d.role_off_s; a.b_roles = h->d.role_rec_s; a.b_prm = h->d.role_prm;
         mdx_fill_bonded_params(h, a.b_p);
     }

@@ -158,6 +158,10 @@ def load_library():
     lib.mdx_single_point_between_mols.argtypes = [C.POINTER(CSystem), C.POINTER(CConfig), C.c_int, C.c_void_p, C.c_uint32,
                                                   C.POINTER(CEnergies), _fp, _fp]
     lib.mdx_comm_info.argtypes = [H, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _u32p, _u32p, _fp]
+    lib.mdx_set_position_restraints.argtypes = [H, C.c_uint32, _u32p, _fp, _fp, _fp]
+    lib.mdx_position_restraints_read.argtypes = [H, C.c_uint32, _u32p, _fp, _fp, _fp]
+    lib.mdx_position_restraints_read.restype = C.c_uint32
+    lib.mdx_restraint_energy.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = lib
     return lib
 
@@ -257,6 +261,42 @@ class MdState:
         out = np.zeros((max(n, 1), max(n, 1)), dtype=np.float32)
         _check(lib.mdx_energy_between_mols(self._h, out.ctypes.data_as(_fp), n))
         return out
+
+    # -- position restraints (include/mdx.h: E = k max(0, |x - r0| - b)^2) ------------------------------------------------
+    def set_position_restraints(self, idx, ref=None, k=1.0, flat_bottom=None):
+        """Replaces the whole restraint set.  idx: atom indices; ref: [n, 3] A or None = the atoms' current positions;
+        k (kcal/mol/A^2) and flat_bottom (A) scalars or [n] arrays.  An empty idx clears the set."""
+        ii = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        n = ii.shape[0]
+        if n == 0:
+            self.clear_position_restraints()
+            return
+        kk = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.float32), (n,)))
+        bb = None if flat_bottom is None else np.ascontiguousarray(np.broadcast_to(np.asarray(flat_bottom, dtype=np.float32), (n,)))
+        rr = None if ref is None else np.ascontiguousarray(ref, dtype=np.float32).reshape(n, 3)
+        _check(load_library().mdx_set_position_restraints(
+            self._h, n, ii.ctypes.data_as(_u32p), None if rr is None else rr.ctypes.data_as(_fp), kk.ctypes.data_as(_fp),
+            None if bb is None else bb.ctypes.data_as(_fp)))
+
+    def clear_position_restraints(self):
+        _check(load_library().mdx_set_position_restraints(self._h, 0, None, None, None, None))
+
+    def position_restraints(self) -> dict:
+        """-> {"idx", "ref" (Cartesian A after any box change), "k", "flat_bottom"} in the order of the last set."""
+        lib = load_library()
+        n = int(lib.mdx_position_restraints_read(self._h, 0, None, None, None, None))
+        idx = np.zeros(n, np.uint32); ref = np.zeros((n, 3), np.float32); k = np.zeros(n, np.float32); b = np.zeros(n, np.float32)
+        if n:
+            lib.mdx_position_restraints_read(self._h, n, idx.ctypes.data_as(_u32p), ref.ctypes.data_as(_fp), k.ctypes.data_as(_fp),
+                                             b.ctypes.data_as(_fp))
+        return {"idx": idx, "ref": ref, "k": k, "flat_bottom": b}
+
+    def restraint_energy(self) -> dict:
+        """The restraints' share of the evaluation energy() last reported: {"energy" (kcal/mol, in potential and
+        potential_bonded), "virial" (kcal/mol, in virial)}."""
+        e, w = C.c_double(0.0), C.c_double(0.0)
+        _check(load_library().mdx_restraint_energy(self._h, C.byref(e), C.byref(w)))
+        return {"energy": float(e.value), "virial": float(w.value)}
 
     def _download(self, which: int) -> np.ndarray:
         out = np.empty((self.n_atoms, 3), dtype=np.float32)
