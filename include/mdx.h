@@ -373,6 +373,24 @@ int mdx_set_integrator(mdx_handle* h, int kind, float gamma_per_ps, float temper
 int mdx_set_alchemical_softcore(mdx_handle* h, float alpha, float sigma_min);
 int mdx_configure_alchemical_window(mdx_handle* h, uint32_t mol_index, double lambda);
 
+/* Foreign-lambda energies: the inputs of BAR / MBAR (GROMACS `calc-lambda-neighbors`).  For a handle with an alchemical window at
+ * lambda and a configured list lambda_1 .. lambda_K (0 <= lambda_k <= 1, K <= MDX_MAX_FOREIGN_LAMBDAS):
+ *     dU_k = U(lambda_k) - U(lambda) at the current positions,
+ * U being the `potential` mdx_energy would report if the window were reconfigured to lambda_k.  Under the coupling form above
+ * only the cross pairs ((1 - lambda) u(r_sc(lambda)), same cutoffs, Coulomb treatment, shifts and images as the forces) and the
+ * SPME reciprocal sum (linear in lambda: (lambda_k - lambda) x its dU/dlambda, exact) depend on lambda; everything else cancels.
+ * One extra pass over the pair list of the cross pairs, no float atomics: the same state gives the same bits; lambda_k == lambda
+ * gives exactly 0.  The list survives mdx_configure_alchemical_window; n = 0 clears it.  While a window is on and the list is set,
+ * every stored snapshot carries its K values (mdx_snapshot_read_foreign; a window switched off keeps the list, its snapshots carry
+ * none; mdx_flush_snapshot_queues drops them with the snapshots).  mdx_foreign_energies is collective on a decomposed handle.
+ * MDX_EPARAM: K > 32, a value outside [0, 1] or not finite, n not the configured / stored count, no active window (the state
+ * stays untouched); MDX_ENAN: a non-finite dU_k. */
+#define MDX_MAX_FOREIGN_LAMBDAS 32
+int      mdx_set_foreign_lambdas(mdx_handle* h, uint32_t n, const double* lambdas);
+int      mdx_foreign_energies(mdx_handle* h, double* du /* [n] */, uint32_t n);      /* dU_k of the current state, kcal/mol */
+uint32_t mdx_snapshot_foreign_count(const mdx_handle* h, uint32_t k);               /* 0: taken without foreign lambdas */
+int      mdx_snapshot_read_foreign(mdx_handle* h, uint32_t k, double* du, uint32_t n);
+
 #define MDX_BAROSTAT_NONE      0
 #define MDX_BAROSTAT_BERENDSEN 1 /* mu^3 = 1 - compressibility (Dt/tau) (P0 - P); box and coordinates scaled by mu */
 #define MDX_BAR_PER_KCAL_MOL_A3 69476.95

@@ -65,6 +65,7 @@ struct Snapshot {
     mdx_energies energy_data{};
     std::vector<float> atom_posits;       // [3N]
     std::vector<float> atom_velocities;   // [3N] or empty
+    std::vector<double> foreign_du;       // [K] dU_k of the foreign lambdas (mdx_set_foreign_lambdas), or empty
 };
 
 /// `SimBox {bounds_low, bounds_high}` (src/properties/sol_shrinking_box.rs:600-603).
@@ -121,9 +122,9 @@ public:
         check(mdx_create(&system, &cfg, device, &h));
         return MdState(h, system.n_atoms);
     }
-    MdState(MdState&& o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_), n_waters_(o.n_waters_), water_sites_(o.water_sites_) {}
+    MdState(MdState&& o) noexcept : h_(std::exchange(o.h_, nullptr)), n_(o.n_), n_waters_(o.n_waters_), water_sites_(o.water_sites_), n_foreign_(o.n_foreign_) {}
     MdState& operator=(MdState&& o) noexcept {
-        if (this != &o) { reset(); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; n_waters_ = o.n_waters_; water_sites_ = o.water_sites_; }
+        if (this != &o) { reset(); h_ = std::exchange(o.h_, nullptr); n_ = o.n_; n_waters_ = o.n_waters_; water_sites_ = o.water_sites_; n_foreign_ = o.n_foreign_; }
         return *this;
     }
     MdState(const MdState&) = delete;
@@ -234,6 +235,16 @@ public:
 
     /// Soft core of the alchemical window (alpha = 0: linear coupling).
     void set_alchemical_softcore(float alpha = 0.5f, float sigma_min = 3.f) { check(mdx_set_alchemical_softcore(h_, alpha, sigma_min)); }
+    /// Foreign lambdas of the window (at most MDX_MAX_FOREIGN_LAMBDAS; empty clears) and dU_k = U(lambda_k) - U(lambda) of the current state.
+    void set_foreign_lambdas(const std::vector<double>& lambdas) {
+        check(mdx_set_foreign_lambdas(h_, (uint32_t)lambdas.size(), lambdas.empty() ? nullptr : lambdas.data()));
+        n_foreign_ = (uint32_t)lambdas.size();
+    }
+    std::vector<double> foreign_energies() {
+        std::vector<double> du(n_foreign_);
+        check(mdx_foreign_energies(h_, du.data(), n_foreign_));
+        return du;
+    }
 
     /// `md.water` (src/properties/sol_shrinking_box.rs:605-613): where the waters sit in the flat atom array ...
     void set_water_layout(uint32_t first_atom, uint32_t n_waters, uint32_t sites_per_water) {
@@ -282,6 +293,8 @@ public:
             if (with_velocities) s.atom_velocities.resize(3 * (size_t)n_);
             check(mdx_snapshot_read(h_, k, &s.time_ps, &s.step, &s.energy_data, s.atom_posits.data(),
                                     with_velocities ? s.atom_velocities.data() : nullptr));
+            s.foreign_du.resize(mdx_snapshot_foreign_count(h_, k));
+            if (!s.foreign_du.empty()) check(mdx_snapshot_read_foreign(h_, k, s.foreign_du.data(), (uint32_t)s.foreign_du.size()));
         }
         return out;
     }
@@ -317,7 +330,7 @@ private:
         check(mdx_upload(h_, which, v.data()));
     }
     mdx_handle* h_ = nullptr;
-    uint32_t n_ = 0, n_waters_ = 0, water_sites_ = 0;
+    uint32_t n_ = 0, n_waters_ = 0, water_sites_ = 0, n_foreign_ = 0;
 };
 
 /// ncclGetUniqueId through the library (rank 0; hand the bytes to the other ranks).

@@ -147,7 +147,7 @@ static void free_device(mdx_handle* h) {
                     d.mchunk_cnt, d.mchunk_off, d.entries, d.entries_in, d.inner_nch, d.list_cursors, d.masks, d.role_off_o, d.role_rec_o, d.role_cnt_s,
                     d.role_off_s, d.role_rec_s, d.role_prm, d.ctl, d.energy,
                     d.flags_dev, d.bbox_red, d.pair_count, d.inner_count, d.pme_force, d.wstep_s, d.path, d.dprune, d.force_b, d.force_c, d.cons_o, d.cons_s, d.cons_tmp, d.cons_mask, d.cons_cnt, d.cons_off, d.cons_vir, d.vsite_o, d.vsite_s, d.gsite_o, d.gsite_s, d.gsite_tmp, d.pme_q, d.pme_f,
-                    d.pme_theta, d.pme_q2, d.pme_f2, d.scratch4, d.tile_bnd, d.tile_scan, d.tile_order, d.tile_lpt, d.rb_ctl, d.scan_chain, d.grp, d.grp_mat, d.star_o, d.star_s, d.ewald_tab};
+                    d.pme_theta, d.pme_q2, d.pme_f2, d.scratch4, d.tile_bnd, d.tile_scan, d.tile_order, d.tile_lpt, d.rb_ctl, d.scan_chain, d.grp, d.grp_mat, d.fl_hot, d.fl_slab, d.star_o, d.star_s, d.ewald_tab};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     d = DeviceState{};
 }
@@ -466,6 +466,7 @@ static int ctl_to_host(mdx_handle* h) {
 static int compute_forces(mdx_handle* h, bool energy, const uint32_t* gate, uint32_t thr) {
     MdxRange range_forces(energy ? "mdx forces+energies" : "mdx forces");
     if (energy) h->stats.energy_evaluations++;
+    h->alch_recip_ok = false;                              // (energy_tail sets it again)
     MDX_TRY(mdx_launch_vsite_construct(h, gate, thr));     // massless sites follow their parents
     bool split = false;
     if (h->dd && h->dd->halo_pending) {                    // decomposed handle, step loop: ghost positions travel now
@@ -1009,7 +1010,7 @@ int mdx_finalize_energy_cache(mdx_handle* h) {
     // (the thermostat's own kinetic-energy launch added into the same word; the force maximum next to it is idempotent)
     HIP_TRY(hipMemsetAsync(h->d.energy + EN_KIN, 0, sizeof(double), h->stream));
     MDX_TRY(energy_tail(h, &h->e_cache));
-    h->e_cache_valid = true; h->e_cache_step = h->step_count;
+    h->e_cache_valid = true; h->e_cache_step = h->step_count; h->e_cache_recip_dudl = h->alch_recip_dudl;
     return MDX_OK;
 }
 
@@ -1018,6 +1019,7 @@ int mdx_energy_impl(mdx_handle* h, mdx_energies* out) {
     HIP_TRY(hipSetDevice(h->device));
     if (h->e_cache_valid && h->e_cache_step == h->step_count && h->forces_valid && h->list_valid && !h->cons_dirty) {
         *out = h->e_cache;      // the step loop evaluated them with the forces of this step (mdx_set_energy_cadence)
+        h->alch_recip_dudl = h->e_cache_recip_dudl; h->alch_recip_ok = true; h->alch_recip_step = h->step_count;
         h->stats.energies_from_step_loop++;
         return MDX_OK;
     }
@@ -1078,6 +1080,8 @@ static int energy_tail(mdx_handle* h, mdx_energies* out) {
         out->virial = e[EN_VIRIAL] + (h->pme_on ? 3.0 * h->ewald_background : 0.0);
         out->pressure = (2.0 * out->kinetic + out->virial) / (3.0 * out->volume) * MDX_BAR_PER_KCAL_MOL_A3;
     }
+    h->alch_recip_dudl = h->alch_on && h->pme_on ? e[EN_COUNT + 5] : 0.0;     // (foreign-lambda energies: mdx_foreign.hip)
+    h->alch_recip_ok = true; h->alch_recip_step = h->step_count;
     if (h->alch_on) {
         // (with the SPME reciprocal sum: + its dU/dlambda = -2 E_env,mol; the real-space cross energy is the "coupled interaction")
         out->dh_dlambda = du_dl + (h->pme_on ? e[EN_COUNT + 5] : 0.0);

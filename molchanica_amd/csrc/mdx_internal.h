@@ -276,6 +276,8 @@ struct DeviceState {
     unsigned long long* scan_chain = nullptr;   // [64] chained-window scans: (generation << 32) | running total per window, then the windows' done ticks
     // energy between molecules / groups (mdx_groups.hip): group of every GLOBAL atom, and the raw n x n sums
     uint8_t* grp = nullptr; double* grp_mat = nullptr;
+    // foreign-lambda energies (mdx_foreign.hip): [S / 8] cluster holds a coupled atom; [FOREIGN_BLOCKS x 32] partial sums + [32] totals
+    uint8_t* fl_hot = nullptr; uint32_t fl_hot_cap = 0; double* fl_slab = nullptr;
     float4* ewald_tab = nullptr;   // Ewald real space: table of the smooth part of the force (mdx_pair_dev.h)
 };
 
@@ -342,6 +344,9 @@ struct mdx_handle {
     std::vector<uint8_t> grp_host; uint32_t n_grp = 0; bool grp_by_mol = false;   // mdx_set_energy_groups: group of every atom (0: no matrix is kept)
     bool alch_on = false; double alch_lambda = 0.0; uint32_t alch_lo = 0, alch_hi = 0;
     float sc_alpha = 0.5f, sc_sigma_min = 3.0f;   // soft core of the alchemical window (mdx_set_alchemical_softcore)
+    std::vector<double> foreign_lams;             // mdx_set_foreign_lambdas (survives window changes; empty: none)
+    double alch_recip_dudl = 0.0, e_cache_recip_dudl = 0.0;   // SPME reciprocal dU/dlambda of the last energy evaluation / of e_cache
+    bool alch_recip_ok = false; uint64_t alch_recip_step = 0;  // ... still that of the current state (cleared by every force call)
     // grid
     GridParams grid{};
     uint32_t ncol = 0, ncells = 0;
@@ -424,7 +429,8 @@ struct mdx_handle {
     uint32_t snap_every = 0; bool snap_vel = false;
     uint32_t snap_handlers[MDX_SNAP_HANDLERS] = {};   // mdx_set_snapshot_handlers: cadence per handler (0 = off); snap_every stays the plain cadence of mdx_set_snapshot_cadence
     double time_ps = 0.0;
-    struct Snapshot { double time; uint64_t step; mdx_energies e; std::vector<float> pos, vel, frc; std::vector<mdx_hbond> hbonds; std::vector<float> between; uint32_t handler_mask = 0; };
+    struct Snapshot { double time; uint64_t step; mdx_energies e; std::vector<float> pos, vel, frc; std::vector<mdx_hbond> hbonds; std::vector<float> between; uint32_t handler_mask = 0;
+                      std::vector<double> foreign; };   // foreign: dU_k of mdx_set_foreign_lambdas (empty: taken without)
     // md.water views and hydrogen-bond detection (mdx_set_water_layout / mdx_set_hbond_detection)
     uint32_t water_first = 0, n_waters = 0, water_sites = 0;
     std::vector<uint8_t> hb_heavy; float hb_dmax = 2.5f, hb_angle_min = 120.f;
@@ -597,6 +603,8 @@ uint32_t mdx_steps_to_next_event(const mdx_handle* h);            // chunk lengt
 bool mdx_energy_wanted_at(const mdx_handle* h, uint64_t step);    // does something read the energies after step `step`?
 int mdx_finalize_energy_cache(mdx_handle* h);                     // e_pending -> e_cache (kinetic energy, constraint virial, read-back)
 int mdx_groups_evaluate(mdx_handle* h, float* out /* [n_grp^2] */);   // energy_potential_between_mols of the current state (mdx_groups.hip)
+int mdx_foreign_evaluate(mdx_handle* h, double* du /* [foreign_lams.size()] */);   // foreign-lambda dU_k of the current state (mdx_foreign.hip); the
+                                                                     // reciprocal part comes from the last energy evaluation, which must be of this state
 int mdx_launch_scale_velocities(mdx_handle* h, float lambda, const double* com_v_or_null);
 int mdx_launch_momentum(mdx_handle* h);                           // energy[EN_COUNT+1..] <- sum m v (3 doubles) + mass
 

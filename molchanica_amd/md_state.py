@@ -162,6 +162,11 @@ def load_library():
     lib.mdx_position_restraints_read.argtypes = [H, C.c_uint32, _u32p, _fp, _fp, _fp]
     lib.mdx_position_restraints_read.restype = C.c_uint32
     lib.mdx_restraint_energy.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.mdx_set_foreign_lambdas.argtypes = [H, C.c_uint32, C.c_void_p]
+    lib.mdx_foreign_energies.argtypes = [H, C.c_void_p, C.c_uint32]
+    lib.mdx_snapshot_foreign_count.argtypes = [H, C.c_uint32]
+    lib.mdx_snapshot_foreign_count.restype = C.c_uint32
+    lib.mdx_snapshot_read_foreign.argtypes = [H, C.c_uint32, C.c_void_p, C.c_uint32]
     _lib = lib
     return lib
 
@@ -375,6 +380,22 @@ class MdState:
         """`md.configure_alchemical_window(dev, mol_index, lambda)` (src/properties/water_sol.rs:556); lam < 0 = off."""
         _check(load_library().mdx_configure_alchemical_window(self._h, int(mol_index), float(lam)))
 
+    _foreign_lams = None
+
+    def set_foreign_lambdas(self, lams):
+        """Foreign lambda values (at most 32, each in [0, 1]; empty or None clears): with a window on, foreign_energies() and every
+        snapshot report dU_k = U(lambda_k) - U(lambda) (include/mdx.h), the inputs of the BAR / MBAR estimators (alchemical.py)."""
+        a = np.ascontiguousarray([] if lams is None else lams, dtype=np.float64).reshape(-1)
+        _check(load_library().mdx_set_foreign_lambdas(self._h, a.shape[0], a.ctypes.data if a.shape[0] else None))
+        self._foreign_lams = a.copy() if a.shape[0] else None
+
+    def foreign_energies(self) -> np.ndarray:
+        """dU_k = U(lambda_k) - U(lambda) of the current state, float64 [K] kcal/mol (needs an active window and foreign lambdas)."""
+        n = 0 if self._foreign_lams is None else self._foreign_lams.shape[0]
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        _check(load_library().mdx_foreign_energies(self._h, out.ctypes.data, n))
+        return out[:n]
+
     def set_alchemical_softcore(self, alpha: float = 0.5, sigma_min: float = 3.0):
         """Soft core of the alchemical window (alpha = 0: linear coupling)."""
         _check(load_library().mdx_set_alchemical_softcore(self._h, float(alpha), float(sigma_min)))
@@ -448,6 +469,13 @@ class MdState:
                 m = np.zeros((n_g, n_g), dtype=np.float32)
                 if lib.mdx_snapshot_read_between_mols(self._h, k, m.ctypes.data_as(_fp), n_g) == MDX_OK:
                     snap["energy_data"]["energy_potential_between_mols"] = m
+            n_f = int(lib.mdx_snapshot_foreign_count(self._h, k))
+            if n_f:      # (the lambdas are the ones set on this MdState: change them only after flushing the snapshots)
+                du = np.zeros(n_f, dtype=np.float64)
+                _check(lib.mdx_snapshot_read_foreign(self._h, k, du.ctypes.data, n_f))
+                snap["energy_data"]["foreign_du"] = du
+                if self._foreign_lams is not None and self._foreign_lams.shape[0] == n_f:
+                    snap["energy_data"]["foreign_lambdas"] = self._foreign_lams.copy()
             n_hb = int(lib.mdx_snapshot_hbond_count(self._h, k))
             hb = (CHBond * max(n_hb, 1))()
             if n_hb:
