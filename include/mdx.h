@@ -322,7 +322,9 @@ int mdx_get_stats(mdx_handle* h, mdx_stats* out);
  * call behind such a rebuild walks the inner list instead of being a pruning pass: one wave per tile, single device), out[17]: the
  * last rebuild was one of them, out[18]: steps so far that took the handle's rigid waters through the one-pass water_step_kernel, out[19]: ... of
  * which with other mobile atoms beside them (a solute in rigid water), out[20]: pair launches so far that were the whole step (body 5),
- * out[21]: steps taken back to a list rebuild because a kick exceeded what the gating words had granted it, out[22..23]: 0.  The parity tests use it to name the body they hold against the oracle; no call
+ * out[21]: steps taken back to a list rebuild because a kick exceeded what the gating words had granted it, out[22]: one-wave units per
+ * closing tile of the last dual-list launch of the step loop (mixed waves per tile, MDX_WPT_TAIL; 0: every tile one unit), out[23]: closing
+ * tiles in that launch.  The parity tests use it to name the body they hold against the oracle; no call
  * of the reference corresponds to it. */
 int mdx_pair_launch_info(const mdx_handle* h, uint32_t out[24]);
 /* The Verlet skin in force, and whether the library is still tuning it (mdx_config.skin == 0). */

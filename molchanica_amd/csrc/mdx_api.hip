@@ -1483,7 +1483,7 @@ extern "C" int mdx_pair_launch_info(const mdx_handle* h, uint32_t out[24]) {
     if (!h || !out) FAIL(MDX_EPARAM, "null argument");
     for (int k = 0; k < 8; ++k) { out[k] = h->pair_info_step[k]; out[8 + k] = h->pair_info_any[k]; }
     out[16] = h->inner_rebuilds; out[17] = h->inner_from_rebuild ? 1u : 0u; out[18] = h->water_step_launches; out[19] = h->water_step_mixed_launches;
-    out[20] = (uint32_t)h->onepass_launches; out[21] = (uint32_t)h->onepass_violations; out[22] = 0u; out[23] = 0u;
+    out[20] = (uint32_t)h->onepass_launches; out[21] = (uint32_t)h->onepass_violations; out[22] = h->pair_info_tail[0]; out[23] = h->pair_info_tail[1];
     return MDX_OK;
 }
 

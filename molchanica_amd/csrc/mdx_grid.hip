@@ -1202,7 +1202,9 @@ __global__ __launch_bounds__(256) void prune_list_kernel(uint32_t T, float r2, f
     if (inner_on) {
         const uint32_t nin_pad = (wcur_in + 7u) & ~7u;
         if (lane < (int)(nin_pad - wcur_in)) pin.entries_in[e0 + cnt.n_masked + wcur_in + lane] = make_uint2(null_cluster, 13u);
-        if (lane == 0) pin.inner_nch[(size_t)t * 8] = nmc + (nin_pad >> 3);
+        // (all eight words: the plain run is contiguous here, so any number of walkers may share it chunk by chunk - the closing tiles
+        // of the pair launch are walked by 2 or 4 one-wave units, mdx_tail_plan)
+        if (lane < 8) pin.inner_nch[(size_t)t * 8 + lane] = nmc + (nin_pad >> 3);
     }
     const bool any_ghost = __any(ghost_hit);
     if (lane == 0) {
@@ -2298,6 +2300,9 @@ int mdx_rebuild(mdx_handle* h) {
     h->prune_pending = !(res.inner_built && h->dual_on);      // (the fused chain's pruning pass has written the inner list of these positions)
     h->inner_from_rebuild = !h->prune_pending;
     if (h->inner_from_rebuild) ++h->inner_rebuilds;
+    // mixed waves per tile: the order by length inside the XCD ranges says which tiles close a range; fixed until the next rebuild
+    h->tail_w = 0; h->tail_tiles = 0;
+    if (h->dual_on && h->tile_lpt_on && h->tile_lpt_grouped && !h->alch_on) mdx_tail_plan(h, T, &h->tail_w, &h->tail_tiles);
     if (!d.inner_count) { ALLOC(d.inner_count, MDX_EPART + 8); HIP_TRY(hipMemsetAsync(d.inner_count, 0, sizeof(unsigned long long) * (MDX_EPART + 8), st)); }
     uint64_t nmask = (uint64_t)MC * 8;
     h->stats.n_atoms = N; h->stats.n_slots = S; h->stats.n_tiles = T; h->stats.n_clusters = NC;

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <chrono>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 #include "../../include/mdx.h"
@@ -422,6 +424,9 @@ struct mdx_handle {
     bool force_zeroed = false;   // the integrate pass just enqueued cleared the force array (half-list kernel: skip the fill)
     bool cons_full_kick = false; // the SHAKE pass about to be enqueued follows a fused full kick (closing + opening): its corrections are those of a force acting through dt
     bool bonded_fused = false;   // the pair launch just enqueued carried the bonded gather in extra workgroups: skip its own launch
+    // mixed waves per tile (mdx_tail_plan; decided at every list rebuild, in force until the next: the inner list is written for it)
+    uint32_t tail_w = 0, tail_tiles = 0;      // units per closing tile (0: none), closing tiles per XCD range
+    uint32_t pair_info_tail[2] = {};          // ... of the last dual-list launch of the step loop: units per tail tile, tail tiles in the launch
     uint32_t pair_info_step[8] = {}, pair_info_any[8] = {};   // the pair-kernel instantiation last launched by the step loop over the dual list / by anything else (mdx_pair_launch_info)
     bool bonded_deferred = false; // step loop, large classes: the NEXT step's fused bonded + kick + drift pass evaluates the bonded terms of this force call
     uint64_t rng_state = 0;
@@ -569,6 +574,39 @@ static inline WptRule mdx_wpt_rule_of(const mdx_handle* h) {
     return r;
 }
 static inline int mdx_nb_wpt_half(const mdx_handle* h, uint32_t T) { return mdx_wpt_rule(mdx_wpt_rule_of(h), T); }
+// Mixed waves per tile in the one-wave class (profiles/pair_drain.txt): the launch ends with a stretch in which the
+// SIMDs run dry one whole tile at a time; the closing tiles of every XCD's range go out as w one-wave units instead.
+// MDX_WPT_TAIL=0: none (the parent arrangement, launch for launch); MDX_WPT_TAIL=w/d: w = 2 or 4 units for the last 1/d of each range
+// (d = 1: every tile).  Default: MDX_WPT_TAIL_DEFAULT from 12 k tiles on.  *w_out = 0 or w, *tiles_out = closing tiles per XCD range.
+#define MDX_WPT_TAIL_DEFAULT_W 4u
+#define MDX_WPT_TAIL_DEFAULT_DEN 8u
+static inline void mdx_tail_plan(const mdx_handle* h, uint32_t T, uint32_t* w_out, uint32_t* tiles_out) {
+    struct TailEnv { int set; uint32_t w, den; };
+    static const TailEnv env = [] {
+        TailEnv r{0, 0u, 0u};
+        const char* e = std::getenv("MDX_WPT_TAIL");
+        if (!e || !e[0]) return r;
+        r.set = 1;
+        const uint32_t w = (uint32_t)std::atoi(e);
+        const char* s = std::strchr(e, '/');
+        const uint32_t den = s ? (uint32_t)std::atoi(s + 1) : 8u;
+        if ((w == 2u || w == 4u) && den >= 1u) { r.w = w; r.den = den; }
+        return r;
+    }();
+    *w_out = 0; *tiles_out = 0;
+    if (h->dd || h->n_local != h->N || mdx_nb_wpt_half(h, T) != 1) return;      // single device, one wave per tile
+    if (const char* e = std::getenv("MDX_ONEPASS")) { if (e[0] == '2') return; }    // (the one-launch-per-step flavour of this class walks every tile with one wave)
+    uint32_t w = 0, den = 0;
+    if (env.set) { w = env.w; den = env.den; }
+    // (handles with the reciprocal-space chain on a side stream keep the parent arrangement unless asked: the default operating point
+    // measured 906 -> 894 steps/s with the split on, profiles/wpt_tail_ab.txt)
+    else if (T >= 12000u && !h->pme_on) { w = MDX_WPT_TAIL_DEFAULT_W; den = MDX_WPT_TAIL_DEFAULT_DEN; }
+    if (w < 2u) return;
+    const uint32_t group = (T + 7u) >> 3;
+    const uint32_t tiles = den == 1u ? group : group / den;
+    if (!tiles) return;
+    *w_out = w; *tiles_out = tiles;
+}
 
 // constraints / virtual sites (mdx_constraints.hip)
 int mdx_build_constraints(mdx_handle* h, const mdx_system* s);

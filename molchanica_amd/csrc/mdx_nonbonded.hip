@@ -49,6 +49,20 @@ NB_EXTERN(false, CM_EWALD_TAB)
 NB_EXTERN(true, CM_SHIFTED) NB_EXTERN(true, CM_RF) NB_EXTERN(true, CM_EWALD) NB_EXTERN(true, CM_SOFT)
 #undef NB_EXTERN
 
+#ifdef NB_DRAIN_TRACE
+// The drain trace (make EXTRA=-DNB_DRAIN_TRACE, off by default; tools/pair_drain.py): while switched on, every merged dual-list pair launch
+// leaves two uint4 per wave - clocks at entry and exit, HW_ID, XCC_ID, pruning pass or not, written - and this call downloads the last one.
+uint4* g_mdx_drain = nullptr; size_t g_mdx_drain_cap = 0; uint32_t g_mdx_drain_n = 0; int g_mdx_drain_on = 0;
+extern "C" int mdx_debug_drain_trace(mdx_handle* h, int on, uint32_t* out, uint32_t cap_waves) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    g_mdx_drain_on = on;
+    if (!out || !g_mdx_drain) return 0;
+    const uint32_t n = std::min(g_mdx_drain_n, cap_waves);
+    HIP_TRY(hipMemcpy(out, g_mdx_drain, sizeof(uint4) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+    return (int)n;
+}
+#endif
+
 static bool cut_on(float rc) { return rc > 0.f && std::isfinite(rc); }
 #define FAIL_NB(msg) do { mdx_set_error(msg); return MDX_EDEVICE; } while (0)
 

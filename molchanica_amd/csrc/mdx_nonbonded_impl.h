@@ -11,6 +11,9 @@
 #include <type_traits>
 
 constexpr int NB_WAVES = MDX_NB_WAVES;      // least waves per workgroup (mdx_internal.h)
+#ifdef NB_DRAIN_TRACE
+extern uint4* g_mdx_drain; extern size_t g_mdx_drain_cap; extern uint32_t g_mdx_drain_n; extern int g_mdx_drain_on;      // mdx_nonbonded.hip
+#endif
 #ifndef NB_ASM_PAIR
 #define NB_ASM_PAIR 0     // 1: the default flavour's pair evaluation is the hand-written block pair_eval_asm (v_cmpx exec handling):
                           // measured round 3 - inner-list walk 0.4566 / 0.4517 ms against 0.4565 / 0.4572 with the compiler's
@@ -243,11 +246,29 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     const uint32_t per_xcd = (nblocks + 7) >> 3;
     // a decomposed rank's tile range is owned bricks (long lists) and halo shells (short lists) in spatial order: a
     // contiguous eighth per XCD would leave whole XCDs with halo tiles only, so there the tiles go round-robin
-    const uint32_t blk = a.xcd_interleave ? blockIdx.x : (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
-    if (blk >= nblocks) return;                               // whole workgroup
+    constexpr bool TAIL = WPT == 1 && HALF && DUAL != 0 && !STEP && BW == 1;      // (mixed waves per tile, below)
+    const bool tail_on = TAIL && a.tail_w > 1u;
+    const uint32_t blk = (a.xcd_interleave || tail_on) ? blockIdx.x : (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    if (!tail_on && blk >= nblocks) return;                   // whole workgroup
     const int tib = SPLIT > 1 ? 0 : wave / WPT;               // tile within the workgroup
-    const int part = SPLIT > 1 ? (int)(blk % SPLIT) * BW + wave : wave % WPT;   // which share of the tile's chunks
-    const uint32_t tidx = SPLIT > 1 ? blk / SPLIT : blk * TPB + tib;
+    int part = SPLIT > 1 ? (int)(blk % SPLIT) * BW + wave : wave % WPT;   // which share of the tile's chunks
+    uint32_t tidx = SPLIT > 1 ? blk / SPLIT : blk * TPB + tib;
+    // Mixed waves per tile (one-wave class, dual list; NbArgs::tail_w): the launch is a list of work UNITS, per XCD range first the
+    // head tiles as one unit each, then every closing tile as tail_w units - one-wave workgroups that share the tile's chunks the way
+    // the waves of a 2 / 4-wave tile do (chunk c goes to unit c mod tail_w) and add their i-forces to the tile's rows with the
+    // atomics this flavour uses anyway.  The units are what the hardware dispatches last: a quarter of a tile instead of a whole one
+    // is what a SIMD may be left holding when its neighbours run dry.
+    uint32_t wv = WPT;                                        // waves (units) this tile's chunks are shared between
+    if (tail_on) {
+        const uint32_t xcd = blockIdx.x & 7u, u = blockIdx.x >> 3;      // (the host sends this geometry out with xcd_interleave off only)
+        tidx = xcd * a.tail_group + u;
+        if (u >= a.tail_head) {
+            const uint32_t v = u - a.tail_head;
+            wv = a.tail_w;                                    // 2 or 4
+            part = (int)(v & (wv - 1u));
+            tidx = xcd * a.tail_group + a.tail_head + (v >> (wv == 4u ? 2 : 1));
+        }
+    }
     const bool t_ok = tidx < ntiles;                          // (the last workgroup may have a tile too many)
     if (WPT == 1 && !t_ok) return;
     // a.T = the null tile: empty list, nothing stored
@@ -387,7 +408,7 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     if ((uint32_t)part < nchunks) {
         const uint2 ent = entries[e0 + part * 8 + (lane >> 3)];
         if ((uint32_t)part < nmc) nmq = a.masks[(size_t)(mbase + part) * 64 + lane];
-        if ((uint32_t)part + WPT < nchunks) ent_n = entries[e0 + (part + WPT) * 8 + (lane >> 3)];
+        if ((uint32_t)part + wv < nchunks) ent_n = entries[e0 + (part + wv) * 8 + (lane >> 3)];
         const uint32_t js = ent.x * MDX_CLUSTER + (lane & 7);
         nj = a.posq[js]; nl = a.lj[js]; ny = ent.y; njc = ent.x;
         if (STEP) nf = a.st_fprev[js];
@@ -407,7 +428,7 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     uint32_t dbg_jh = 0, dbg_ih = 0, dbg_q = 0, dbg_pairs = 0;
 #endif
     // (pruning launch) first plain chunk of this wave's share, and how many compacted plain entries it has written
-    const uint32_t c_first = nmc + ((uint32_t)part + WPT - nmc % WPT) % WPT;
+    const uint32_t c_first = nmc + (TAIL ? (((uint32_t)part + wv - (nmc & (wv - 1u))) & (wv - 1u)) : ((uint32_t)part + WPT - nmc % WPT) % WPT);
     uint32_t wcur = 0;
     // HALF: the j-forces of a chunk collect in the wave's LDS strip and leave as three 64-lane
     // atomics (x, y, z of j-atom `lane`) when the chunk is done: always three, issued AFTER the
@@ -421,7 +442,7 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     // entry loop.  The software pipeline's state (nj, nl, ny, njc, ent_n, nmq) carries over from the first loop into the second.
     auto chunk_pass = [&](auto masked_tag, const uint32_t c_begin, const uint32_t c_end) __attribute__((always_inline)) {
     constexpr bool MASKED_CHUNK = decltype(masked_tag)::value;
-    for (uint32_t c = c_begin; c < c_end; c += WPT) {
+    for (uint32_t c = c_begin; c < c_end; c += wv) {
         const uint32_t cur_y = ny, cur_jc = njc;
         constexpr bool masked = MASKED_CHUNK;
         if (masked) s_mask[wave][lane] = nmq;                   // read back a byte per entry: two VGPRs fewer
@@ -443,13 +464,13 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
             sl[lane] = nl;
         }
         WAVE_LDS_SYNC();
-        if (c + WPT < nmc) nmq = a.masks[(size_t)(mbase + c + WPT) * 64 + lane];
-        if (c + WPT < nchunks) {
+        if (c + wv < nmc) nmq = a.masks[(size_t)(mbase + c + wv) * 64 + lane];
+        if (c + wv < nchunks) {
             const uint32_t js = ent_n.x * MDX_CLUSTER + (lane & 7);
             nj = a.posq[js]; nl = a.lj[js]; ny = ent_n.y; njc = ent_n.x;
             if (STEP) nf = a.st_fprev[js];
             if (ENERGY && HALF) nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
-            if (c + 2 * WPT < nchunks) ent_n = entries[e0 + (c + 2 * WPT) * 8 + (lane >> 3)];
+            if (c + 2 * wv < nchunks) ent_n = entries[e0 + (c + 2 * wv) * 8 + (lane >> 3)];
         }
         float celj = 0.f, cecoul = 0.f, cevir = 0.f, cecross = 0.f, cedudl = 0.f;   // (ENERGY) fp32 partial sums of this chunk
         uint32_t newy = cur_y & 0xFFu;                                // (pruning launch) this lane's entry word with the inner mask
@@ -539,7 +560,7 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
                 const unsigned long long bal = __ballot(alive);
                 if (alive) {
                     const uint32_t k = wcur + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-                    a.entries_in[e0 + (c_first + (k >> 3) * WPT) * 8 + (k & 7u)] = make_uint2(cur_jc, newy);
+                    a.entries_in[e0 + (c_first + (k >> 3) * wv) * 8 + (k & 7u)] = make_uint2(cur_jc, newy);
                 }
                 wcur += (uint32_t)__popcll(bal);
             }
@@ -590,9 +611,9 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
         const uint32_t nfull = (wcur + 7u) >> 3;
         if ((uint32_t)lane < nfull * 8u - wcur) {
             const uint32_t k = wcur + (uint32_t)lane;
-            a.entries_in[e0 + (c_first + (k >> 3) * WPT) * 8 + (k & 7u)] = make_uint2(a.T * MDX_CL_PER_TILE, 13u);
+            a.entries_in[e0 + (c_first + (k >> 3) * wv) * 8 + (k & 7u)] = make_uint2(a.T * MDX_CL_PER_TILE, 13u);
         }
-        if (lane == 0) a.inner_nch[t * 8 + part] = nfull ? c_first + (nfull - 1u) * WPT + 1u : nmc;
+        if (lane == 0) a.inner_nch[t * 8 + part] = nfull ? c_first + (nfull - 1u) * wv + 1u : nmc;
     }
     if (prune) {
         // path lengths count from this pass (a boundary pass asked for by the ghosts alone restarts the ghosts only)
@@ -730,6 +751,9 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
         // (biased by the byte offset of the table's first binade: pair_eval adds the masked bits of x, shifted, and nothing else)
         etab = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_dyn_etab) - ((EWALD_TAB_CBITS >> a.p.etab_shift) << 4));
     }
+#ifdef NB_DRAIN_TRACE
+    const unsigned long long drain_t0 = wall_clock64();
+#endif
     if (DUAL == 0) {
         nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 0, BW>(a, true, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
     } else {
@@ -748,11 +772,25 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
             if (want_prune != (DUAL == 2)) return;
             nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, DUAL == 2 ? 2 : 1, BW>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
         }
+#ifdef NB_DRAIN_TRACE
+        // every wave: the constant-rate clock at entry and at exit (after its atomics have left), HW_ID and XCC_ID (which SIMD of which
+        // CU of which XCD it ran on), written by lane 0 with ordinary vector stores
+        if (DUAL == 3 && a.drain) {
+            __builtin_amdgcn_s_waitcnt(0);
+            const unsigned long long t1 = wall_clock64();
+            if ((threadIdx.x & 63u) == 0u) {
+                uint4* const o = a.drain + 2 * ((size_t)blockIdx.x * BW + (threadIdx.x >> 6));
+                o[0] = make_uint4((uint32_t)drain_t0, (uint32_t)(drain_t0 >> 32), (uint32_t)t1, (uint32_t)(t1 >> 32));
+                o[1] = make_uint4(__builtin_amdgcn_s_getreg(4 | (31 << 11)), __builtin_amdgcn_s_getreg(20 | (31 << 11)), want_prune ? 1u : 0u, 1u);
+            }
+        }
+#endif
     }
 }
 
 template <bool ENERGY, int COUL>
-void launch_variant(mdx_handle* h, const NbArgs& a, bool geom, bool samecut) {
+void launch_variant(mdx_handle* h, const NbArgs& a_in, bool geom, bool samecut) {
+    NbArgs a = a_in;
     const int var = mdx_nb_variant(h);
     // waves per tile: split a tile's list over the 4 waves of its workgroup when the launch has
     // fewer tiles than ~3 per SIMD (the chip holds 4 waves/SIMD of this kernel on 1024 SIMDs)
@@ -771,6 +809,34 @@ void launch_variant(mdx_handle* h, const NbArgs& a, bool geom, bool samecut) {
     const uint32_t grid = ((nblocks + 7) / 8) * 8;
     if (nblocks == 0) return;
     dim3 g(grid), b(bw * 64);
+    // mixed waves per tile (mdx_tail_plan): dual-list launches of the one-wave class over the order by length inside the XCD ranges - per
+    // range tail_head one-unit tiles, then tail_w units for each closing tile.  Everything else keeps the grid above.
+    if (half && wpt == 1 && a.inner && !ENERGY && !a.st_fprev && h->tail_w > 1u && h->tile_lpt_on && a.tile_order == h->d.tile_lpt && !a.xcd_interleave) {
+        a.tail_group = (a.T + 7u) >> 3;
+        const uint32_t tail = std::min(h->tail_tiles, a.tail_group);
+        a.tail_w = h->tail_w; a.tail_head = a.tail_group - tail;
+        g = dim3(8u * (a.tail_head + a.tail_w * tail));
+    }
+    if (a.inner) {      // (mdx_pair_launch_info: units per closing tile, closing tiles in the launch - the last XCD's range may be short)
+        uint32_t n_tail = 0;
+        for (uint32_t x = 0; a.tail_w && x < 8u; ++x) {
+            const uint32_t in_range = a.T > x * a.tail_group ? std::min(a.T - x * a.tail_group, a.tail_group) : 0u;
+            n_tail += in_range > a.tail_head ? in_range - a.tail_head : 0u;
+        }
+        h->pair_info_tail[0] = a.tail_w; h->pair_info_tail[1] = n_tail;
+    }
+#ifdef NB_DRAIN_TRACE
+    if (a.inner && g_mdx_drain_on) {      // (the merged dual-list launch only; the buffer is sized by the largest grid seen)
+        const size_t want = (size_t)g.x * bw * 2;
+        if (want > g_mdx_drain_cap) {
+            if (g_mdx_drain) (void)hipFree(g_mdx_drain);
+            (void)hipMalloc((void**)&g_mdx_drain, sizeof(uint4) * want);
+            g_mdx_drain_cap = want;
+        }
+        (void)hipMemsetAsync(g_mdx_drain, 0, sizeof(uint4) * want, h->stream);
+        a.drain = g_mdx_drain; g_mdx_drain_n = (uint32_t)(g.x * bw);
+    }
+#endif
     // MDX_NB_LDS_PAD=<bytes> (experiment): dynamic LDS the pair kernel asks for and never touches, on handles whose reciprocal-space
     // chain runs on a side stream.  Four waves of this kernel per SIMD hold the whole register file, so the chain's kernels only get
     // a CU when a pair workgroup retires - the two time-slice instead of overlapping; padding the LDS footprint caps the pair

@@ -56,6 +56,12 @@ struct NbArgs {
     uint32_t* st_disp_out;        // ctl.disp2[s + 2]: (bound of |x - ref| at the NEXT position stage)^2, raised only above thr_bits
     uint32_t* st_prune_out;       // ctl.prune[s + 2]
     uint32_t* st_viol;            // ctl.viol[s]: the stage this launch found contradicts the words that let it run - the host takes the step back to a list rebuild
+    // mixed waves per tile (one-wave class, dual-list launches; mdx_tail_plan): tail_w = 2 / 4 units for each of the closing tiles of an
+    // XCD's range (0 / 1: none), tail_group = tiles per XCD range, tail_head = how many of them stay one unit
+    uint32_t tail_w, tail_head, tail_group;
+#ifdef NB_DRAIN_TRACE
+    uint4* drain;                 // (make EXTRA=-DNB_DRAIN_TRACE, tools/pair_drain.py) two records per wave of the launch: clocks at entry and exit, where it ran
+#endif
 };
 
 enum { CM_SHIFTED = 0, CM_RF = 1, CM_EWALD = 2, CM_SOFT = 3,

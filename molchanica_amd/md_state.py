@@ -540,7 +540,9 @@ class MdState:
         return {"step": dict(zip(keys, (int(v) for v in out[0:8]))), "any": dict(zip(keys, (int(v) for v in out[8:16]))),
                 "inner_lists_from_rebuilds": int(out[16]), "last_rebuild_wrote_the_inner_list": bool(out[17]),
                 "water_step_launches": int(out[18]), "water_step_mixed_launches": int(out[19]),
-                "one_launch_steps": int(out[20]), "kicks_beyond_grant": int(out[21])}
+                "one_launch_steps": int(out[20]), "kicks_beyond_grant": int(out[21]),
+                # mixed waves per tile of the last dual-list launch of the step loop: units per closing tile (0: none), closing tiles
+                "tail": {"waves_per_tile": int(out[22]), "tiles": int(out[23])}}
 
     def skin(self):
         """-> (Verlet skin in force, still tuning?)  (MdConfig.skin == 0 lets the library choose it)."""
