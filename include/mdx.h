@@ -528,6 +528,27 @@ int      mdx_snapshot_read_between_mols(mdx_handle* h, uint32_t k, float* out /*
 int      mdx_single_point_between_mols(const mdx_system* sys, const mdx_config* cfg, int device, const uint8_t* group_of_atom,
                                        uint32_t n_groups, mdx_energies* out, float* forces_or_null, float* matrix_out /* [n * n] */);
 
+/* ---- a batch of ligand poses against the resident complex (docking / screening: src/docking/mod.rs:81-154 "You need a binding
+ * energy computation each step") -----------------------------------------------------------------------------------------------
+ * Energy groups must be set, and the atoms [first, first + count) must be exactly one group L: every atom of the range is in L and
+ * no other atom is.  Then out[p][b] is the element M[L][b] that mdx_energy_between_mols would return if the handle's positions of
+ * the range were replaced by pose p and everything else were left as it is now:
+ *   - same cutoffs, same real-space Coulomb treatment (shifted / reaction field / erfc), same combining rule, same minimum image;
+ *     poses may lie anywhere, wrapped or not;
+ *   - b = L is the intra-ligand element: the non-excluded pairs inside the range once each plus its scaled 1-4 pairs (flexible
+ *     poses and conformers change it);
+ *   - the SPME mesh term is no part of the row, as it is no part of the matrix.
+ * The handle is not changed: positions, velocities, forces, lists, energy caches and snapshots stay as they are, and a handle that
+ * scored poses continues bit for bit like one that did not.  A pose gives the same bits alone or in a batch of any size, at any
+ * place in it.  poses are in caller order, Angstrom; rows are kcal/mol.
+ * MDX_EPARAM (mdx_last_error says which; out is left untouched): no groups set or n_groups is not the group count; the range is not
+ * exactly one group; count == 0, count > MDX_POSE_MAX_ATOMS or the range exceeds N; a bond, constraint, exclusion or 1-4 pair links
+ * the range to an atom outside it; an alchemical window is active; the handle is decomposed; a pose coordinate is not finite.
+ * n_poses == 0 succeeds and does nothing. */
+#define MDX_POSE_MAX_ATOMS 256
+int      mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses,
+                         const float* poses /* [n_poses][count][3] */, float* out /* [n_poses][n_groups] */, uint32_t n_groups);
+
 /* ---- multi-GPU: one periodic box spatially decomposed over the GPUs of a node (the reference is
  * single-device, src/util.rs:1086 `CudaContext::new(0)`, so this is new capability, not parity) -------------------
  * One rank (process or thread) per GPU.  Every rank creates a handle from the SAME global system (static per-atom data

@@ -160,6 +160,16 @@ public:
         check(mdx_upload_range(h_, MDX_POS, first, (uint32_t)(p.size() / 3), p.data()));
     }
     void set_velocities(const std::vector<float>& v) { upload(MDX_VEL, v); }
+    /// mdx_score_poses: rows [n_poses][n_groups] of the ligand group's energies for alternative placements of atoms [first,
+    /// first + count) - poses: [n_poses][count][3] A in caller order; the state of the handle is left as it is.
+    std::vector<float> score_poses(uint32_t first, uint32_t count, const std::vector<float>& poses) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        if (count == 0 || poses.size() % (3 * (size_t)count) != 0) throw std::invalid_argument("score_poses: poses must hold [n_poses][count][3] floats");
+        const uint32_t n = (uint32_t)(poses.size() / (3 * (size_t)count));
+        std::vector<float> out((size_t)n * g);
+        check(mdx_score_poses(h_, first, count, n, poses.data(), out.data(), g));
+        return out;
+    }
 
     /// `md.cell = SimBox::new(lo, hi)` + `md.rebuild_spatial_caches()` (sol_shrinking_box.rs:600-603, 632).
     void set_cell(const SimBox& b) { check(mdx_set_box(h_, b.bounds_low.data(), b.bounds_high.data())); }

@@ -24,6 +24,8 @@ COMBINE_LORENTZ_BERTHELOT, COMBINE_GEOMETRIC = 0, 1
 
 POS, VEL, FORCE = 0, 1, 2
 
+POSE_MAX_ATOMS = 256   # MDX_POSE_MAX_ATOMS: the largest ligand mdx_score_poses takes
+
 _fp = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)

@@ -224,6 +224,7 @@ extern "C" int mdx_set_energy_groups(mdx_handle* h, const uint8_t* group_of_atom
     const uint32_t N = h->N;
     std::vector<uint8_t> g(N, 0);
     uint32_t G = n_groups;
+    h->grp_epoch++;
     if (!group_of_atom) {
         if (n_groups == MDX_GROUPS_OFF || (n_groups == 0 && h->mol_start.empty())) {      // off (explicitly, or as before on a system without molecules)
             if (h->d.grp) { (void)hipFree(h->d.grp); h->d.grp = nullptr; }

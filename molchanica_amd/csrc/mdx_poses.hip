@@ -1,0 +1,381 @@
+// mdx_poses.hip - mdx_score_poses: the ligand row of `energy_potential_between_mols` for a BATCH of alternative placements of one
+// group of atoms (the docking scorer of BASELINE config 3, /root/reference src/docking/mod.rs:81-154 "a binding energy computation each
+// step"; src/screening wants the same), in one pass that leaves the handle as it found it.
+//
+// Per pose only ~count x a few thousand pairs depend on the pose; mdx_upload_range + mdx_energy_between_mols pays a pass over the whole
+// pair list of the complex for them.  Here the environment stays where it is - slot-space posq / lj of the current state, the column /
+// tile structure of the last rebuild - and a pose is the ligand's rows in LDS:
+//
+//   grid (POSE_UNITS + 1, poses of the chunk), 256 threads.  Every workgroup stages its pose (xyz from the batch, charge and LJ record
+//   from the ligand's own slots) and takes the pose's bounding box.
+//   units 0 .. POSE_UNITS-1  the environment.  The columns whose atoms can lie within r_list of the box (periodic axes wrap, a
+//       non-periodic grid clamps), their tiles, of those the tiles with t mod POSE_UNITS = unit; the tile's eight cluster boxes are tested by
+//       eight lanes at once - the boxes were taken at the rebuild, so the test radius is r_list = cutoff + skin, twice the drift the list
+//       allows - and the clusters that pass go round the four waves.  Lane = (environment atom ii of the cluster, ligand atom jj of a
+//       strip of 8), looping over the ligand in strips: the 8 x 8 shape of the pair kernels.  The minimum image is taken per pair
+//       (d - rint(d / L) L, as the bonded gather and the oracle take it), then the SAME pair_eval (mdx_pair_dev.h) in its energy flavour:
+//       a row is made of the pair terms mdx_energy sums.  Slots of the ligand's own group and dummy slots are skipped.
+//       fp64 per lane, keyed by the environment atom's group; when a key changes the wave folds its sums - shuffles over jj, then the
+//       eight ii in lane order - into its own LDS row.  At the end the four rows are added in wave order.
+//   unit POSE_UNITS  the ligand's own pairs from the class map (plain: pair_eval; excluded: nothing; 1-4: the scaled records, the
+//       arithmetic of group_pairs14_kernel), one fixed share per thread, folded in lane and wave order.
+//   Every unit writes its partial row into slab[pose][unit][group]; pose_sum_kernel adds the units in order.  Which tiles a unit
+//   takes, which cluster a wave takes and the order of every sum depend on the pose and the resident structure alone - not on the
+//   batch, its size or timing - so a pose gives the same bits alone or among 4096, anywhere in the batch.  No atomics.
+#include "mdx_bonded_dev.h"
+#include "mdx_pair_dev.h"
+#include <cmath>
+#include <cstring>
+
+#define FAIL(code, msg) do { mdx_set_error(msg); return (code); } while (0)
+
+#define POSE_UNITS 16u     // environment units per pose: a batch of one pose still spreads over 17 workgroups
+#define POSE_CHUNK 256u    // poses staged per launch (host staging only: it does not enter the arithmetic)
+
+struct Pose14 { uint32_t a, b; float sig, e4, qq; };      // ligand-local atoms; sigma_ij, 4 scale eps_ij, scale k_e q_i q_j
+
+struct PoseArgs {
+    NbParams p;
+    GridParams g;
+    const float4* posq; const float2* lj;
+    const uint32_t* orig_of; const uint32_t* gid; const uint8_t* grp; const uint32_t* slot_of;
+    const uint32_t* tile_start; const float4* cl_lo; const float4* cl_hi;
+    uint32_t G, L, first, count;
+    const float* poses;            // [poses of the chunk][count][3]
+    double* slab;                  // [poses of the chunk][POSE_UNITS + 1][G]
+    float r_cull;                  // r_list (+ rounding room); not finite: no cutoff, everything is a candidate
+    float box[3], inv_box[3];      // periodic axes (0: none)
+    const uint8_t* cls; const Pose14* p14; uint32_t n14;
+};
+
+__device__ __forceinline__ float pose_mimg(float d, float box, float inv) { return box > 0.f ? d - rintf(d * inv) * box : d; }
+
+// the wave's per-lane sums leave for its LDS row: lanes of equal ii hold the same key
+__device__ __forceinline__ void pose_fold(double& dacc, uint32_t key, double* row, int lane) {
+    double v = dacc;
+    v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k)
+        if (lane == k && v != 0.0) row[key] += v;
+    dacc = 0.0;
+}
+
+template <int COUL, bool GEOM>
+__global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
+    __shared__ float4 s_xyzq[MDX_POSE_MAX_ATOMS];
+    __shared__ float2 s_lj[MDX_POSE_MAX_ATOMS];
+    __shared__ double s_row[4][256];
+    __shared__ float s_bb[4][6];
+    const uint32_t tid = threadIdx.x, unit = blockIdx.x, pose = blockIdx.y;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t count = a.count;
+
+    // ---- the pose: rows in LDS, bounding box ----
+    float4 me = make_float4(0.f, 0.f, 0.f, 0.f); float2 mlj = make_float2(0.f, 0.f);
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    if (tid < count) {
+        const uint32_t s = a.slot_of[a.first + tid];
+        const float* x = a.poses + ((size_t)pose * count + tid) * 3;
+        me = make_float4(x[0], x[1], x[2], 0.f);
+        if (s != MDX_INVALID) { me.w = a.posq[s].w; mlj = a.lj[s]; }
+        lo[0] = hi[0] = me.x; lo[1] = hi[1] = me.y; lo[2] = hi[2] = me.z;
+    }
+    s_xyzq[tid] = me; s_lj[tid] = mlj;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) s_row[w][tid] = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) { lo[d] = fminf(lo[d], __shfl_xor(lo[d], m)); hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], m)); }
+    if (lane == 0)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { s_bb[wave][d] = lo[d]; s_bb[wave][3 + d] = hi[d]; }
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        lo[d] = fminf(fminf(s_bb[0][d], s_bb[1][d]), fminf(s_bb[2][d], s_bb[3][d]));
+        hi[d] = fmaxf(fmaxf(s_bb[0][3 + d], s_bb[1][3 + d]), fmaxf(s_bb[2][3 + d], s_bb[3][3 + d]));
+    }
+    double* out = a.slab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * a.G;
+
+    if (unit == POSE_UNITS) {
+        // ---- the ligand's own pairs ----
+        double acc = 0.0;
+        const uint32_t n2 = count * count;
+        for (uint32_t i = tid; i < n2; i += 256u) {
+            const uint32_t ia = i / count, ib = i - ia * count;
+            if (ia >= ib || a.cls[i] != 0) continue;
+            const float4 pa = s_xyzq[ia], pb = s_xyzq[ib];
+            const float2 la = s_lj[ia];
+            const float dx = pose_mimg(pa.x - pb.x, a.box[0], a.inv_box[0]), dy = pose_mimg(pa.y - pb.y, a.box[1], a.inv_box[1]),
+                        dz = pose_mimg(pa.z - pb.z, a.box[2], a.inv_box[2]);
+            float fx = 0.f, fy = 0.f, fz = 0.f, e1 = 0.f, e2 = 0.f;
+            pair_eval<true, COUL, GEOM, false, true, false, false, true>(dx, dy, dz, pa.w, la.x, la.y, make_float4(0.f, 0.f, 0.f, pb.w), s_lj[ib], true, a.p,
+                                                                       fx, fy, fz, e1, e2, nullptr, nullptr, nullptr, 0.f);
+            acc += (double)(e1 + e2);
+        }
+        for (uint32_t k = tid; k < a.n14; k += 256u) {
+            const Pose14 r = a.p14[k];
+            const float4 pa = s_xyzq[r.a], pb = s_xyzq[r.b];
+            const float dx = pose_mimg(pa.x - pb.x, a.box[0], a.inv_box[0]), dy = pose_mimg(pa.y - pb.y, a.box[1], a.inv_box[1]),
+                        dz = pose_mimg(pa.z - pb.z, a.box[2], a.inv_box[2]);
+            const float r2 = dx * dx + dy * dy + dz * dz, rinv = rsqrtf(r2), rinv2 = rinv * rinv;
+            const float s2 = r.sig * r.sig * rinv2, s6 = s2 * s2 * s2;
+            acc += (double)(r.e4 * s6 * (s6 - 1.0f)) + (double)(r.qq * rinv);
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
+        if (lane == 0) s_row[wave][0] = acc;
+        __syncthreads();
+        if (tid < a.G) out[tid] = tid == a.L ? ((s_row[0][0] + s_row[1][0]) + s_row[2][0]) + s_row[3][0] : 0.0;
+        return;
+    }
+
+    // ---- the environment ----
+    const GridParams& g = a.g;
+    const float r = a.r_cull;
+    const bool all = !(r < 1.0e30f);
+    int ix0 = 0, ix1 = g.ncx - 1, iy0 = 0, iy1 = g.ncy - 1;
+    if (!all) {
+        ix0 = mdx_col_of(g, 0, lo[0] - r); ix1 = mdx_col_of(g, 0, hi[0] + r);
+        iy0 = mdx_col_of(g, 1, lo[1] - r); iy1 = mdx_col_of(g, 1, hi[1] + r);
+        if (!g.per[0]) { ix0 = max(ix0, 0); ix1 = min(ix1, g.ncx - 1); }
+        else if ((long long)ix1 - ix0 + 1 >= g.ncx) { ix0 = 0; ix1 = g.ncx - 1; }
+        if (!g.per[1]) { iy0 = max(iy0, 0); iy1 = min(iy1, g.ncy - 1); }
+        else if ((long long)iy1 - iy0 + 1 >= g.ncy) { iy0 = 0; iy1 = g.ncy - 1; }
+    }
+    const int nxr = max(ix1 - ix0 + 1, 0), nyr = max(iy1 - iy0 + 1, 0), ncr = nxr * nyr;
+    const float r2cull = r * r;
+    const float bcx = 0.5f * (lo[0] + hi[0]), bcy = 0.5f * (lo[1] + hi[1]), bcz = 0.5f * (lo[2] + hi[2]);
+    const float bhx = 0.5f * (hi[0] - lo[0]), bhy = 0.5f * (hi[1] - lo[1]), bhz = 0.5f * (hi[2] - lo[2]);
+    const int ii = lane & 7, jj = lane >> 3;
+    const uint32_t nstrip = (count + 7u) >> 3;
+    uint32_t cur_g = 0xFFFFFFFFu;
+    double dacc = 0.0;
+    double* row = s_row[wave];
+    for (int base = 0; base < ncr; base += 64) {
+        uint32_t t0 = 0, t1 = 0;
+        const int q = base + lane;
+        if (q < ncr) {
+            int cx = ix0 + q / nyr, cy = iy0 + q % nyr;
+            cx %= g.ncx; if (cx < 0) cx += g.ncx;       // (periodic axes; the others were clamped)
+            cy %= g.ncy; if (cy < 0) cy += g.ncy;
+            const uint32_t c = (uint32_t)(cx * g.ncy + cy);
+            t0 = a.tile_start[c]; t1 = a.tile_start[c + 1];
+        }
+        const int nq = min(64, ncr - base);
+        for (int l = 0; l < nq; ++l) {
+            const uint32_t a0 = (uint32_t)__builtin_amdgcn_readlane((int)t0, l), a1 = (uint32_t)__builtin_amdgcn_readlane((int)t1, l);
+            for (uint32_t t = a0 + ((unit + POSE_UNITS - (a0 % POSE_UNITS)) % POSE_UNITS); t < a1; t += POSE_UNITS) {
+                // eight lanes, eight cluster boxes (as the rebuild left them: r_cull covers the drift since)
+                bool near = false;
+                if (lane < 8) {
+                    const float4 l4 = a.cl_lo[t * MDX_CL_PER_TILE + lane], h4 = a.cl_hi[t * MDX_CL_PER_TILE + lane];
+                    if (l4.w > 0.f) {
+                        const float gx = fmaxf(0.f, fabsf(pose_mimg(0.5f * (l4.x + h4.x) - bcx, a.box[0], a.inv_box[0])) - (0.5f * (h4.x - l4.x) + bhx));
+                        const float gy = fmaxf(0.f, fabsf(pose_mimg(0.5f * (l4.y + h4.y) - bcy, a.box[1], a.inv_box[1])) - (0.5f * (h4.y - l4.y) + bhy));
+                        const float gz = fmaxf(0.f, fabsf(pose_mimg(0.5f * (l4.z + h4.z) - bcz, a.box[2], a.inv_box[2])) - (0.5f * (h4.z - l4.z) + bhz));
+                        near = all || gx * gx + gy * gy + gz * gz <= r2cull;
+                    }
+                }
+                uint32_t mask = (uint32_t)(__ballot(near) & 0xFFull);
+                for (uint32_t turn = 0; mask; ++turn) {
+                    const uint32_t ci = (uint32_t)__ffs((int)mask) - 1u;
+                    mask &= mask - 1u;
+                    if ((turn & 3u) != (uint32_t)wave) continue;
+                    const uint32_t s = (t * MDX_CL_PER_TILE + ci) * MDX_CLUSTER + (uint32_t)ii;
+                    const uint32_t o = a.orig_of[s];
+                    const uint32_t ge = o == MDX_INVALID ? 0xFFFFFFFFu : (uint32_t)a.grp[a.gid[o]];
+                    const bool live = o != MDX_INVALID && ge != a.L;
+                    if (!__ballot(live)) continue;
+                    if (__ballot(live && ge != cur_g && dacc != 0.0)) pose_fold(dacc, cur_g, row, lane);
+                    if (live && dacc == 0.0) cur_g = ge;
+                    const float4 pi = a.posq[s];
+                    const float2 li = a.lj[s];
+#pragma unroll 1
+                    for (uint32_t k = 0; k < nstrip; ++k) {
+                        const uint32_t ja = k * 8u + (uint32_t)jj;
+                        const float4 pj = s_xyzq[ja];
+                        const float2 lj = s_lj[ja];
+                        const float dx = pose_mimg(pi.x - pj.x, a.box[0], a.inv_box[0]), dy = pose_mimg(pi.y - pj.y, a.box[1], a.inv_box[1]),
+                                    dz = pose_mimg(pi.z - pj.z, a.box[2], a.inv_box[2]);
+                        const float bias = (live && ja < count) ? 0.f : __builtin_nanf("");
+                        float fx = 0.f, fy = 0.f, fz = 0.f, e1 = 0.f, e2 = 0.f;
+                        pair_eval<true, COUL, GEOM, false, true, false, false, true>(dx, dy, dz, pi.w, li.x, li.y, make_float4(0.f, 0.f, 0.f, pj.w), lj, true, a.p,
+                                                                                   fx, fy, fz, e1, e2, nullptr, nullptr, nullptr, bias);
+                        dacc += (double)(e1 + e2);
+                    }
+                }
+            }
+        }
+    }
+    pose_fold(dacc, cur_g, row, lane);
+    __syncthreads();
+    if (tid < a.G) out[tid] = ((s_row[0][tid] + s_row[1][tid]) + s_row[2][tid]) + s_row[3][tid];
+}
+
+__global__ __launch_bounds__(256) void pose_sum_kernel(uint32_t n, uint32_t G, const double* __restrict__ slab, double* __restrict__ rows) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * G) return;
+    const uint32_t pose = i / G, b = i - pose * G;
+    const double* s = slab + (size_t)pose * (POSE_UNITS + 1u) * G + b;
+    double v = 0.0;
+    for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * G];
+    rows[i] = v;
+}
+
+template <int COUL>
+static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n) {
+    const dim3 g(POSE_UNITS + 1u, n), b(256);
+    if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true>), g, b, 0, h->stream, a);
+    else hipLaunchKernelGGL((pose_score_kernel<COUL, false>), g, b, 0, h->stream, a);
+}
+
+// The ligand's own pairs, once per (range, group map): who is excluded, who is a scaled 1-4 pair and with what parameters - from the
+// handle's merged exclusion / 1-4 CSR and the 1-4 roles of the bonded gather.  Refuses a range that is tied to the outside.
+static int pose_table(mdx_handle* h, uint32_t first, uint32_t count) {
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t last = first + count;
+    auto inside = [&](uint32_t i) { return i >= first && i < last; };
+    for (size_t k = 0; k + 1 < h->h_bond_pairs.size(); k += 2)
+        if (inside(h->h_bond_pairs[k]) != inside(h->h_bond_pairs[k + 1]))
+            FAIL(MDX_EPARAM, "mdx_score_poses: a bond or constraint links the range to an atom outside it");
+    for (const VSite& v : h->h_vsites) {
+        const bool in = inside(v.site);
+        if (inside(v.p0) != in || inside(v.p1) != in || inside(v.p2) != in)
+            FAIL(MDX_EPARAM, "mdx_score_poses: a virtual site links the range to an atom outside it");
+    }
+    std::vector<uint32_t> off(count + 1), idx;
+    HIP_TRY(hipMemcpyAsync(off.data(), d.excl_off + first, sizeof(uint32_t) * (count + 1), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    idx.resize(off[count] - off[0]);
+    if (!idx.empty()) HIP_TRY(hipMemcpyAsync(idx.data(), d.excl_idx + off[0], sizeof(uint32_t) * idx.size(), hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> roff(count + 1, 0);
+    std::vector<RoleRec> recs;
+    std::vector<float4> prm(h->n_prm_base);
+    if (h->n_roles) {
+        HIP_TRY(hipMemcpyAsync(roff.data(), d.role_off_o + first, sizeof(uint32_t) * (count + 1), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        recs.resize(roff[count] - roff[0]);
+        if (!recs.empty()) HIP_TRY(hipMemcpyAsync(recs.data(), d.role_rec_o + roff[0], sizeof(RoleRec) * recs.size(), hipMemcpyDeviceToHost, st));
+        if (!prm.empty()) HIP_TRY(hipMemcpyAsync(prm.data(), d.role_prm, sizeof(float4) * prm.size(), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<uint8_t> cls((size_t)count * count, 0);
+    for (uint32_t i = 0; i < count; ++i)
+        for (uint32_t k = off[i] - off[0]; k < off[i + 1] - off[0]; ++k) {
+            if (!inside(idx[k])) FAIL(MDX_EPARAM, "mdx_score_poses: an exclusion or 1-4 pair links the range to an atom outside it");
+            cls[(size_t)i * count + (idx[k] - first)] = 1;      // (the CSR is symmetric)
+        }
+    std::vector<Pose14> p14;
+    const bool skip14 = (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) != 0;
+    for (uint32_t i = 0; i < count; ++i)
+        for (uint32_t k = roff[i] - roff[0]; k < roff[i + 1] - roff[0] && k < recs.size(); ++k) {
+            const RoleRec& r = recs[k];
+            if ((r.meta & 0xFu) != ROLE_PAIR14 || ((r.meta >> 4) & 0xFu) != 0u) continue;
+            if (!inside(r.p[0])) FAIL(MDX_EPARAM, "mdx_score_poses: an exclusion or 1-4 pair links the range to an atom outside it");
+            const uint32_t b = r.p[0] - first, pi = r.meta >> 8;
+            cls[(size_t)i * count + b] = 2; cls[(size_t)b * count + i] = 2;
+            if (skip14 || pi >= prm.size()) continue;      // (bonded terms disabled: the matrix leaves the scaled pairs out too)
+            p14.push_back(Pose14{i, b, prm[pi].x, prm[pi].y, prm[pi].z});
+        }
+    if (d.ps_cls) { (void)hipFree(d.ps_cls); d.ps_cls = nullptr; }
+    if (d.ps_p14) { (void)hipFree(d.ps_p14); d.ps_p14 = nullptr; }
+    HIP_TRY(hipMalloc((void**)&d.ps_cls, cls.size()));
+    HIP_TRY(hipMalloc((void**)&d.ps_p14, sizeof(Pose14) * std::max<size_t>(p14.size(), 1)));
+    HIP_TRY(hipMemcpyAsync(d.ps_cls, cls.data(), cls.size(), hipMemcpyHostToDevice, st));
+    if (!p14.empty()) HIP_TRY(hipMemcpyAsync(d.ps_p14, p14.data(), sizeof(Pose14) * p14.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    h->ps_n14 = (uint32_t)p14.size();
+    return MDX_OK;
+}
+
+extern "C" int mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, float* out,
+                               uint32_t n_groups) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_poses == 0) return MDX_OK;
+    if (!poses || !out) FAIL(MDX_EPARAM, "null argument");
+    const uint32_t G = h->n_grp;
+    if (!G) FAIL(MDX_EPARAM, "no energy groups are set (mdx_set_energy_groups)");
+    if (n_groups != G) FAIL(MDX_EPARAM, "n_groups must be the number of groups (mdx_energy_group_count)");
+    if (count == 0 || count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, "mdx_score_poses: count must be in 1..MDX_POSE_MAX_ATOMS (256)");
+    if ((uint64_t)first + count > h->N) FAIL(MDX_EPARAM, "atom range out of bounds");
+    if (h->dd || h->n_local != h->N) FAIL(MDX_EPARAM, "mdx_score_poses on a decomposed handle (single-device handles only)");
+    if (h->alch_on) FAIL(MDX_EPARAM, "mdx_score_poses while an alchemical window is active");
+    const bool fresh = !h->ps_valid || h->ps_first != first || h->ps_count != count || h->ps_epoch != h->grp_epoch;
+    uint32_t L = h->ps_group;
+    if (fresh) {
+        L = h->grp_host[first];
+        uint32_t members = 0;
+        for (uint32_t i = 0; i < h->N; ++i) members += h->grp_host[i] == L ? 1u : 0u;
+        bool whole = members == count;
+        for (uint32_t i = first; i < first + count && whole; ++i) whole = h->grp_host[i] == L;
+        if (!whole) FAIL(MDX_EPARAM, "mdx_score_poses: the range must be exactly one energy group");
+    }
+    const size_t per_pose = 3 * (size_t)count;
+    for (size_t k = 0; k < per_pose * n_poses; ++k)
+        if (!std::isfinite(poses[k])) FAIL(MDX_EPARAM, "mdx_score_poses: non-finite pose coordinate");
+    HIP_TRY(hipSetDevice(h->device));
+    if (fresh) {
+        h->ps_valid = false;
+        MDX_TRY(pose_table(h, first, count));
+        h->ps_valid = true; h->ps_first = first; h->ps_count = count; h->ps_group = L; h->ps_epoch = h->grp_epoch;
+    }
+    MDX_TRY(mdx_ensure_ready(h));          // what the matrix would see: list, constraints and virtual sites of the current state
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t chunk = std::min(n_poses, POSE_CHUNK);
+    if (h->ps_cap_stage < per_pose * chunk) {
+        if (d.ps_stage) { (void)hipFree(d.ps_stage); d.ps_stage = nullptr; }
+        h->ps_cap_stage = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_stage, sizeof(float) * per_pose * POSE_CHUNK));
+        h->ps_cap_stage = per_pose * POSE_CHUNK;
+    }
+    if (h->ps_cap_slab < (size_t)G) {
+        if (d.ps_slab) { (void)hipFree(d.ps_slab); d.ps_slab = nullptr; }
+        if (d.ps_rows) { (void)hipFree(d.ps_rows); d.ps_rows = nullptr; }
+        h->ps_cap_slab = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_slab, sizeof(double) * (size_t)POSE_CHUNK * (POSE_UNITS + 1u) * G));
+        HIP_TRY(hipMalloc((void**)&d.ps_rows, sizeof(double) * (size_t)POSE_CHUNK * G));
+        h->ps_cap_slab = G;
+    }
+    PoseArgs a{};
+    int mode = 0; bool geom = false, samecut = false;
+    mdx_fill_nb_params(h, a.p, &mode, &geom, &samecut);
+    a.g = h->grid;
+    a.posq = d.posq; a.lj = d.lj; a.orig_of = d.orig_of; a.gid = d.gid; a.grp = d.grp; a.slot_of = d.slot_of;
+    a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
+    a.G = G; a.L = L; a.first = first; a.count = count;
+    a.poses = d.ps_stage; a.slab = d.ps_slab;
+    a.r_cull = std::isfinite(h->r_list) ? h->r_list + 0.01f : INFINITY;
+    for (int k = 0; k < 3; ++k) {
+        a.box[k] = h->per[k] ? h->box_hi[k] - h->box_lo[k] : 0.f;
+        a.inv_box[k] = h->per[k] ? 1.0f / a.box[k] : 0.f;
+    }
+    a.cls = d.ps_cls; a.p14 = (const Pose14*)d.ps_p14; a.n14 = h->ps_n14;
+    std::vector<double> rows((size_t)chunk * G);
+    std::vector<float> res((size_t)n_poses * G);
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
+        const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
+        HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
+        mdx_prof_begin(h, 0);
+        switch (mode) {
+        case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n); break;
+        case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n); break;
+        case CM_RF: launch_poses<CM_RF>(h, a, geom, n); break;
+        default: launch_poses<CM_EWALD>(h, a, geom, n); break;
+        }
+        hipLaunchKernelGGL(pose_sum_kernel, dim3((n * G + 255u) / 256u), dim3(256), 0, st, n, G, d.ps_slab, d.ps_rows);
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rows.data(), d.ps_rows, sizeof(double) * (size_t)n * G, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t k = 0; k < (size_t)n * G; ++k) {
+            if (!std::isfinite(rows[k])) FAIL(MDX_ENAN, "mdx_score_poses: non-finite energy in a row");
+            res[(size_t)p0 * G + k] = (float)rows[k];
+        }
+    }
+    std::memcpy(out, res.data(), sizeof(float) * res.size());
+    return MDX_OK;
+}

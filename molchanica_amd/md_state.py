@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from ._abi import (CCommDiag, CHBond, CConfig, CEnergies, CStats, CSystem, FORCE, MDX_EDEVICE, MDX_ENAN, MDX_EOOM,
-                   MDX_EPARAM, MDX_OK, POS, VEL, MdConfig, MdSystem)
+                   MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, VEL, MdConfig, MdSystem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDX_LIB") or os.path.join(_HERE, "libmdx.so")   # MDX_LIB: A/B builds of the same ABI
@@ -167,6 +167,7 @@ def load_library():
     lib.mdx_snapshot_foreign_count.argtypes = [H, C.c_uint32]
     lib.mdx_snapshot_foreign_count.restype = C.c_uint32
     lib.mdx_snapshot_read_foreign.argtypes = [H, C.c_uint32, C.c_void_p, C.c_uint32]
+    lib.mdx_score_poses.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, C.c_uint32]
     _lib = lib
     return lib
 
@@ -266,6 +267,23 @@ class MdState:
         out = np.zeros((max(n, 1), max(n, 1)), dtype=np.float32)
         _check(lib.mdx_energy_between_mols(self._h, out.ctypes.data_as(_fp), n))
         return out
+
+    def score_poses(self, first: int, poses) -> np.ndarray:
+        """`mdx_score_poses`: the ligand row of energy_between_mols() for each of P alternative placements of the atoms [first,
+        first + count) - one whole energy group.  poses: float32 [P, count, 3] A, caller order.  -> float32 [P, n_groups] kcal/mol.
+        The state of the handle is left as it is; the docking loop ranks a batch per call instead of a pose per pair-list pass."""
+        if not isinstance(poses, np.ndarray) or poses.dtype != np.float32:
+            raise ParamError("score_poses: poses must be a float32 ndarray [P, count, 3]")
+        if poses.ndim != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= POSE_MAX_ATOMS:
+            raise ParamError(f"score_poses: poses must have shape [P, count, 3] with 1 <= count <= {POSE_MAX_ATOMS}, got {poses.shape}")
+        if int(first) < 0 or int(first) + poses.shape[1] > self.n_atoms:
+            raise ParamError("score_poses: atom range out of bounds")
+        lib = load_library()
+        a = np.ascontiguousarray(poses)
+        n = int(lib.mdx_energy_group_count(self._h))
+        out = np.zeros((a.shape[0], max(n, 1)), dtype=np.float32)
+        _check(lib.mdx_score_poses(self._h, int(first), a.shape[1], a.shape[0], a.ctypes.data_as(_fp), out.ctypes.data_as(_fp), n))
+        return out[:, :n] if n else out[:, :0]
 
     # -- position restraints (include/mdx.h: E = k max(0, |x - r0| - b)^2) ------------------------------------------------
     def set_position_restraints(self, idx, ref=None, k=1.0, flat_bottom=None):
