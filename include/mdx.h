@@ -549,6 +549,25 @@ int      mdx_single_point_between_mols(const mdx_system* sys, const mdx_config* 
 int      mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses,
                          const float* poses /* [n_poses][count][3] */, float* out /* [n_poses][n_groups] */, uint32_t n_groups);
 
+/* ---- the same batch with gradients: per-atom forces, net force and torque per pose (what a local pose refinement follows) -------
+ * Preconditions, refusals and the treatment of the handle are exactly those of mdx_score_poses; forces == NULL is MDX_EPARAM too, and
+ * a refused call leaves all three output buffers untouched.  With S_p = the sum over b of the row mdx_score_poses returns for pose p,
+ *   forces[p][i] = -dS_p / dx_i of ligand atom i, kcal/mol/A: the Lennard-Jones + Coulomb pair force (configured real-space
+ *     treatment, cutoffs, combining rule, minimum image per pair) from every atom outside the range, from the range's own non-excluded
+ *     pairs and from its scaled 1-4 pairs.  As in the row: no SPME mesh term, no bond / angle / dihedral term of the ligand, no 1-4
+ *     force under MDX_OVR_BONDED_DISABLED; an MDX_ATOM_BONDED_ONLY atom gets zero.  One exception to "minus the gradient": with
+ *     softening_sq != 0 the Coulomb force is the engine's softened one (r^2 / (r^2 + softening_sq) of the plain force, as in every force
+ *     call) while the row's Coulomb energy is not softened, so the two agree to softening_sq / r^2 relative only.
+ *   rigid[p] = (sum_i f_i, sum_i (x_i - c) x f_i), c = the unweighted mean of pose p's coordinates AS GIVEN: pass every pose as one
+ *     whole molecule.  The forces do not care across which box face an atom is wrapped; the torque does.  Both sums are taken on the
+ *     device in fp64, in atom order, of the unrounded forces.
+ *   rows_or_null, where given, receives the rows of mdx_score_poses for the same poses, bit for bit.
+ * The handle is not changed, and a pose gives the same bits (rows, forces, rigid) alone or in a batch of any size, at any place in it.
+ * MDX_ENAN: a non-finite energy or force (atoms on top of each other).  n_poses == 0 succeeds and does nothing. */
+int      mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses,
+                         const float* poses /* [n_poses][count][3] */, float* rows_or_null /* [n_poses][n_groups] */, uint32_t n_groups,
+                         float* forces /* [n_poses][count][3] */, float* rigid_or_null /* [n_poses][6] */);
+
 /* ---- multi-GPU: one periodic box spatially decomposed over the GPUs of a node (the reference is
  * single-device, src/util.rs:1086 `CudaContext::new(0)`, so this is new capability, not parity) -------------------
  * One rank (process or thread) per GPU.  Every rank creates a handle from the SAME global system (static per-atom data

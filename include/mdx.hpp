@@ -170,6 +170,19 @@ public:
         check(mdx_score_poses(h_, first, count, n, poses.data(), out.data(), g));
         return out;
     }
+    /// mdx_pose_forces: forces [n_poses][count][3] kcal/mol/A on the atoms of every pose (minus the gradient of the sum of its row);
+    /// rows (if not null) receives the rows of score_poses, rigid (if not null) [n_poses][6]: net force, torque about the pose's centroid.
+    std::vector<float> pose_forces(uint32_t first, uint32_t count, const std::vector<float>& poses, std::vector<float>* rows = nullptr,
+                                   std::vector<float>* rigid = nullptr) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        if (count == 0 || poses.size() % (3 * (size_t)count) != 0) throw std::invalid_argument("pose_forces: poses must hold [n_poses][count][3] floats");
+        const uint32_t n = (uint32_t)(poses.size() / (3 * (size_t)count));
+        std::vector<float> f(poses.size());
+        if (rows) rows->assign((size_t)n * g, 0.f);
+        if (rigid) rigid->assign((size_t)n * 6, 0.f);
+        check(mdx_pose_forces(h_, first, count, n, poses.data(), rows ? rows->data() : nullptr, g, f.data(), rigid ? rigid->data() : nullptr));
+        return f;
+    }
 
     /// `md.cell = SimBox::new(lo, hi)` + `md.rebuild_spatial_caches()` (sol_shrinking_box.rs:600-603, 632).
     void set_cell(const SimBox& b) { check(mdx_set_box(h_, b.bounds_low.data(), b.bounds_high.data())); }

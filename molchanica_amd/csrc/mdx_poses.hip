@@ -22,6 +22,20 @@
 //   Every unit writes its partial row into slab[pose][unit][group]; pose_sum_kernel adds the units in order.  Which tiles a unit
 //   takes, which cluster a wave takes and the order of every sum depend on the pose and the resident structure alone - not on the
 //   batch, its size or timing - so a pose gives the same bits alone or among 4096, anywhere in the batch.  No atomics.
+//
+// mdx_pose_forces: the same pass in its force flavour (FORCE = true; the energy flavour is the parent's code) - per pose the force on
+// every ligand atom, -d(sum of the row)/dx_i, and their net force and torque about the pose's centroid.
+//   environment units  pair_eval hands back the force on the environment atom; minus it is the force on ligand atom ja.  The eight ii
+//       lanes of a jj fold it with three fp32 shuffle-adds (eight pair forces: 3 roundings of 2^-24 of their gross sum, below what the
+//       fp32 pair arithmetic itself leaves), and lane ii = 0 adds the sum into the wave's own fp64 LDS accumulator [wave][xyz][ja]:
+//       the eight ja of a strip are distinct and the accumulator belongs to one wave - plain read-modify-write, no atomics.  fp64
+//       there because a ligand atom collects thousands of pair forces that largely cancel.  Dynamic LDS, 96 B per ligand atom (rounded
+//       up to whole strips): 5.4 kB for 50 atoms, 24 kB for 256.  At the end the four waves' sums are added in wave order.
+//   ligand unit  thread ia owns ligand atom ia: it walks ib in order over the class map (each plain pair is evaluated from both sides;
+//       d and -d give forces that are exact negatives) and the 1-4 records that name ia, fp64 in registers.  The energy part is the
+//       energy flavour's, statement by statement: the rows are the bits mdx_score_poses returns.
+//   Every unit writes fslab[pose][unit][count][3]; pose_force_sum_kernel adds the units in order, rounds to fp32 and forms the net
+//   force and the torque in fp64 in atom order.
 #include "mdx_bonded_dev.h"
 #include "mdx_pair_dev.h"
 #include <cmath>
@@ -43,6 +57,7 @@ struct PoseArgs {
     uint32_t G, L, first, count;
     const float* poses;            // [poses of the chunk][count][3]
     double* slab;                  // [poses of the chunk][POSE_UNITS + 1][G]
+    double* fslab;                 // force flavour: [poses of the chunk][POSE_UNITS + 1][count][3]
     float r_cull;                  // r_list (+ rounding room); not finite: no cutoff, everything is a candidate
     float box[3], inv_box[3];      // periodic axes (0: none)
     const uint8_t* cls; const Pose14* p14; uint32_t n14;
@@ -60,8 +75,9 @@ __device__ __forceinline__ void pose_fold(double& dacc, uint32_t key, double* ro
     dacc = 0.0;
 }
 
-template <int COUL, bool GEOM>
+template <int COUL, bool GEOM, bool FORCE>
 __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
+    extern __shared__ double s_f[];      // FORCE: [4 waves][xyz][fstride] (nothing otherwise)
     __shared__ float4 s_xyzq[MDX_POSE_MAX_ATOMS];
     __shared__ float2 s_lj[MDX_POSE_MAX_ATOMS];
     __shared__ double s_row[4][256];
@@ -97,6 +113,8 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
         hi[d] = fmaxf(fmaxf(s_bb[0][3 + d], s_bb[1][3 + d]), fmaxf(s_bb[2][3 + d], s_bb[3][3 + d]));
     }
     double* out = a.slab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * a.G;
+    const uint32_t fstride = ((count + 7u) >> 3) << 3;
+    double* fout = FORCE ? a.fslab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * count * 3u : nullptr;
 
     if (unit == POSE_UNITS) {
         // ---- the ligand's own pairs ----
@@ -128,8 +146,44 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
         if (lane == 0) s_row[wave][0] = acc;
         __syncthreads();
         if (tid < a.G) out[tid] = tid == a.L ? ((s_row[0][0] + s_row[1][0]) + s_row[2][0]) + s_row[3][0] : 0.0;
+        if (FORCE && tid < count) {
+            // thread ia: the force on ligand atom ia from the ligand's other atoms, ib in order, then the 1-4 records that name it
+            const uint32_t ia = tid;
+            const float4 pa = s_xyzq[ia];
+            const float2 la = s_lj[ia];
+            double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+            for (uint32_t ib = 0; ib < count; ++ib) {
+                if (ib == ia || a.cls[ib * count + ia] != 0) continue;      // (the map is symmetric: this row is read coalesced)
+                const float4 pb = s_xyzq[ib];
+                const float dx = pose_mimg(pa.x - pb.x, a.box[0], a.inv_box[0]), dy = pose_mimg(pa.y - pb.y, a.box[1], a.inv_box[1]),
+                            dz = pose_mimg(pa.z - pb.z, a.box[2], a.inv_box[2]);
+                float fx = 0.f, fy = 0.f, fz = 0.f, e1 = 0.f, e2 = 0.f;
+                pair_eval<false, COUL, GEOM, false, true, false, false, true>(dx, dy, dz, pa.w, la.x, la.y, make_float4(0.f, 0.f, 0.f, pb.w), s_lj[ib], true, a.p,
+                                                                            fx, fy, fz, e1, e2, nullptr, nullptr, nullptr, 0.f);
+                f0 += (double)fx; f1 += (double)fy; f2 += (double)fz;
+            }
+            for (uint32_t k = 0; k < a.n14; ++k) {
+                const Pose14 r = a.p14[k];
+                if (r.a != ia && r.b != ia) continue;
+                const float4 p0 = s_xyzq[r.a], p1 = s_xyzq[r.b];
+                const float dx = pose_mimg(p0.x - p1.x, a.box[0], a.inv_box[0]), dy = pose_mimg(p0.y - p1.y, a.box[1], a.inv_box[1]),
+                            dz = pose_mimg(p0.z - p1.z, a.box[2], a.inv_box[2]);
+                const float r2 = dx * dx + dy * dy + dz * dz, rinv = rsqrtf(r2), rinv2 = rinv * rinv;
+                const float s2 = r.sig * r.sig * rinv2, s6 = s2 * s2 * s2;
+                // -dE/dr / r of E = e4 s6 (s6 - 1) + qq / r, on atom r.a; r.b takes minus it
+                float fs = (6.0f * r.e4 * s6 * (2.0f * s6 - 1.0f) + r.qq * rinv) * rinv2;
+                if (r.b == ia) fs = -fs;
+                f0 += (double)(fs * dx); f1 += (double)(fs * dy); f2 += (double)(fs * dz);
+            }
+            fout[ia * 3u] = f0; fout[ia * 3u + 1u] = f1; fout[ia * 3u + 2u] = f2;
+        }
         return;
     }
+    if (FORCE) {
+        for (uint32_t i = tid; i < 12u * fstride; i += 256u) s_f[i] = 0.0;
+        __syncthreads();
+    }
+    double* facc = s_f + (size_t)wave * 3u * fstride;
 
     // ---- the environment ----
     const GridParams& g = a.g;
@@ -204,6 +258,16 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
                         pair_eval<true, COUL, GEOM, false, true, false, false, true>(dx, dy, dz, pi.w, li.x, li.y, make_float4(0.f, 0.f, 0.f, pj.w), lj, true, a.p,
                                                                                    fx, fy, fz, e1, e2, nullptr, nullptr, nullptr, bias);
                         dacc += (double)(e1 + e2);
+                        if (FORCE) {
+                            // fx is the force on the environment atom: the ligand atom takes minus it, summed over the eight ii
+                            float lx = -fx, ly = -fy, lz = -fz;
+                            lx += __shfl_xor(lx, 1); ly += __shfl_xor(ly, 1); lz += __shfl_xor(lz, 1);
+                            lx += __shfl_xor(lx, 2); ly += __shfl_xor(ly, 2); lz += __shfl_xor(lz, 2);
+                            lx += __shfl_xor(lx, 4); ly += __shfl_xor(ly, 4); lz += __shfl_xor(lz, 4);
+                            if (ii == 0 && (lx != 0.f || ly != 0.f || lz != 0.f)) {
+                                facc[ja] += (double)lx; facc[fstride + ja] += (double)ly; facc[2u * fstride + ja] += (double)lz;
+                            }
+                        }
                     }
                 }
             }
@@ -212,6 +276,11 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
     pose_fold(dacc, cur_g, row, lane);
     __syncthreads();
     if (tid < a.G) out[tid] = ((s_row[0][tid] + s_row[1][tid]) + s_row[2][tid]) + s_row[3][tid];
+    if (FORCE)
+        for (uint32_t i = tid; i < count * 3u; i += 256u) {
+            const uint32_t ia = i / 3u, k = (i - ia * 3u) * fstride + ia;
+            fout[i] = ((s_f[k] + s_f[3u * fstride + k]) + s_f[6u * fstride + k]) + s_f[9u * fstride + k];
+        }
 }
 
 __global__ __launch_bounds__(256) void pose_sum_kernel(uint32_t n, uint32_t G, const double* __restrict__ slab, double* __restrict__ rows) {
@@ -224,27 +293,63 @@ __global__ __launch_bounds__(256) void pose_sum_kernel(uint32_t n, uint32_t G, c
     rows[i] = v;
 }
 
+// forces[pose][atom] = the units' partial forces added in unit order (fp64, rounded once); rigid[pose] = (sum_i f_i, sum_i (x_i - c) x f_i),
+// c the unweighted mean of the pose's coordinates as the caller gave them - fp64, atom order, of the unrounded forces.
+__global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, const float* __restrict__ poses, const double* __restrict__ fslab,
+                                                             float* __restrict__ forces, float* __restrict__ rigid) {
+    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_c[3];
+    const uint32_t tid = threadIdx.x, pose = blockIdx.x;
+    if (tid < count) {
+        const double* s = fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
+        const size_t at = ((size_t)pose * count + tid) * 3u;
+        for (uint32_t c = 0; c < 3u; ++c) {
+            double v = 0.0;
+            for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * count * 3u + c];
+            s_v[tid][c] = v; s_x[tid][c] = (double)poses[at + c];
+            forces[at + c] = (float)v;
+        }
+    }
+    __syncthreads();
+    if (tid < 3u) {
+        double c = 0.0;
+        for (uint32_t i = 0; i < count; ++i) c += s_x[i][tid];
+        s_c[tid] = c / (double)count;
+    }
+    __syncthreads();
+    if (tid < 6u) {
+        const uint32_t d = tid % 3u, d1 = (d + 1u) % 3u, d2 = (d + 2u) % 3u;
+        double v = 0.0;
+        for (uint32_t i = 0; i < count; ++i)
+            v += tid < 3u ? s_v[i][d] : (s_x[i][d1] - s_c[d1]) * s_v[i][d2] - (s_x[i][d2] - s_c[d2]) * s_v[i][d1];
+        rigid[(size_t)pose * 6u + tid] = (float)v;
+    }
+}
+
 template <int COUL>
-static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n) {
+static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force) {
     const dim3 g(POSE_UNITS + 1u, n), b(256);
-    if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true>), g, b, 0, h->stream, a);
-    else hipLaunchKernelGGL((pose_score_kernel<COUL, false>), g, b, 0, h->stream, a);
+    if (force) {
+        const size_t lds = sizeof(double) * 12u * (((a.count + 7u) >> 3) << 3);
+        if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, true>), g, b, lds, h->stream, a);
+        else hipLaunchKernelGGL((pose_score_kernel<COUL, false, true>), g, b, lds, h->stream, a);
+    } else if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, false>), g, b, 0, h->stream, a);
+    else hipLaunchKernelGGL((pose_score_kernel<COUL, false, false>), g, b, 0, h->stream, a);
 }
 
 // The ligand's own pairs, once per (range, group map): who is excluded, who is a scaled 1-4 pair and with what parameters - from the
 // handle's merged exclusion / 1-4 CSR and the 1-4 roles of the bonded gather.  Refuses a range that is tied to the outside.
-static int pose_table(mdx_handle* h, uint32_t first, uint32_t count) {
+static int pose_table(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count) {
     DeviceState& d = h->d;
     hipStream_t st = h->stream;
     const uint32_t last = first + count;
     auto inside = [&](uint32_t i) { return i >= first && i < last; };
     for (size_t k = 0; k + 1 < h->h_bond_pairs.size(); k += 2)
         if (inside(h->h_bond_pairs[k]) != inside(h->h_bond_pairs[k + 1]))
-            FAIL(MDX_EPARAM, "mdx_score_poses: a bond or constraint links the range to an atom outside it");
+            FAIL(MDX_EPARAM, who + ": a bond or constraint links the range to an atom outside it");
     for (const VSite& v : h->h_vsites) {
         const bool in = inside(v.site);
         if (inside(v.p0) != in || inside(v.p1) != in || inside(v.p2) != in)
-            FAIL(MDX_EPARAM, "mdx_score_poses: a virtual site links the range to an atom outside it");
+            FAIL(MDX_EPARAM, who + ": a virtual site links the range to an atom outside it");
     }
     std::vector<uint32_t> off(count + 1), idx;
     HIP_TRY(hipMemcpyAsync(off.data(), d.excl_off + first, sizeof(uint32_t) * (count + 1), hipMemcpyDeviceToHost, st));
@@ -265,7 +370,7 @@ static int pose_table(mdx_handle* h, uint32_t first, uint32_t count) {
     std::vector<uint8_t> cls((size_t)count * count, 0);
     for (uint32_t i = 0; i < count; ++i)
         for (uint32_t k = off[i] - off[0]; k < off[i + 1] - off[0]; ++k) {
-            if (!inside(idx[k])) FAIL(MDX_EPARAM, "mdx_score_poses: an exclusion or 1-4 pair links the range to an atom outside it");
+            if (!inside(idx[k])) FAIL(MDX_EPARAM, who + ": an exclusion or 1-4 pair links the range to an atom outside it");
             cls[(size_t)i * count + (idx[k] - first)] = 1;      // (the CSR is symmetric)
         }
     std::vector<Pose14> p14;
@@ -274,7 +379,7 @@ static int pose_table(mdx_handle* h, uint32_t first, uint32_t count) {
         for (uint32_t k = roff[i] - roff[0]; k < roff[i + 1] - roff[0] && k < recs.size(); ++k) {
             const RoleRec& r = recs[k];
             if ((r.meta & 0xFu) != ROLE_PAIR14 || ((r.meta >> 4) & 0xFu) != 0u) continue;
-            if (!inside(r.p[0])) FAIL(MDX_EPARAM, "mdx_score_poses: an exclusion or 1-4 pair links the range to an atom outside it");
+            if (!inside(r.p[0])) FAIL(MDX_EPARAM, who + ": an exclusion or 1-4 pair links the range to an atom outside it");
             const uint32_t b = r.p[0] - first, pi = r.meta >> 8;
             cls[(size_t)i * count + b] = 2; cls[(size_t)b * count + i] = 2;
             if (skip14 || pi >= prm.size()) continue;      // (bonded terms disabled: the matrix leaves the scaled pairs out too)
@@ -291,18 +396,17 @@ static int pose_table(mdx_handle* h, uint32_t first, uint32_t count) {
     return MDX_OK;
 }
 
-extern "C" int mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, float* out,
-                               uint32_t n_groups) {
-    if (!h) FAIL(MDX_EPARAM, "null handle");
-    if (n_poses == 0) return MDX_OK;
-    if (!poses || !out) FAIL(MDX_EPARAM, "null argument");
+// mdx_score_poses (forces == nullptr: the energy flavour, rows only) and mdx_pose_forces (the force flavour; out / rigid may be null)
+static int pose_run(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, float* out,
+                    uint32_t n_groups, float* forces, float* rigid) {
+    const bool force = forces != nullptr;
     const uint32_t G = h->n_grp;
     if (!G) FAIL(MDX_EPARAM, "no energy groups are set (mdx_set_energy_groups)");
     if (n_groups != G) FAIL(MDX_EPARAM, "n_groups must be the number of groups (mdx_energy_group_count)");
-    if (count == 0 || count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, "mdx_score_poses: count must be in 1..MDX_POSE_MAX_ATOMS (256)");
+    if (count == 0 || count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, who + ": count must be in 1..MDX_POSE_MAX_ATOMS (256)");
     if ((uint64_t)first + count > h->N) FAIL(MDX_EPARAM, "atom range out of bounds");
-    if (h->dd || h->n_local != h->N) FAIL(MDX_EPARAM, "mdx_score_poses on a decomposed handle (single-device handles only)");
-    if (h->alch_on) FAIL(MDX_EPARAM, "mdx_score_poses while an alchemical window is active");
+    if (h->dd || h->n_local != h->N) FAIL(MDX_EPARAM, who + " on a decomposed handle (single-device handles only)");
+    if (h->alch_on) FAIL(MDX_EPARAM, who + " while an alchemical window is active");
     const bool fresh = !h->ps_valid || h->ps_first != first || h->ps_count != count || h->ps_epoch != h->grp_epoch;
     uint32_t L = h->ps_group;
     if (fresh) {
@@ -311,15 +415,15 @@ extern "C" int mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, ui
         for (uint32_t i = 0; i < h->N; ++i) members += h->grp_host[i] == L ? 1u : 0u;
         bool whole = members == count;
         for (uint32_t i = first; i < first + count && whole; ++i) whole = h->grp_host[i] == L;
-        if (!whole) FAIL(MDX_EPARAM, "mdx_score_poses: the range must be exactly one energy group");
+        if (!whole) FAIL(MDX_EPARAM, who + ": the range must be exactly one energy group");
     }
     const size_t per_pose = 3 * (size_t)count;
     for (size_t k = 0; k < per_pose * n_poses; ++k)
-        if (!std::isfinite(poses[k])) FAIL(MDX_EPARAM, "mdx_score_poses: non-finite pose coordinate");
+        if (!std::isfinite(poses[k])) FAIL(MDX_EPARAM, who + ": non-finite pose coordinate");
     HIP_TRY(hipSetDevice(h->device));
     if (fresh) {
         h->ps_valid = false;
-        MDX_TRY(pose_table(h, first, count));
+        MDX_TRY(pose_table(h, who, first, count));
         h->ps_valid = true; h->ps_first = first; h->ps_count = count; h->ps_group = L; h->ps_epoch = h->grp_epoch;
     }
     MDX_TRY(mdx_ensure_ready(h));          // what the matrix would see: list, constraints and virtual sites of the current state
@@ -340,6 +444,15 @@ extern "C" int mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, ui
         HIP_TRY(hipMalloc((void**)&d.ps_rows, sizeof(double) * (size_t)POSE_CHUNK * G));
         h->ps_cap_slab = G;
     }
+    if (force && h->ps_cap_fslab < per_pose) {
+        if (d.ps_fslab) { (void)hipFree(d.ps_fslab); d.ps_fslab = nullptr; }
+        if (d.ps_fout) { (void)hipFree(d.ps_fout); d.ps_fout = nullptr; }
+        h->ps_cap_fslab = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_fslab, sizeof(double) * (size_t)POSE_CHUNK * (POSE_UNITS + 1u) * per_pose));
+        HIP_TRY(hipMalloc((void**)&d.ps_fout, sizeof(float) * (size_t)POSE_CHUNK * per_pose));
+        if (!d.ps_rigid) HIP_TRY(hipMalloc((void**)&d.ps_rigid, sizeof(float) * (size_t)POSE_CHUNK * 6u));
+        h->ps_cap_fslab = per_pose;
+    }
     PoseArgs a{};
     int mode = 0; bool geom = false, samecut = false;
     mdx_fill_nb_params(h, a.p, &mode, &geom, &samecut);
@@ -347,7 +460,7 @@ extern "C" int mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, ui
     a.posq = d.posq; a.lj = d.lj; a.orig_of = d.orig_of; a.gid = d.gid; a.grp = d.grp; a.slot_of = d.slot_of;
     a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
     a.G = G; a.L = L; a.first = first; a.count = count;
-    a.poses = d.ps_stage; a.slab = d.ps_slab;
+    a.poses = d.ps_stage; a.slab = d.ps_slab; a.fslab = d.ps_fslab;
     a.r_cull = std::isfinite(h->r_list) ? h->r_list + 0.01f : INFINITY;
     for (int k = 0; k < 3; ++k) {
         a.box[k] = h->per[k] ? h->box_hi[k] - h->box_lo[k] : 0.f;
@@ -355,27 +468,54 @@ extern "C" int mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, ui
     }
     a.cls = d.ps_cls; a.p14 = (const Pose14*)d.ps_p14; a.n14 = h->ps_n14;
     std::vector<double> rows((size_t)chunk * G);
-    std::vector<float> res((size_t)n_poses * G);
+    std::vector<float> res((size_t)n_poses * G), fres(force ? per_pose * n_poses : 0), rres(force ? 6u * (size_t)n_poses : 0);
     for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
         const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
         HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
         mdx_prof_begin(h, 0);
         switch (mode) {
-        case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n); break;
-        case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n); break;
-        case CM_RF: launch_poses<CM_RF>(h, a, geom, n); break;
-        default: launch_poses<CM_EWALD>(h, a, geom, n); break;
+        case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, force); break;
+        case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, force); break;
+        case CM_RF: launch_poses<CM_RF>(h, a, geom, n, force); break;
+        default: launch_poses<CM_EWALD>(h, a, geom, n, force); break;
         }
         hipLaunchKernelGGL(pose_sum_kernel, dim3((n * G + 255u) / 256u), dim3(256), 0, st, n, G, d.ps_slab, d.ps_rows);
+        if (force) hipLaunchKernelGGL(pose_force_sum_kernel, dim3(n), dim3(256), 0, st, count, d.ps_stage, d.ps_fslab, d.ps_fout, d.ps_rigid);
         mdx_prof_end(h);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(rows.data(), d.ps_rows, sizeof(double) * (size_t)n * G, hipMemcpyDeviceToHost, st));
+        if (force) {
+            HIP_TRY(hipMemcpyAsync(fres.data() + per_pose * p0, d.ps_fout, sizeof(float) * per_pose * n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(rres.data() + 6u * (size_t)p0, d.ps_rigid, sizeof(float) * 6u * n, hipMemcpyDeviceToHost, st));
+        }
         HIP_TRY(hipStreamSynchronize(st));
+        for (size_t k = 0; force && k < per_pose * n; ++k)
+            if (!std::isfinite(fres[per_pose * p0 + k])) FAIL(MDX_ENAN, who + ": non-finite force");
+        for (size_t k = 0; force && k < 6u * (size_t)n; ++k)
+            if (!std::isfinite(rres[6u * (size_t)p0 + k])) FAIL(MDX_ENAN, who + ": non-finite net force or torque");
         for (size_t k = 0; k < (size_t)n * G; ++k) {
-            if (!std::isfinite(rows[k])) FAIL(MDX_ENAN, "mdx_score_poses: non-finite energy in a row");
+            if (!std::isfinite(rows[k])) FAIL(MDX_ENAN, who + ": non-finite energy in a row");
             res[(size_t)p0 * G + k] = (float)rows[k];
         }
     }
-    std::memcpy(out, res.data(), sizeof(float) * res.size());
+    if (out) std::memcpy(out, res.data(), sizeof(float) * res.size());
+    if (force) std::memcpy(forces, fres.data(), sizeof(float) * fres.size());
+    if (force && rigid) std::memcpy(rigid, rres.data(), sizeof(float) * rres.size());
     return MDX_OK;
+}
+
+extern "C" int mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, float* out,
+                               uint32_t n_groups) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_poses == 0) return MDX_OK;
+    if (!poses || !out) FAIL(MDX_EPARAM, "null argument");
+    return pose_run(h, "mdx_score_poses", first, count, n_poses, poses, out, n_groups, nullptr, nullptr);
+}
+
+extern "C" int mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, float* rows_or_null,
+                               uint32_t n_groups, float* forces, float* rigid_or_null) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_poses == 0) return MDX_OK;
+    if (!poses || !forces) FAIL(MDX_EPARAM, "null argument");
+    return pose_run(h, "mdx_pose_forces", first, count, n_poses, poses, rows_or_null, n_groups, forces, rigid_or_null);
 }

@@ -168,6 +168,7 @@ def load_library():
     lib.mdx_snapshot_foreign_count.restype = C.c_uint32
     lib.mdx_snapshot_read_foreign.argtypes = [H, C.c_uint32, C.c_void_p, C.c_uint32]
     lib.mdx_score_poses.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, C.c_uint32]
+    lib.mdx_pose_forces.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, C.c_uint32, _fp, _fp]
     _lib = lib
     return lib
 
@@ -284,6 +285,33 @@ class MdState:
         out = np.zeros((a.shape[0], max(n, 1)), dtype=np.float32)
         _check(lib.mdx_score_poses(self._h, int(first), a.shape[1], a.shape[0], a.ctypes.data_as(_fp), out.ctypes.data_as(_fp), n))
         return out[:, :n] if n else out[:, :0]
+
+    def pose_forces(self, first: int, poses, rows=True, rigid=False):
+        """`mdx_pose_forces`: the force on every atom of each of P alternative placements of the atoms [first, first + count) - minus
+        the gradient of the sum of the pose's score_poses() row.  poses: float32 [P, count, 3] A, each a whole molecule.
+        -> (forces [P, count, 3] kcal/mol/A[, rows [P, n_groups] - the bits of score_poses()][, rigid [P, 6]: net force, torque about
+        the pose's centroid]), all float32; rows / rigid false or None leave the entry out.  The handle is left as it is."""
+        if not isinstance(poses, np.ndarray) or poses.dtype != np.float32:
+            raise ParamError("pose_forces: poses must be a float32 ndarray [P, count, 3]")
+        if poses.ndim != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= POSE_MAX_ATOMS:
+            raise ParamError(f"pose_forces: poses must have shape [P, count, 3] with 1 <= count <= {POSE_MAX_ATOMS}, got {poses.shape}")
+        if int(first) < 0 or int(first) + poses.shape[1] > self.n_atoms:
+            raise ParamError("pose_forces: atom range out of bounds")
+        lib = load_library()
+        a = np.ascontiguousarray(poses)
+        n = int(lib.mdx_energy_group_count(self._h))
+        f = np.zeros(a.shape, dtype=np.float32)
+        r = np.zeros((a.shape[0], max(n, 1)), dtype=np.float32) if rows else None
+        t = np.zeros((a.shape[0], 6), dtype=np.float32) if rigid else None
+        _check(lib.mdx_pose_forces(self._h, int(first), a.shape[1], a.shape[0], a.ctypes.data_as(_fp),
+                                   None if r is None else r.ctypes.data_as(_fp), n, f.ctypes.data_as(_fp),
+                                   None if t is None else t.ctypes.data_as(_fp)))
+        out = (f,)
+        if r is not None:
+            out += (r[:, :n] if n else r[:, :0],)
+        if t is not None:
+            out += (t,)
+        return out
 
     # -- position restraints (include/mdx.h: E = k max(0, |x - r0| - b)^2) ------------------------------------------------
     def set_position_restraints(self, idx, ref=None, k=1.0, flat_bottom=None):
