@@ -568,6 +568,49 @@ int      mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, uint32_t
                          const float* poses /* [n_poses][count][3] */, float* rows_or_null /* [n_poses][n_groups] */, uint32_t n_groups,
                          float* forces /* [n_poses][count][3] */, float* rigid_or_null /* [n_poses][6] */);
 
+/* ---- local refinement of the same batch on the device: rigid-body steepest descent, one adaptive step length per pose -------------
+ * What a host loop over mdx_pose_forces with the stepper below would produce, without its round trips: per chunk of 256 poses the
+ * library enqueues max_evals x (force pass, step kernel) and waits once.  Preconditions, refusals and the treatment of the handle are
+ * exactly those of mdx_pose_forces (the handle is not changed; a refused call writes nothing).  MDX_EPARAM also for: opts or poses_out
+ * NULL; max_evals == 0 or > MDX_REFINE_MAX_EVALS_CAP; f_tol, tau_tol, h_start or h_max negative or not finite; h_start > h_max (after the
+ * defaults: h_start == 0 selects 0.01 A, h_max == 0 selects 0.2 A, the values of mdx_minimize_energy).  n_poses == 0 succeeds and does nothing.
+ *
+ * The stepper, per pose, fp64 unless it says fp32; n = count, atoms in caller order, X0 the input pose (fp32):
+ *   setup       c0 = (1/n) sum X0_i, b_i = X0_i - c0; unit quaternion q = (1, 0, 0, 0) in (w, x, y, z) order, translation t = 0, step h = h_start;
+ *               coords(q, t)_i = fp32(c0 + t + R(q) b_i), which is X0 bit for bit at q = identity, t = 0.
+ *   evaluation k = 0, 1, ... at the trial Y = coords(q_try, t_try): r = the row mdx_score_poses gives for Y, forces and rigid = what
+ *               mdx_pose_forces gives for Y (fp32, the same bits), S = sum_b (double) r[b] in group order.
+ *               Anything in r, the forces or rigid not finite: at k = 0 the pose ends with status MDX_REFINE_NONFINITE - its outputs
+ *               are the input pose and whatever row and rigid were computed; the call as a whole does not fail for it - and at
+ *               k > 0 the evaluation counts as a reject.
+ *     accept    when k = 0 or S < S_accepted: the accepted state becomes (q_try, t_try, S, r, rigid, Y); for k > 0 h <- min(1.2 h, h_max);
+ *               |rigid[0:3]| <= f_tol and |rigid[3:6]| <= tau_tol: MDX_REFINE_CONVERGED, the pose ends.
+ *     reject    h <- 0.5 h; h < 1e-5 A (one fp32 ulp of a coordinate at 100 A: the trial would be the accepted pose): MDX_REFINE_STALLED, the pose ends.
+ *   next trial  always from the accepted state: v = F_net / n; c = the mean of (double) Y_i (the centroid rigid was taken about),
+ *               r_i = Y_i - c, I = sum_i (|r_i|^2 E - r_i r_i^T), omega = (I + lambda E)^-1 tau with lambda = 1e-6 trace(I) + 1e-12 A^2
+ *               (one atom, two atoms or collinear atoms leave I a null axis; a rotation about it moves nothing, and omega = 0 for
+ *               n = 1); u_i = v + omega x r_i, m = max_i |u_i| - (v, omega) is the least-squares projection of the per-atom descent
+ *               field onto rigid motions; m == 0: MDX_REFINE_CONVERGED.  s = h / m, t_try = t + s v, q_try = normalise(dq (x) q),
+ *               dq the rotation by s |omega| about omega / |omega| (the identity for omega = 0): no atom moves further than h.
+ *   end         after max_evals evaluations a pose that has not ended gets MDX_REFINE_MAX_EVALS.  evals[p] >= 1 counts its evaluations.
+ * Outputs, all of the ACCEPTED state: poses_out[p] = its coordinates Y, rows_out[p] = its row (the bits mdx_score_poses returns for
+ * poses_out[p]), rigid_out[p] (the bits mdx_pose_forces returns for it), xform_out[p] = (q, t) rounded to fp32 - coords(q, t) of the
+ * rounded values reproduces poses_out to about 1e-6 of the molecule's extent only -, status_out[p], evals_out[p].
+ * A pose gives the same bits (poses, rows, rigid, status, evals) alone or in a batch of any size, at any place in it.  Pass every pose
+ * as one whole molecule: centroid, torque and inertia are taken of the coordinates as given.  The gradient carries no bond, angle or
+ * dihedral term of the ligand, so the refinement is rigid; with tolerances of 0 every pose runs until it stalls or max_evals is spent. */
+typedef struct { uint32_t max_evals; float f_tol, tau_tol, h_start, h_max; } mdx_refine_opts;
+#define MDX_REFINE_CONVERGED 0u
+#define MDX_REFINE_MAX_EVALS 1u
+#define MDX_REFINE_STALLED   2u
+#define MDX_REFINE_NONFINITE 3u
+#define MDX_REFINE_MAX_EVALS_CAP 4096u
+int      mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses /* [n_poses][count][3] */,
+                          const mdx_refine_opts* opts, float* poses_out /* [n_poses][count][3] */,
+                          float* rows_out_or_null /* [n_poses][n_groups] */, uint32_t n_groups, float* rigid_out_or_null /* [n_poses][6] */,
+                          float* xform_out_or_null /* [n_poses][7]: q (w, x, y, z), t */, uint32_t* status_out_or_null /* [n_poses] */,
+                          uint32_t* evals_out_or_null /* [n_poses] */);
+
 /* ---- multi-GPU: one periodic box spatially decomposed over the GPUs of a node (the reference is
  * single-device, src/util.rs:1086 `CudaContext::new(0)`, so this is new capability, not parity) -------------------
  * One rank (process or thread) per GPU.  Every rank creates a handle from the SAME global system (static per-atom data

@@ -183,6 +183,22 @@ public:
         check(mdx_pose_forces(h_, first, count, n, poses.data(), rows ? rows->data() : nullptr, g, f.data(), rigid ? rigid->data() : nullptr));
         return f;
     }
+    /// mdx_refine_poses: rigid-body steepest descent of every pose on the device (the stepper is stated in mdx.h).
+    struct RefinedPoses {
+        std::vector<float> poses, rows, rigid, xform;      ///< [n][count][3], [n][n_groups], [n][6], [n][7] = q (w, x, y, z), t - of the accepted state
+        std::vector<uint32_t> status, evals;               ///< MDX_REFINE_* and the evaluations taken, per pose
+    };
+    RefinedPoses refine_poses(uint32_t first, uint32_t count, const std::vector<float>& poses, const mdx_refine_opts& opts) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        if (count == 0 || poses.size() % (3 * (size_t)count) != 0) throw std::invalid_argument("refine_poses: poses must hold [n_poses][count][3] floats");
+        const uint32_t n = (uint32_t)(poses.size() / (3 * (size_t)count));
+        RefinedPoses r;
+        r.poses.assign(poses.size(), 0.f); r.rows.assign((size_t)n * g, 0.f); r.rigid.assign((size_t)n * 6, 0.f); r.xform.assign((size_t)n * 7, 0.f);
+        r.status.assign(n, 0u); r.evals.assign(n, 0u);
+        check(mdx_refine_poses(h_, first, count, n, poses.data(), &opts, r.poses.data(), r.rows.data(), g, r.rigid.data(), r.xform.data(),
+                               r.status.data(), r.evals.data()));
+        return r;
+    }
 
     /// `md.cell = SimBox::new(lo, hi)` + `md.rebuild_spatial_caches()` (sol_shrinking_box.rs:600-603, 632).
     void set_cell(const SimBox& b) { check(mdx_set_box(h_, b.bounds_low.data(), b.bounds_high.data())); }

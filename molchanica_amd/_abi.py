@@ -25,6 +25,8 @@ COMBINE_LORENTZ_BERTHELOT, COMBINE_GEOMETRIC = 0, 1
 POS, VEL, FORCE = 0, 1, 2
 
 POSE_MAX_ATOMS = 256   # MDX_POSE_MAX_ATOMS: the largest ligand mdx_score_poses takes
+REFINE_CONVERGED, REFINE_MAX_EVALS, REFINE_STALLED, REFINE_NONFINITE = 0, 1, 2, 3      # MDX_REFINE_*: status of a refined pose
+REFINE_MAX_EVALS_CAP = 4096      # MDX_REFINE_MAX_EVALS_CAP
 
 _fp = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
@@ -60,6 +62,11 @@ class CConfig(C.Structure):
         ("nb_variant", C.c_uint32), ("constraint_tol", C.c_float), ("constraint_max_iter", C.c_uint32),
         ("pme_grid", C.c_uint32 * 3), ("pme_order", C.c_uint32), ("inner_skin", C.c_float),
     ]
+
+
+class CRefineOpts(C.Structure):
+    """mdx_refine_opts"""
+    _fields_ = [("max_evals", C.c_uint32), ("f_tol", C.c_float), ("tau_tol", C.c_float), ("h_start", C.c_float), ("h_max", C.c_float)]
 
 
 class CEnergies(C.Structure):

@@ -286,6 +286,8 @@ struct DeviceState {
     uint8_t* ps_cls = nullptr; void* ps_p14 = nullptr; float* ps_stage = nullptr; double* ps_slab = nullptr; double* ps_rows = nullptr;
     // mdx_pose_forces: the units' fp64 partial forces [chunk][units][count][3], the summed forces [chunk][count][3], net force and torque [chunk][6]
     double* ps_fslab = nullptr; float* ps_fout = nullptr; float* ps_rigid = nullptr;
+    // mdx_refine_poses: frozen words, state records, accepted coordinates / rows / rigid and the input poses of one chunk (RefineLayout)
+    void* ps_refine = nullptr;
 };
 
 struct MdxDecomp;   // mdx_comm.h: the handle is one rank of a spatially decomposed box
@@ -352,7 +354,7 @@ struct mdx_handle {
     uint64_t grp_epoch = 0;                                                       // ... counts the calls: what was derived from a map knows its age
     // mdx_score_poses (mdx_poses.hip): the range and the group map the intra-ligand table was built for, its group, its 1-4 records
     bool ps_valid = false; uint32_t ps_first = 0, ps_count = 0, ps_group = 0, ps_n14 = 0; uint64_t ps_epoch = 0;
-    size_t ps_cap_stage = 0, ps_cap_slab = 0, ps_cap_fslab = 0;
+    size_t ps_cap_stage = 0, ps_cap_slab = 0, ps_cap_fslab = 0, ps_cap_refine = 0;
     bool alch_on = false; double alch_lambda = 0.0; uint32_t alch_lo = 0, alch_hi = 0;
     float sc_alpha = 0.5f, sc_sigma_min = 3.0f;   // soft core of the alchemical window (mdx_set_alchemical_softcore)
     std::vector<double> foreign_lams;             // mdx_set_foreign_lambdas (survives window changes; empty: none)

@@ -36,8 +36,17 @@
 //       energy flavour's, statement by statement: the rows are the bits mdx_score_poses returns.
 //   Every unit writes fslab[pose][unit][count][3]; pose_force_sum_kernel adds the units in order, rounds to fp32 and forms the net
 //   force and the torque in fp64 in atom order.
+//
+// mdx_refine_poses: a rigid-body steepest descent of every pose of the batch with its own adaptive step length (the rule of
+// mdx_minimize_energy carried over to rigid motions; mdx_refine_step.h holds its arithmetic), max_evals x (the force flavour,
+// pose_refine_step_kernel) per chunk on the stream, one read-back and one wait at the end.
+//   pose_refine_step_kernel  one workgroup per pose.  It adds the units' rows and forces as the two sum kernels do, forms rigid as
+//       pose_force_sum_kernel does, accepts or rejects the trial from the pose's state record, and writes the next trial into the
+//       staging buffer the force flavour reads.  A pose that has finished sets its word in frozen[]; the REFINE instantiation of
+//       pose_score_kernel reads it before anything else and the whole workgroup returns, as the step kernel's does.
 #include "mdx_bonded_dev.h"
 #include "mdx_pair_dev.h"
+#include "mdx_refine_step.h"
 #include <cmath>
 #include <cstring>
 
@@ -61,6 +70,7 @@ struct PoseArgs {
     float r_cull;                  // r_list (+ rounding room); not finite: no cutoff, everything is a candidate
     float box[3], inv_box[3];      // periodic axes (0: none)
     const uint8_t* cls; const Pose14* p14; uint32_t n14;
+    const uint32_t* frozen;        // REFINE: [poses of the chunk], non-zero = the pose has finished, its workgroups return at once
 };
 
 __device__ __forceinline__ float pose_mimg(float d, float box, float inv) { return box > 0.f ? d - rintf(d * inv) * box : d; }
@@ -75,9 +85,10 @@ __device__ __forceinline__ void pose_fold(double& dacc, uint32_t key, double* ro
     dacc = 0.0;
 }
 
-template <int COUL, bool GEOM, bool FORCE>
+template <int COUL, bool GEOM, bool FORCE, bool REFINE = false>
 __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
     extern __shared__ double s_f[];      // FORCE: [4 waves][xyz][fstride] (nothing otherwise)
+    if (REFINE && a.frozen[blockIdx.y] != 0u) return;      // (uniform over the workgroup, before any barrier)
     __shared__ float4 s_xyzq[MDX_POSE_MAX_ATOMS];
     __shared__ float2 s_lj[MDX_POSE_MAX_ATOMS];
     __shared__ double s_row[4][256];
@@ -293,6 +304,15 @@ __global__ __launch_bounds__(256) void pose_sum_kernel(uint32_t n, uint32_t G, c
     rows[i] = v;
 }
 
+// component k of (sum_i f_i, sum_i (x_i - c) x f_i), atoms in order: the one statement both kernels below take rigid from
+__device__ __forceinline__ double pose_rigid_component(uint32_t k, uint32_t count, const double (*s_x)[3], const double (*s_v)[3], const double* s_c) {
+    const uint32_t d = k % 3u, d1 = (d + 1u) % 3u, d2 = (d + 2u) % 3u;
+    double v = 0.0;
+    for (uint32_t i = 0; i < count; ++i)
+        v += k < 3u ? s_v[i][d] : (s_x[i][d1] - s_c[d1]) * s_v[i][d2] - (s_x[i][d2] - s_c[d2]) * s_v[i][d1];
+    return v;
+}
+
 // forces[pose][atom] = the units' partial forces added in unit order (fp64, rounded once); rigid[pose] = (sum_i f_i, sum_i (x_i - c) x f_i),
 // c the unweighted mean of the pose's coordinates as the caller gave them - fp64, atom order, of the unrounded forces.
 __global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, const float* __restrict__ poses, const double* __restrict__ fslab,
@@ -316,19 +336,123 @@ __global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, con
         s_c[tid] = c / (double)count;
     }
     __syncthreads();
-    if (tid < 6u) {
-        const uint32_t d = tid % 3u, d1 = (d + 1u) % 3u, d2 = (d + 2u) % 3u;
+    if (tid < 6u) rigid[(size_t)pose * 6u + tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
+}
+
+struct RefineArgs {
+    uint32_t count, G;
+    float* stage;                  // [poses of the chunk][count][3]: the trial the force flavour evaluated; receives the next one
+    const double* slab; const double* fslab;
+    uint32_t* frozen; mdx_rf_state* st;
+    float* x0;                     // [..][count][3] the input poses (kept at evaluation 0)
+    float* y; float* row; float* rigid;      // the accepted state: coordinates [..][count][3], row [..][G], rigid [..][6]
+    mdx_rf_opts o;
+};
+
+// One evaluation of every live pose ends here: rows and forces of the 17 units added in unit order and rounded where pose_sum_kernel /
+// pose_run and pose_force_sum_kernel round them, rigid by the statement of pose_force_sum_kernel, then the stepper of mdx_refine_step.h.
+// Thread 0 takes the decisions (a few dozen fp64 operations); the sums over atoms run one component per thread, in atom order.
+__global__ __launch_bounds__(256) void pose_refine_step_kernel(RefineArgs a) {
+    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_c[3], s_I[6], s_R[9], s_m[4];
+    __shared__ float s_row[256], s_rigid[6];
+    __shared__ mdx_rf_state s_st;
+    __shared__ uint32_t s_bad, s_flags;
+    const uint32_t tid = threadIdx.x, pose = blockIdx.x, count = a.count;
+    if (a.frozen[pose] != 0u) return;      // (uniform over the workgroup, before any barrier)
+    if (tid == 0u) { s_bad = 0u; s_st = a.st[pose]; }
+    __syncthreads();
+    bool bad = false;
+    if (tid < a.G) {
+        const double* s = a.slab + (size_t)pose * (POSE_UNITS + 1u) * a.G + tid;
         double v = 0.0;
-        for (uint32_t i = 0; i < count; ++i)
-            v += tid < 3u ? s_v[i][d] : (s_x[i][d1] - s_c[d1]) * s_v[i][d2] - (s_x[i][d2] - s_c[d2]) * s_v[i][d1];
-        rigid[(size_t)pose * 6u + tid] = (float)v;
+        for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * a.G];
+        const float r = (float)v;
+        s_row[tid] = r;
+        bad = !isfinite(r);
+    }
+    const size_t at = ((size_t)pose * count + tid) * 3u;
+    if (tid < count) {
+        const double* s = a.fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
+        for (uint32_t c = 0; c < 3u; ++c) {
+            double v = 0.0;
+            for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * count * 3u + c];
+            s_v[tid][c] = v; s_x[tid][c] = (double)a.stage[at + c];
+            bad = bad || !isfinite((float)v);
+        }
+    }
+    if (bad) s_bad = 1u;      // (every writer stores the same word)
+    __syncthreads();
+    if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
+    __syncthreads();
+    if (tid < 6u) s_rigid[tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
+    if (tid >= 64u && tid < 70u) s_I[tid - 64u] = rf_inertia(&s_x[0][0], count, s_c, tid - 64u);      // (a wave of its own, beside rigid)
+    __syncthreads();
+    if (tid == 0u) {
+        bool finite = s_bad == 0u;
+        for (int k = 0; k < 6; ++k) finite = finite && isfinite(s_rigid[k]);
+        double S = 0.0;
+        for (uint32_t b = 0; b < a.G; ++b) S += (double)s_row[b];
+        if (s_st.evals == 0u) rf_start(s_st, s_c, a.o.h_start);      // (the record was zeroed: the trial is the input pose)
+        const uint32_t fl = rf_decide(s_st, a.o, S, finite, s_rigid);
+        if (fl == MDX_RF_STORE) rf_direction(s_st, count, s_rigid, s_I);
+        s_flags = fl;
+    }
+    __syncthreads();
+    const bool first = s_st.evals == 1u;
+    uint32_t fl = s_flags;
+    if (fl & MDX_RF_STORE) {
+        if (tid < count)
+            for (uint32_t c = 0; c < 3u; ++c) a.y[at + c] = a.stage[at + c];
+        if (tid < a.G) a.row[(size_t)pose * a.G + tid] = s_row[tid];
+        if (tid < 6u) a.rigid[(size_t)pose * 6u + tid] = s_rigid[tid];
+    }
+    if (first && tid < count)
+        for (uint32_t c = 0; c < 3u; ++c) a.x0[at + c] = a.stage[at + c];
+    if (fl == MDX_RF_STORE) {
+        // the largest atom speed of the new direction (a maximum: exact in any order)
+        double m = 0.0;
+        if (tid < count) {
+            const double r[3] = {s_x[tid][0] - s_c[0], s_x[tid][1] - s_c[1], s_x[tid][2] - s_c[2]};
+            m = rf_speed(s_st.v, s_st.w, r);
+        }
+#pragma unroll
+        for (int k = 32; k > 0; k >>= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
+        if ((tid & 63u) == 0u) s_m[tid >> 6] = m;
+        __syncthreads();
+        if (tid == 0u) {
+            double mm = s_m[0];
+            for (int k = 1; k < 4; ++k) mm = s_m[k] > mm ? s_m[k] : mm;
+            s_flags = fl = fl | rf_set_speed(s_st, mm);
+        }
+        __syncthreads();
+        fl = s_flags;
+    }
+    if (fl & MDX_RF_FROZEN) {
+        if (tid == 0u) { a.st[pose] = s_st; a.frozen[pose] = 1u; }
+        return;
+    }
+    if (tid == 0u) {
+        rf_trial(s_st);
+        rf_rotation(s_st.qt, s_R);
+        a.st[pose] = s_st;
+    }
+    __syncthreads();
+    if (tid < count) {
+        const float x0[3] = {a.x0[at], a.x0[at + 1u], a.x0[at + 2u]};
+        float y[3];
+        rf_coords(s_st.c0, s_st.tt, s_R, x0, y);
+        for (uint32_t c = 0; c < 3u; ++c) a.stage[at + c] = y[c];
     }
 }
 
 template <int COUL>
-static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force) {
+static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force, bool refine = false) {
     const dim3 g(POSE_UNITS + 1u, n), b(256);
-    if (force) {
+    if (refine) {
+        const size_t lds = sizeof(double) * 12u * (((a.count + 7u) >> 3) << 3);
+        if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, true, true>), g, b, lds, h->stream, a);
+        else hipLaunchKernelGGL((pose_score_kernel<COUL, false, true, true>), g, b, lds, h->stream, a);
+    } else if (force) {
         const size_t lds = sizeof(double) * 12u * (((a.count + 7u) >> 3) << 3);
         if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, true>), g, b, lds, h->stream, a);
         else hipLaunchKernelGGL((pose_score_kernel<COUL, false, true>), g, b, lds, h->stream, a);
@@ -396,10 +520,9 @@ static int pose_table(mdx_handle* h, const std::string& who, uint32_t first, uin
     return MDX_OK;
 }
 
-// mdx_score_poses (forces == nullptr: the energy flavour, rows only) and mdx_pose_forces (the force flavour; out / rigid may be null)
-static int pose_run(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, float* out,
-                    uint32_t n_groups, float* forces, float* rigid) {
-    const bool force = forces != nullptr;
+// What the three entry points share: the refusals, the intra-ligand table, the buffers of a chunk and the kernel's arguments
+static int pose_setup(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses,
+                      uint32_t n_groups, bool force, PoseArgs& a, int& mode, bool& geom) {
     const uint32_t G = h->n_grp;
     if (!G) FAIL(MDX_EPARAM, "no energy groups are set (mdx_set_energy_groups)");
     if (n_groups != G) FAIL(MDX_EPARAM, "n_groups must be the number of groups (mdx_energy_group_count)");
@@ -428,7 +551,6 @@ static int pose_run(mdx_handle* h, const std::string& who, uint32_t first, uint3
     }
     MDX_TRY(mdx_ensure_ready(h));          // what the matrix would see: list, constraints and virtual sites of the current state
     DeviceState& d = h->d;
-    hipStream_t st = h->stream;
     const uint32_t chunk = std::min(n_poses, POSE_CHUNK);
     if (h->ps_cap_stage < per_pose * chunk) {
         if (d.ps_stage) { (void)hipFree(d.ps_stage); d.ps_stage = nullptr; }
@@ -453,8 +575,8 @@ static int pose_run(mdx_handle* h, const std::string& who, uint32_t first, uint3
         if (!d.ps_rigid) HIP_TRY(hipMalloc((void**)&d.ps_rigid, sizeof(float) * (size_t)POSE_CHUNK * 6u));
         h->ps_cap_fslab = per_pose;
     }
-    PoseArgs a{};
-    int mode = 0; bool geom = false, samecut = false;
+    a = PoseArgs{};
+    bool samecut = false;
     mdx_fill_nb_params(h, a.p, &mode, &geom, &samecut);
     a.g = h->grid;
     a.posq = d.posq; a.lj = d.lj; a.orig_of = d.orig_of; a.gid = d.gid; a.grp = d.grp; a.slot_of = d.slot_of;
@@ -467,6 +589,20 @@ static int pose_run(mdx_handle* h, const std::string& who, uint32_t first, uint3
         a.inv_box[k] = h->per[k] ? 1.0f / a.box[k] : 0.f;
     }
     a.cls = d.ps_cls; a.p14 = (const Pose14*)d.ps_p14; a.n14 = h->ps_n14;
+    return MDX_OK;
+}
+
+// mdx_score_poses (forces == nullptr: the energy flavour, rows only) and mdx_pose_forces (the force flavour; out / rigid may be null)
+static int pose_run(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, float* out,
+                    uint32_t n_groups, float* forces, float* rigid) {
+    const bool force = forces != nullptr;
+    PoseArgs a{};
+    int mode = 0; bool geom = false;
+    MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, force, a, mode, geom));
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t G = h->n_grp, chunk = std::min(n_poses, POSE_CHUNK);
+    const size_t per_pose = 3 * (size_t)count;
     std::vector<double> rows((size_t)chunk * G);
     std::vector<float> res((size_t)n_poses * G), fres(force ? per_pose * n_poses : 0), rres(force ? 6u * (size_t)n_poses : 0);
     for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
@@ -518,4 +654,100 @@ extern "C" int mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, ui
     if (n_poses == 0) return MDX_OK;
     if (!poses || !forces) FAIL(MDX_EPARAM, "null argument");
     return pose_run(h, "mdx_pose_forces", first, count, n_poses, poses, rows_or_null, n_groups, forces, rigid_or_null);
+}
+
+// The refinement's own device block of a chunk of n poses: [frozen words | state records | accepted coordinates | rows | rigid |
+// input poses]; the first two are zeroed at the start of the chunk, records .. rigid come back in one copy at its end.
+struct RefineLayout {
+    size_t frozen, state, y, row, rigid, x0, end;
+    RefineLayout(uint32_t n, size_t per_pose, uint32_t G) {
+        frozen = 0;
+        state = ((sizeof(uint32_t) * n + 15u) / 16u) * 16u;
+        y = state + sizeof(mdx_rf_state) * n;
+        row = y + sizeof(float) * per_pose * n;
+        rigid = row + sizeof(float) * (size_t)G * n;
+        x0 = rigid + sizeof(float) * 6u * n;
+        end = x0 + sizeof(float) * per_pose * n;
+    }
+};
+
+extern "C" int mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses,
+                                const mdx_refine_opts* opts, float* poses_out, float* rows_out_or_null, uint32_t n_groups,
+                                float* rigid_out_or_null, float* xform_out_or_null, uint32_t* status_out_or_null,
+                                uint32_t* evals_out_or_null) {
+    const std::string who = "mdx_refine_poses";
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_poses == 0) return MDX_OK;
+    if (!poses || !poses_out || !opts) FAIL(MDX_EPARAM, "null argument");
+    if (opts->max_evals == 0 || opts->max_evals > MDX_REFINE_MAX_EVALS_CAP) FAIL(MDX_EPARAM, who + ": max_evals must be in 1..MDX_REFINE_MAX_EVALS_CAP (4096)");
+    for (float v : {opts->f_tol, opts->tau_tol, opts->h_start, opts->h_max})
+        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": a tolerance or step length is negative or not finite");
+    mdx_rf_opts o{(double)opts->f_tol, (double)opts->tau_tol, opts->h_start > 0.f ? (double)opts->h_start : 0.01,
+                  opts->h_max > 0.f ? (double)opts->h_max : 0.2};
+    if (o.h_start > o.h_max) FAIL(MDX_EPARAM, who + ": h_start exceeds h_max");
+    PoseArgs a{};
+    int mode = 0; bool geom = false;
+    MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, true, a, mode, geom));
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t G = h->n_grp;
+    const size_t per_pose = 3 * (size_t)count;
+    const size_t need = RefineLayout(POSE_CHUNK, per_pose, G).end;
+    if (h->ps_cap_refine < need) {
+        if (d.ps_refine) { (void)hipFree(d.ps_refine); d.ps_refine = nullptr; }
+        h->ps_cap_refine = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_refine, need));
+        h->ps_cap_refine = need;
+    }
+    std::vector<float> yres(per_pose * n_poses), rres((size_t)n_poses * G), gres(6u * (size_t)n_poses), xres(7u * (size_t)n_poses);
+    std::vector<uint32_t> sres(n_poses), eres(n_poses);
+    std::vector<unsigned char> back;
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
+        const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
+        const RefineLayout lay(n, per_pose, G);
+        unsigned char* blk = (unsigned char*)d.ps_refine;
+        RefineArgs r{};
+        r.count = count; r.G = G; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
+        r.frozen = (uint32_t*)(blk + lay.frozen); r.st = (mdx_rf_state*)(blk + lay.state);
+        r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
+        r.o = o;
+        a.frozen = r.frozen;
+        HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(blk, 0, lay.y, st));
+        mdx_prof_begin(h, 0);
+        for (uint32_t k = 0; k < opts->max_evals; ++k) {
+            switch (mode) {
+            case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, true, true); break;
+            case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, true, true); break;
+            case CM_RF: launch_poses<CM_RF>(h, a, geom, n, true, true); break;
+            default: launch_poses<CM_EWALD>(h, a, geom, n, true, true); break;
+            }
+            hipLaunchKernelGGL(pose_refine_step_kernel, dim3(n), dim3(256), 0, st, r);
+        }
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        back.resize(lay.x0 - lay.state);
+        HIP_TRY(hipMemcpyAsync(back.data(), blk + lay.state, back.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const unsigned char* b0 = back.data() - lay.state;
+        std::memcpy(yres.data() + per_pose * p0, b0 + lay.y, sizeof(float) * per_pose * n);
+        std::memcpy(rres.data() + (size_t)p0 * G, b0 + lay.row, sizeof(float) * (size_t)G * n);
+        std::memcpy(gres.data() + 6u * (size_t)p0, b0 + lay.rigid, sizeof(float) * 6u * n);
+        for (uint32_t k = 0; k < n; ++k) {
+            mdx_rf_state s;
+            std::memcpy(&s, b0 + lay.state + sizeof(mdx_rf_state) * k, sizeof(s));
+            sres[p0 + k] = s.frozen ? s.status : MDX_REFINE_MAX_EVALS;
+            eres[p0 + k] = s.evals;
+            float* x = xres.data() + 7u * (size_t)(p0 + k);
+            for (int c = 0; c < 4; ++c) x[c] = (float)s.q[c];
+            for (int c = 0; c < 3; ++c) x[4 + c] = (float)s.t[c];
+        }
+    }
+    std::memcpy(poses_out, yres.data(), sizeof(float) * yres.size());
+    if (rows_out_or_null) std::memcpy(rows_out_or_null, rres.data(), sizeof(float) * rres.size());
+    if (rigid_out_or_null) std::memcpy(rigid_out_or_null, gres.data(), sizeof(float) * gres.size());
+    if (xform_out_or_null) std::memcpy(xform_out_or_null, xres.data(), sizeof(float) * xres.size());
+    if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
+    if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
+    return MDX_OK;
 }

@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from ._abi import (CCommDiag, CHBond, CConfig, CEnergies, CStats, CSystem, FORCE, MDX_EDEVICE, MDX_ENAN, MDX_EOOM,
+from ._abi import (CCommDiag, CHBond, CConfig, CEnergies, CRefineOpts, CStats, CSystem, FORCE, MDX_EDEVICE, MDX_ENAN, MDX_EOOM,
                    MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, VEL, MdConfig, MdSystem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -169,6 +169,8 @@ def load_library():
     lib.mdx_snapshot_read_foreign.argtypes = [H, C.c_uint32, C.c_void_p, C.c_uint32]
     lib.mdx_score_poses.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, C.c_uint32]
     lib.mdx_pose_forces.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, C.c_uint32, _fp, _fp]
+    lib.mdx_refine_poses.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, C.POINTER(CRefineOpts), _fp, _fp, C.c_uint32, _fp, _fp,
+                                     _u32p, _u32p]
     _lib = lib
     return lib
 
@@ -312,6 +314,36 @@ class MdState:
         if t is not None:
             out += (t,)
         return out
+
+    def refine_poses(self, first: int, poses, max_evals: int, f_tol: float, tau_tol: float, h_start: float = 0.0, h_max: float = 0.0):
+        """`mdx_refine_poses`: a rigid-body steepest descent of each of P placements of the atoms [first, first + count) on the
+        device, every pose with its own adaptive step length (include/mdx.h states the stepper).  poses: float32 [P, count, 3] A,
+        each a whole molecule; f_tol kcal/mol/A and tau_tol kcal/mol bound |net force| and |torque| of a converged pose; h_start /
+        h_max = 0 select 0.01 / 0.2 A.
+        -> (poses_out [P, count, 3] f32, rows [P, n_groups] f32 - the bits of score_poses(poses_out) -, rigid [P, 6] f32, xform [P, 7]
+        f32: quaternion (w, x, y, z) and translation, status [P] u32 (REFINE_CONVERGED / MAX_EVALS / STALLED / NONFINITE), evals [P]
+        u32), all of the accepted state.  The handle is left as it is."""
+        if not isinstance(poses, np.ndarray) or poses.dtype != np.float32:
+            raise ParamError("refine_poses: poses must be a float32 ndarray [P, count, 3]")
+        if poses.ndim != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= POSE_MAX_ATOMS:
+            raise ParamError(f"refine_poses: poses must have shape [P, count, 3] with 1 <= count <= {POSE_MAX_ATOMS}, got {poses.shape}")
+        if int(first) < 0 or int(first) + poses.shape[1] > self.n_atoms:
+            raise ParamError("refine_poses: atom range out of bounds")
+        lib = load_library()
+        a = np.ascontiguousarray(poses)
+        n = int(lib.mdx_energy_group_count(self._h))
+        P = a.shape[0]
+        opts = CRefineOpts(int(max_evals), float(f_tol), float(tau_tol), float(h_start), float(h_max))
+        y = np.zeros(a.shape, dtype=np.float32)
+        r = np.zeros((P, max(n, 1)), dtype=np.float32)
+        t = np.zeros((P, 6), dtype=np.float32)
+        x = np.zeros((P, 7), dtype=np.float32)
+        st = np.zeros(P, dtype=np.uint32)
+        ev = np.zeros(P, dtype=np.uint32)
+        _check(lib.mdx_refine_poses(self._h, int(first), a.shape[1], P, a.ctypes.data_as(_fp), C.byref(opts), y.ctypes.data_as(_fp),
+                                    r.ctypes.data_as(_fp), n, t.ctypes.data_as(_fp), x.ctypes.data_as(_fp), st.ctypes.data_as(_u32p),
+                                    ev.ctypes.data_as(_u32p)))
+        return y, (r[:, :n] if n else r[:, :0]), t, x, st, ev
 
     # -- position restraints (include/mdx.h: E = k max(0, |x - r0| - b)^2) ------------------------------------------------
     def set_position_restraints(self, idx, ref=None, k=1.0, flat_bottom=None):
