@@ -146,7 +146,7 @@ static void free_device(mdx_handle* h) {
                     d.tile_col, d.scan_tmp, d.cl_lo, d.cl_hi, d.cl_kind, d.list_counts, d.entry_cnt, d.entry_off,
                     d.mchunk_cnt, d.mchunk_off, d.entries, d.entries_in, d.inner_nch, d.list_cursors, d.masks, d.role_off_o, d.role_rec_o, d.role_cnt_s,
                     d.role_off_s, d.role_rec_s, d.role_prm, d.ctl, d.energy,
-                    d.flags_dev, d.bbox_red, d.pair_count, d.inner_count, d.pme_force, d.wstep_s, d.path, d.dprune, d.force_b, d.force_c, d.cons_o, d.cons_s, d.cons_tmp, d.cons_mask, d.cons_cnt, d.cons_off, d.cons_vir, d.vsite_o, d.vsite_s, d.gsite_o, d.gsite_s, d.gsite_tmp, d.pme_q, d.pme_f,
+                    d.flags_dev, d.bonded_part, d.bbox_red, d.pair_count, d.inner_count, d.pme_force, d.wstep_s, d.path, d.dprune, d.force_b, d.force_c, d.cons_o, d.cons_s, d.cons_tmp, d.cons_mask, d.cons_cnt, d.cons_off, d.cons_vir, d.vsite_o, d.vsite_s, d.gsite_o, d.gsite_s, d.gsite_tmp, d.pme_q, d.pme_f,
                     d.pme_theta, d.pme_q2, d.pme_f2, d.scratch4, d.tile_bnd, d.tile_scan, d.tile_order, d.tile_lpt, d.rb_ctl, d.scan_chain, d.grp, d.grp_mat, d.fl_hot, d.fl_slab, d.star_o, d.star_s, d.ewald_tab,
                     d.ps_cls, d.ps_p14, d.ps_stage, d.ps_slab, d.ps_rows, d.ps_fslab, d.ps_fout, d.ps_rigid, d.ps_refine};
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -844,14 +844,16 @@ extern "C" int mdx_step(mdx_handle* h, float dt, const float* ext_forces, uint32
             MDX_TRY(frc);
             if (vv && !fused) {
                 MDX_TRY(mdx_launch_integrate(h, 2, dt, &d.ctl->disp2[s + 1], nullptr, thr));
-                MDX_TRY(mdx_launch_constrain_velocities(h, &d.ctl->disp2[s + 1], thr));
+                if (dt != 0.f) MDX_TRY(mdx_launch_constrain_velocities(h, &d.ctl->disp2[s + 1], thr));
             }
         }
         h->prof_tag = (int)chunk;
         if (fused) {
             // (one launch per step, no energy step at the end: the last launch passes its own gate - or a kick beyond its grant - on in the next word)
             MDX_TRY(mdx_launch_integrate(h, 2, dt, &d.ctl->disp2[(onepass && !want_e) ? chunk + 1 : chunk], nullptr, thr));
-            MDX_TRY(mdx_launch_constrain_velocities(h, &d.ctl->disp2[chunk], thr));     // (no-op without constraints)
+            // (no-op without constraints; a step of zero length kicked by nothing: the velocities are the ones the last projection left, and
+            // projecting them again would move their last bits)
+            if (dt != 0.f) MDX_TRY(mdx_launch_constrain_velocities(h, &d.ctl->disp2[chunk], thr));
         }
         h->prof_tag = -1;
         if (h->dd) { h->chunk_s = -1; mdx_dd_pipe_chunk_end(h); }
@@ -924,7 +926,7 @@ extern "C" int mdx_step(mdx_handle* h, float dt, const float* ext_forces, uint32
                 MDX_TRY(frc);
                 if (vv) {
                     MDX_TRY(mdx_launch_integrate(h, 2, dt, nullptr, nullptr, thr));
-                    MDX_TRY(mdx_launch_constrain_velocities(h, nullptr, 0));
+                    if (dt != 0.f) MDX_TRY(mdx_launch_constrain_velocities(h, nullptr, 0));
                 }
                 done = s + 1;
                 break;

@@ -22,6 +22,7 @@ struct BondedArgs {
     uint32_t S;
     const uint32_t* role_off; const RoleRec* roles; const float4* prm;
     const float4* posq; float4* force; double* energy;
+    double* part; uint32_t* done;      // energy flavour: [gridDim.x][9] per-block sums, blocks finished
     BondedParams p;
     const uint32_t* gate; uint32_t thr_bits;
 };
@@ -77,10 +78,34 @@ __global__ __launch_bounds__(256) void bonded_gather_kernel(BondedArgs a) {
             if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6][q] = t;
         }
         __syncthreads();
+        // The blocks' sums are added in an order that does not depend on which block finishes first: every block leaves its sums in
+        // `part`, the last one to finish adds them all - lane t the blocks t, t + 256, ..., then the same shuffle and LDS steps - and
+        // makes ONE addition per term.  (One atomic per term and block in order of arrival gave two energy() calls on an untouched
+        // handle bond / angle / dihedral energies that differed in the last bit.)
+        if (threadIdx.x < NV)
+            a.part[(size_t)blockIdx.x * 9 + threadIdx.x] = s_e[0][threadIdx.x] + s_e[1][threadIdx.x] + s_e[2][threadIdx.x] + s_e[3][threadIdx.x];
+        __threadfence();
+        __syncthreads();
+        __shared__ uint32_t s_last;
+        if (threadIdx.x == 0) s_last = atomicAdd(a.done, 1u) == gridDim.x - 1 ? 1u : 0u;
+        __syncthreads();
+        if (!s_last) return;
+        __threadfence();
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            double t = 0.0;
+            for (uint32_t b = threadIdx.x; b < gridDim.x; b += blockDim.x)
+                t += __hip_atomic_load(&a.part[(size_t)b * 9 + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) t += __shfl_xor(t, m);
+            if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6][q] = t;
+        }
+        __syncthreads();
         if (threadIdx.x < NV) {
             const double t = s_e[0][threadIdx.x] + s_e[1][threadIdx.x] + s_e[2][threadIdx.x] + s_e[3][threadIdx.x];
             if (t != 0.0) atomicAdd(&a.energy[slot[threadIdx.x]], t);
         }
+        if (threadIdx.x == 0) *a.done = 0u;      // ready for the next launch
     }
 }
 
@@ -125,13 +150,26 @@ int mdx_launch_bonded(mdx_handle* h, bool energy, const uint32_t* d_gate, uint32
     a.S = h->S; a.role_off = h->d.role_off_s; a.roles = h->d.role_rec_s; a.prm = h->d.role_prm;
     a.posq = h->d.posq; a.force = h->d.force; a.energy = h->d.energy; a.gate = d_gate; a.thr_bits = thr_bits;
     mdx_fill_bonded_params(h, a.p);
-    mdx_prof_begin(h, energy ? 3 : 1);
     // lanes per atom by the mean role count of the slots (MDX_BONDED_LPA=2|4 forces it for A/B)
     static const int lpa_env = [] { const char* e = std::getenv("MDX_BONDED_LPA"); return e ? std::atoi(e) : 0; }();
     // (n_roles counts the whole system: a decomposed handle holds n_local of its N atoms, and only the owned ones carry roles)
     const double roles_here = (double)h->n_roles * ((h->n_local != h->N && h->N) ? (double)h->n_local / (double)h->N : 1.0);
     const int lpa = (lpa_env == 1 || lpa_env == 2 || lpa_env == 4) ? lpa_env : (roles_here < 2.6 * (double)h->S ? 1 : (roles_here < 6.0 * (double)h->S ? 2 : 4));
     const dim3 g((uint32_t)(((size_t)h->S * lpa + 255) / 256)), b(256);
+    if (energy) {      // per-block sums of the energy flavour + (behind them, 8-byte aligned) the count of finished blocks, which a launch leaves at zero
+        const size_t need = (size_t)g.x * 9 + 1;
+        if (need > h->d.cap_bonded_part) {
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (h->d.bonded_part) { (void)hipFree(h->d.bonded_part); h->d.bonded_part = nullptr; h->d.cap_bonded_part = 0; }
+            const size_t cap = need + need / 4;
+            HIP_TRY(hipMalloc((void**)&h->d.bonded_part, sizeof(double) * cap));
+            HIP_TRY(hipMemsetAsync(h->d.bonded_part, 0, sizeof(double) * cap, h->stream));
+            h->d.cap_bonded_part = cap;
+        }
+        a.part = h->d.bonded_part;
+        a.done = reinterpret_cast<uint32_t*>(h->d.bonded_part + h->d.cap_bonded_part - 1);
+    }
+    mdx_prof_begin(h, energy ? 3 : 1);
     if (h->n_posre) {      // restrained handle: the flavours with the ROLE_POSRE branch
         if (lpa == 1) {
             if (energy) hipLaunchKernelGGL((bonded_gather_kernel<true, 1, true>), g, b, 0, h->stream, a);

@@ -1005,7 +1005,7 @@ __global__ __launch_bounds__(128) void water_step_kernel(uint32_t n_groups, cons
             float wc = 0.f;
             bool settled = false;
             const Triangle tri = rigid_triangle(cg, im);
-            if (p.settle && tri.ok && settle_positions(xo, xn, im, tri)) {
+            if (p.settle && dt != 0.f && tri.ok && settle_positions(xo, xn, im, tri)) {      // (dt = 0: nothing drifted - constrain_positions_kernel's rule)
                 settled = true;
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
@@ -1035,8 +1035,8 @@ __global__ __launch_bounds__(128) void water_step_kernel(uint32_t n_groups, cons
                     if (done) break;
                 }
             }
-            const float idt = 1.0f / dt;
-            if (cons_vir) cons_vir[g] = p.vir_scale * wc * idt * idt;
+            const float idt = dt != 0.f ? 1.0f / dt : 0.f;
+            if (cons_vir && dt != 0.f) cons_vir[g] = p.vir_scale * wc * idt * idt;      // (a dt = 0 step keeps the last step's virial, as the separate launches do)
             float4 p0n = pk[0];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {

@@ -262,6 +262,7 @@ struct DeviceState {
     double*  energy = nullptr;     // [EN_COUNT + 8 + MDX_ESTRIDE*MDX_EPART]: energies, max|F|^2 bits, momentum (px,py,pz,mass),
                                    // then MDX_EPART x {lj, coulomb, virial, -} partial sums of the pair kernel
     uint32_t* flags_dev = nullptr; // misc error flags
+    double*  bonded_part = nullptr; size_t cap_bonded_part = 0;   // [blocks x 9] per-block sums of the bonded energy flavour, + its count of finished blocks behind them
     unsigned long long* pair_count = nullptr;  // cluster pairs in the list (statistics)
     unsigned long long* inner_count = nullptr; // [MDX_EPART + 1] dual list: kept cluster pairs per pruning pass (spread), passes
     float*   bbox_red = nullptr;   // [6] min/max reduction (vacuum grid)

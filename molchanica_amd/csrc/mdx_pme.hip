@@ -1334,7 +1334,8 @@ int mdx_pme_setup(mdx_handle* h) {
         if (p->have_xpass) { p->destroy(p->fwd2); p->destroy(p->inv2); p->have_xpass = false; }
         if (p->tw) { (void)hipFree(p->tw); p->tw = nullptr; }
     if (p->phi) { (void)hipFree(p->phi); p->phi = nullptr; }
-        static const bool xpass_env = [] { const char* e = std::getenv("MDX_PME_XPASS"); return !(e && e[0] == '0'); }();
+        const char* const xe = std::getenv("MDX_PME_XPASS");      // read whenever a handle lays its mesh out (not on the step path): a test can choose per handle
+        const bool xpass_env = !(xe && xe[0] == '0');
         if (xpass_env && pitch != K3h && pitch % XP_TK == 0 && K[0] <= 512) {
             int n2[2] = {K[1], K[2]}, re2[2] = {K[1], K[2]}, cx2[2] = {K[1], pitch};
             if (p->plan_many(&p->fwd2, 2, n2, re2, 1, K[1] * K[2], cx2, 1, K[1] * pitch, HIPFFT_R2C, K[0]) == HIPFFT_SUCCESS) {

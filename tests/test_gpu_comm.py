@@ -366,6 +366,85 @@ def _spme_decomposed_body(s, cfg, world, slab):
         assert 0 < pme["mesh_bytes_sent"] + pme["transpose_bytes_sent"] < 2 * pme["replicated_mesh_bytes"]
 
 
+@pytest.mark.parametrize("world", [2, 4])
+def test_decomposed_orthorhombic_cell_off_origin(orc, world):
+    """Every other system of this file is a cube at the origin.  mdx_decomp.hip reads `box_lo` at 23 places (domain faces, owners,
+    image shifts of the ghosts): 2,300 waters in a 90 x 44 x 21 A cell at PAD (tests/cell_cases.py) on 2 and 4 ranks - the start
+    forces against the fp64 oracle and against one GPU, 10 steps against one GPU.  (The edges of tests/test_gpu_edge_geometry.py's
+    orthorhombic case in another order: 2 ranks cut x and 4 ranks x and y, whatever the cell, and a cut edge must hold a brick and two
+    halos - 21 x 44 x 90 is refused with "brick + 2 halo exceeds the box".)"""
+    from molchanica_amd.md_state import MdState
+    from tests.cell_cases import PAD, cell_of, force_ratios, placed, record
+    from tests.test_gpu_edge_geometry import _waters_in_cell
+    from tests.test_gpu_parity import assert_forces
+    s = placed(_waters_in_cell(2300, (90.0, 44.0, 21.0), seed=13), PAD)
+    cfg = MdConfig(lj_cutoff=8.0, coulomb_cutoff=8.0, skin=1.5, coulomb_mode=1, chunk_steps=8)      # (2 (rc + skin) = 19 < 21)
+    with MdState(s, cfg) as md:
+        lo, L = cell_of(md)
+        pos0 = md.positions()
+        e_ref = md.energy()
+        f_ref = md.forces().astype(np.float64)
+        md.step(0.0005, None, 10)
+        p_ref = md.positions().astype(np.float64)
+    res = run_ranks(s, cfg, world, 10, want_forces=True)
+    r0 = res[0]
+    assert tuple(r0["info"]["grid"]) == ((2, 1, 1) if world == 2 else (2, 2, 1))
+    fo, _ = orc.forces(s, cfg, pos=pos0.astype(np.float64), use_cells=False)
+    slack = orc.cutoff_slack(s, cfg, pos=pos0)
+    df = np.linalg.norm(r0["f0"].astype(np.float64) - f_ref, axis=1)
+    r_atom, r_rms = force_ratios(r0["f0"], fo, slack)
+    dev = rms_dev(r0["pos"], p_ref, L)
+    record(f"decomposed, world {world}, grid {r0['info']['grid']}", force_atom_vs_oracle=r_atom, force_rms_vs_oracle=r_rms,
+           force_vs_one_gpu=float((df / (2e-4 * np.maximum(np.linalg.norm(f_ref, axis=1), 1.0) + 2e-4)).max()), rms_over_2e3=dev / 2e-3)
+    assert_forces(r0["f0"], fo, slack, f"world {world}")
+    assert (df <= 2e-4 * np.maximum(np.linalg.norm(f_ref, axis=1), 1.0) + 2e-4).all()
+    for k in ("lj", "coulomb", "bond", "angle", "kinetic", "virial"):
+        assert abs(r0["e0"][k] - e_ref[k]) <= max(2e-2, 3e-6 * abs(e_ref[k])), (k, r0["e0"][k], e_ref[k])
+    assert dev < 2e-3
+    assert sum(res[r]["stats"]["n_owned"] for r in range(world)) == s.n_atoms
+    assert all(res[r]["stats"]["n_ghost"] > 0 for r in range(world))
+    for r in range(1, world):
+        assert np.array_equal(res[r]["pos"], r0["pos"]), "ranks disagree on the gathered global state"
+
+
+def test_slab_spme_in_an_orthorhombic_cell_off_origin():
+    """The slab-decomposed mesh (x-slabs, one per rank; K0 and K1 even) of the same cell on 2 ranks: `coulomb_recip` and the forces
+    against one GPU (the bounds of _spme_decomposed_body) and against the numpy restatement (those of tests/test_gpu_pme.py)."""
+    from molchanica_amd import _abi
+    from molchanica_amd.md_state import MdState
+    from oracle import pme_ref as P
+    from tests.cell_cases import PAD, approx_ratio, cell_of, placed, record
+    from tests.test_gpu_edge_geometry import _waters_in_cell
+    from tests.test_gpu_pme import excluded_pairs, rel_rms
+    s = placed(_waters_in_cell(2300, (90.0, 44.0, 21.0), seed=13), PAD)
+    beta, grid = 0.40, (90, 48, 24)
+    base = dict(lj_cutoff=8.0, coulomb_cutoff=8.0, skin=1.5, chunk_steps=8, coulomb_mode=2, ewald_alpha=beta)
+    cfg = MdConfig(overrides=0, pme_grid=grid, **base)
+    with MdState(s, MdConfig(overrides=_abi.OVR_LONG_RANGE_RECIP_DISABLED, **base)) as md:
+        pos = md.positions()
+        lo, L = cell_of(md)
+        f_real = md.forces().astype(np.float64)
+    with MdState(s, cfg) as md:
+        assert np.array_equal(md.positions(), pos)
+        e_ref, f_ref = md.energy(), md.forces().astype(np.float64)
+    res = run_ranks(s, cfg, 2, 4, want_forces=True)
+    r0 = res[0]
+    assert r0["info"]["pme"]["slab_on"] and max(r0["info"]["grid"]) == 2
+    for k in ("coulomb", "coulomb_recip", "lj", "bond", "angle", "virial"):
+        assert abs(r0["e0"][k] - e_ref[k]) <= max(5e-2, 1e-5 * abs(e_ref[k])), (k, r0["e0"][k], e_ref[k])
+    df = np.linalg.norm(r0["f0"].astype(np.float64) - f_ref, axis=1)
+    q = s.charge.astype(np.float64)
+    e_np, f_np = P.spme_recip(pos.astype(np.float64), q, lo, L, beta, grid, 4)
+    e_x, f_x = P.excluded_pair_correction(pos.astype(np.float64), q, excluded_pairs(s), L, beta)
+    e_np += e_x + P.ewald_self_energy(q, beta) + P.ewald_background_energy(q, L, beta)
+    err = rel_rms(r0["f0"].astype(np.float64) - f_real, f_np + f_x)
+    record("slab SPME, world 2", force_vs_one_gpu=float((df / (3e-4 * np.maximum(np.linalg.norm(f_ref, axis=1), 1.0) + 3e-4)).max()),
+           force_rms_vs_numpy=err / 2e-4, energy_vs_numpy=approx_ratio(r0["e0"]["coulomb_recip"], e_np, 2e-5, 5e-2))
+    assert (df <= 3e-4 * np.maximum(np.linalg.norm(f_ref, axis=1), 1.0) + 3e-4).all(), float(df.max())
+    assert err < 2e-4, err
+    assert r0["e0"]["coulomb_recip"] == pytest.approx(e_np, rel=2e-5, abs=5e-2)
+
+
 @pytest.mark.parametrize("kind", [1, 2])
 def test_other_integrators_on_decomposed_handles(kind):
     """Leapfrog and Langevin middle (src/ui/panels/md.rs:296-305) on 4 ranks: the Langevin noise is keyed by

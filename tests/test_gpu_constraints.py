@@ -24,7 +24,7 @@ def mdx():
 def bond_errors(s, x):
     b = s.constraint_idx.astype(int)
     d = x[b[:, 0]] - x[b[:, 1]]
-    L = np.array(s.box_hi, dtype=np.float64)
+    L = np.array(s.box_hi, dtype=np.float64) - np.array(s.box_lo, dtype=np.float64)
     d -= np.round(d / L) * L
     return np.abs(np.linalg.norm(d, axis=1) - s.constraint_len) / s.constraint_len
 
@@ -107,6 +107,28 @@ def test_rigid_waters_straddling_box_faces(mdx, orc, model):
     rms = math.sqrt((d ** 2).sum(1).mean())
     assert rms < 2e-3, f"trajectory deviates from the oracle: {rms:.2e} A"
     assert abs(e1["potential"] + e1["kinetic"] - t0) < 0.02 * e["kinetic"], "energy not conserved over 60 steps of NVE"
+
+
+@pytest.mark.parametrize("model", ["tip3p_rigid", "opc"])
+def test_steps_of_zero_length_on_rigid_water_move_nothing(mdx, model):
+    """`mdx_step` refuses only a non-finite dt.  water_step_kernel divided by dt unconditionally: 0 * inf = NaN in every velocity and
+    in the constraint virial (the two older kernels have always guarded it).  A step of zero length kicks by nothing, drifts by nothing
+    and has nothing for SETTLE to correct: the state comes back bit for bit."""
+    s = systems.water_box(6, seed=7, rigid=True) if model == "tip3p_rigid" else systems.opc_water_box(6, seed=7)
+    cfg = MdConfig(lj_cutoff=8.0, coulomb_cutoff=8.0, skin=1.0, coulomb_mode=1)
+    with mdx.MdState(s, cfg) as md:
+        md.step(0.002, None, 10)
+        x0, v0 = md.positions(), md.velocities()
+        n0 = md.pair_launch_info()["water_step_launches"]
+        md.step(0.0, None, 3)
+        x1, v1 = md.positions(), md.velocities()
+        if os.environ.get("MDX_WATER_STEP", "1") != "0":
+            assert md.pair_launch_info()["water_step_launches"] >= n0 + 3, "the one-pass kernel is the one under test"
+        e = md.energy()
+    assert np.isfinite(x1).all() and np.isfinite(v1).all()
+    assert np.isfinite(e["virial"]) and np.isfinite(e["kinetic"]) and np.isfinite(e["pressure"])
+    assert np.array_equal(x1, x0), float(np.abs(x1 - x0).max())
+    assert np.array_equal(v1, v0), float(np.abs(v1 - v0).max())
 
 
 def test_opc_box_conserves_energy_after_equilibration(mdx):

@@ -51,15 +51,27 @@ CASES = {
 }
 
 
+def case_system(name):
+    nw, box, rc, skin = CASES[name]
+    return _waters_in_cell(nw, box, seed=len(name)), rc, skin
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_single_point_and_step_loop(mdx, orc, name):
-    nw, box, rc, skin = CASES[name]
-    s = _waters_in_cell(nw, box, seed=len(name))
+    s, rc, skin = case_system(name)
+    single_point_and_step_loop(mdx, orc, s, rc, skin, name)
+
+
+def single_point_and_step_loop(mdx, orc, s, rc, skin, name):
+    """The body of the test above as a function of the system (tests/test_gpu_cell_placement.py runs it in cells off the origin)."""
+    from tests.cell_cases import energy_ratio, force_ratios, record
     cfg = MdConfig(lj_cutoff=rc, coulomb_cutoff=rc, skin=skin, coulomb_mode=1)
     with mdx.MdState(s, cfg) as md:
         pos = md.positions()
         f, e = md.forces(), md.energy()
         fo, eo = orc.forces(s, cfg, pos=pos.astype(np.float64), use_cells=False)
+        r_atom, r_rms = force_ratios(f, fo, orc.cutoff_slack(s, cfg, pos=pos))
+        record(f"edge geometry [{name}] single point", force_atom=r_atom, force_rms=r_rms, energy=energy_ratio(e, eo))
         assert_forces(f, fo, orc.cutoff_slack(s, cfg, pos=pos), name)
         assert_energies(e, eo, name)
         # neighbour list of this geometry, bit for bit (brute-force oracle)
@@ -75,6 +87,7 @@ def test_single_point_and_step_loop(mdx, orc, name):
         md.energy()
         f_plain = md.forces().astype(np.float64)
         scale = 1e-4 * np.maximum(np.linalg.norm(f_plain, axis=1), 1.0) + 1e-5 * math.sqrt((f_plain ** 2).sum(1).mean())
+        record(f"edge geometry [{name}] loop forces vs fresh", ratio=float((np.linalg.norm(f_loop - f_plain, axis=1) / scale).max()))
         assert (np.linalg.norm(f_loop - f_plain, axis=1) <= scale).all(), name
         assert md.stats()["rebuild_count"] >= 2
         # Against the oracle at the SAME fp32 coordinates: between rebuilds an atom that left the cell is kept unwrapped
@@ -84,6 +97,8 @@ def test_single_point_and_step_loop(mdx, orc, name):
         pos2 = md.positions()
         md.energy()
         fo2, _ = orc.forces(s, cfg, pos=pos2.astype(np.float64), use_cells=False)
+        r_atom, r_rms = force_ratios(md.forces(), fo2, orc.cutoff_slack(s, cfg, pos=pos2))
+        record(f"edge geometry [{name}] after 60 steps", force_atom=r_atom, force_rms=r_rms)
         assert_forces(md.forces(), fo2, orc.cutoff_slack(s, cfg, pos=pos2), name + " after 60 steps")
 
 
