@@ -327,6 +327,13 @@ int mdx_get_stats(mdx_handle* h, mdx_stats* out);
  * tiles in that launch.  The parity tests use it to name the body they hold against the oracle; no call
  * of the reference corresponds to it. */
 int mdx_pair_launch_info(const mdx_handle* h, uint32_t out[24]);
+/* Diagnostics: the constant-sigma^2 body of the pair kernel.  A handle in which every atom with a Lennard-Jones well carries the same
+ * sigma (one LJ atom type: a water box, rigid OPC; Lorentz-Berthelot rule, no alchemical window) is eligible: its force-only pair launches
+ * multiply by the one f32 value sigma_ij^2 can take instead of adding and squaring per pair - the same bits, two vector instructions
+ * fewer per cluster pair.  out[0]: the handle is eligible (MDX_UNI_LJ=0 in the environment: never), out[1]: the last pair launch of the
+ * step loop ran such a body, out[2]: the last pair launch of any kind did, out[3]: the bits of that f32 value (0 when not eligible).
+ * No call of the reference corresponds to it. */
+int mdx_pair_body_info(const mdx_handle* h, uint32_t out[4]);
 /* The Verlet skin in force, and whether the library is still tuning it (mdx_config.skin == 0). */
 int mdx_get_skin(const mdx_handle* h, float* skin, int* tuning);
 

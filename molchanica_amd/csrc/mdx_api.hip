@@ -237,6 +237,7 @@ static int create_impl(const mdx_system* s, const mdx_config* c, int device, mdx
         const char* const e = std::getenv("MDX_KIND_CLUSTERS");
         h->kind_split = e ? e[0] != '0' : (n_lj_only >= N / 20u && n_q_only >= N / 20u && N >= 200000u);      // (23 k sites: 6780 steps/s without, 6650 with)
     }
+    mdx_refresh_uni_lj(h);      // one LJ atom type (a water box, rigid OPC): the pair launches take the constant-sigma^2 bodies
     h->mol_start.assign(s->mol_start ? s->mol_start : nullptr, s->mol_start ? s->mol_start + s->n_mols : nullptr);
     h->total_charge = 0.0; h->sum_q2 = 0.0;
     h->q_abs_max = 0.0;
@@ -1487,6 +1488,13 @@ extern "C" int mdx_pair_launch_info(const mdx_handle* h, uint32_t out[24]) {
     for (int k = 0; k < 8; ++k) { out[k] = h->pair_info_step[k]; out[8 + k] = h->pair_info_any[k]; }
     out[16] = h->inner_rebuilds; out[17] = h->inner_from_rebuild ? 1u : 0u; out[18] = h->water_step_launches; out[19] = h->water_step_mixed_launches;
     out[20] = (uint32_t)h->onepass_launches; out[21] = (uint32_t)h->onepass_violations; out[22] = h->pair_info_tail[0]; out[23] = h->pair_info_tail[1];
+    return MDX_OK;
+}
+
+extern "C" int mdx_pair_body_info(const mdx_handle* h, uint32_t out[4]) {
+    if (!h || !out) FAIL(MDX_EPARAM, "null argument");
+    out[0] = h->uni_lj ? 1u : 0u; out[1] = h->pair_body_step; out[2] = h->pair_body_any;
+    std::memcpy(&out[3], &h->uni_c, 4);
     return MDX_OK;
 }
 

@@ -60,6 +60,33 @@ __attribute__((target("avx2"))) static uint64_t fp_mix_avx2(uint64_t h, const vo
     return fp_mix_scalar(x, b + k, bytes - k);      // (the tail, and the final avalanche)
 }
 #endif
+// One Lennard-Jones atom type?  lj = the per-atom records (sigma / 2, sqrt(24 eps)) as [n][2] floats (mdx_api.hip create_impl).  True iff
+// at least one atom has a well (record .y != 0; an alchemical window's sign flag on a well-free atom, -0.0, is no well) and every atom
+// that has one carries bit for bit the same sigma / 2 = h.  Then sigma_ij^2 of every pair whose LJ term is not multiplied by 0 is the
+// one f32 value *c_out = fl(fl(h + h) * fl(h + h)) - computed here the way the pair kernel computes it, an add and a multiply in f32 -
+// and the pair kernel's constant-sigma^2 body (pair_eval<..., UNI>) gives the bits of the general one.  Atoms without a well may carry
+// any sigma.  Never under the geometric rule (sigma_ij is a product there) and never under an alchemical window (the soft core needs
+// sigma_ij of the pair).
+bool mdx_uniform_lj(const float* lj, size_t n, bool geometric, bool alch_on, float* c_out) {
+    if (c_out) *c_out = 0.f;
+    if (!lj || geometric || alch_on) return false;
+    bool have = false;
+    uint32_t hbits = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (lj[2 * i + 1] == 0.f) continue;
+        uint32_t b; std::memcpy(&b, &lj[2 * i], 4);
+        if (!have) { have = true; hbits = b; }
+        else if (b != hbits) return false;
+    }
+    if (!have) return false;
+    float h; std::memcpy(&h, &hbits, 4);
+    volatile float sig = h + h;      // (volatile: the sum is rounded to f32 before it is squared, whatever the host's evaluation method)
+    const float s = sig;
+    volatile float c = s * s;
+    if (c_out) *c_out = c;
+    return true;
+}
+
 uint64_t mdx_fp_mix(uint64_t h, const void* p, size_t bytes) {
     if (!p) return (h ^ 0x9E3779B97F4A7C15ull) * 0xBF58476D1CE4E5B9ull;
 #ifdef MDX_HOST_X86

@@ -91,6 +91,7 @@ struct NbParams {
     // (mdx_pair_dev.h: EWALD_TAB_*): F/r = q q (1/r^3 - g) without v_exp / v_rcp in the pair loop.  null: the closed form.
     const float4* etab; uint32_t etab_n;
     float etab_scale; uint32_t etab_shift;      // x = r^2 * etab_scale + EWALD_TAB_C; index = (bits(x) >> etab_shift) - (bits(EWALD_TAB_C) >> etab_shift)
+    float uni_c;             // one LJ atom type (mdx_uniform_lj): sigma_ij^2 of every pair with a well, what the UNI bodies multiply by; else 0
 };
 
 struct BondedParams {
@@ -440,6 +441,10 @@ struct mdx_handle {
     uint32_t tail_w = 0, tail_tiles = 0;      // units per closing tile (0: none), closing tiles per XCD range
     uint32_t pair_info_tail[2] = {};          // ... of the last dual-list launch of the step loop: units per tail tile, tail tiles in the launch
     uint32_t pair_info_step[8] = {}, pair_info_any[8] = {};   // the pair-kernel instantiation last launched by the step loop over the dual list / by anything else (mdx_pair_launch_info)
+    // one LJ atom type (mdx_refresh_uni_lj: at create and wherever the LJ records or the alchemical state change): the pair launches that
+    // have a constant-sigma^2 body (pair_eval<..., UNI>, launch_variant) send it out.  mdx_pair_body_info reads the three words.
+    bool uni_lj = false; float uni_c = 0.f;
+    uint32_t pair_body_step = 0, pair_body_any = 0;      // the last pair launch of the step loop / of any kind ran a UNI body
     bool bonded_deferred = false; // step loop, large classes: the NEXT step's fused bonded + kick + drift pass evaluates the bonded terms of this force call
     uint64_t rng_state = 0;
     bool zero_com = false;
@@ -618,6 +623,18 @@ static inline void mdx_tail_plan(const mdx_handle* h, uint32_t T, uint32_t* w_ou
     const uint32_t tiles = den == 1u ? group : group / den;
     if (!tiles) return;
     *w_out = w; *tiles_out = tiles;
+}
+
+// One LJ atom type (mdx_hostutil.cpp): does every atom with a well carry the same sigma / 2, and if so, sigma_ij^2 as the device rounds it.
+bool mdx_uniform_lj(const float* lj, size_t n, bool geometric, bool alch_on, float* c_out);
+// ... decided for a handle from h_lj, the combining rule and the alchemical state.  MDX_UNI_LJ=0: never (the parent's launches,
+// instantiation for instantiation; read once per process).
+static inline void mdx_refresh_uni_lj(mdx_handle* h) {
+    static const bool off = [] { const char* e = std::getenv("MDX_UNI_LJ"); return e && e[0] == '0'; }();
+    float c = 0.f;
+    const bool ok = !off && mdx_uniform_lj(reinterpret_cast<const float*>(h->h_lj.data()), h->h_lj.size(),
+                                           h->cfg.combining_rule == MDX_COMBINE_GEOMETRIC, h->alch_on, &c);
+    h->uni_lj = ok; h->uni_c = ok ? c : 0.f;
 }
 
 // constraints / virtual sites (mdx_constraints.hip)

@@ -95,6 +95,7 @@ void mdx_fill_nb_params(const mdx_handle* h, NbParams& p, int* mode_out, bool* g
     p.etab = mode == CM_EWALD ? h->d.ewald_tab : nullptr;
     p.etab_n = p.etab ? h->ewald_tab_n : 0u;
     p.etab_scale = h->ewald_tab_scale; p.etab_shift = h->ewald_tab_shift;
+    p.uni_c = h->uni_lj ? h->uni_c : 0.f;
 }
 
 // g(r^2) = [erf(beta r)/r - 2 beta/sqrt(pi) exp(-beta^2 r^2)] / r^2 over the intervals of the bit-indexed table (mdx_pair_dev.h), in fp64

@@ -229,7 +229,10 @@ __device__ __forceinline__ float dpp_xadd(float v) {
 // from the two rows every reader uses (mdx_bonded_dev.h step_pos), full kick, the next step's Y, path length, the words that gate the next
 // launch - then evaluates the pairs at x as below, j-atoms reconstructed from the same two rows, and its atoms' bonded roles.  The separate
 // bonded + kick + drift pass (35 us of a 513 us step at 1 M atoms, 112 B per atom) rides inside this compute-bound launch instead.
-template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, int WPT, bool HALF, bool ALCH, int DUAL, int BW, bool STEP = false>
+// UNI (handles with one Lennard-Jones atom type, mdx_uniform_lj; force-only Lorentz-Berthelot flavours without STEP): sigma_ij^2 is the
+// constant a.p.uni_c (pair_eval<..., UNI>), so the eight sgi registers, the .x of the j-side pipeline registers and of the per-entry
+// LDS read are gone: the strip s_lj holds ONE float per j-atom, sqrt(24 eps).  The lj[] rows in memory keep both halves.
+template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, int WPT, bool HALF, bool ALCH, int DUAL, int BW, bool STEP = false, bool UNI = false>
 __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owned_prune, float4 (*s_xyzq)[64], float2 (*s_lj)[64],
                                                 float (*s_red)[3][64], float (*s_ownj)[64], float4 (*s_g)[64],
                                                 unsigned long long (*s_mask)[64], const float4* __restrict__ etab = nullptr) {
@@ -239,6 +242,7 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     // BW < WPT: the WPT waves of a tile sit in WPT / BW workgroups (systems of a few hundred tiles: with one workgroup per
     // tile 370 tiles land on 256 CUs as one or two per CU and the launch lasts as long as the CUs that got two)
     constexpr int SPLIT = BW < WPT ? WPT / BW : 1;
+    static_assert(!UNI || (!ENERGY && !GEOM && !ALCH && !STEP), "the constant-sigma^2 body: force-only, Lorentz-Berthelot, no alchemical window");
     static_assert(SPLIT == 1 || HALF, "a tile split over workgroups returns its i-forces through atomics");
     constexpr int TPB = SPLIT > 1 ? 1 : BW / WPT;             // tiles per workgroup
     const uint32_t ntiles = a.tile_order ? a.t_count : a.T;   // (a decomposed handle launches its interior and boundary tiles apart)
@@ -367,7 +371,7 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     for (int ci = 0; ci < 8; ++ci) {
         const uint32_t s = t * MDX_TILE + ci * MDX_CLUSTER + ii;
         const float4 pi = a.posq[s];
-        const float2 li = a.lj[s];
+        const float2 li = UNI ? make_float2(0.f, reinterpret_cast<const float*>(a.lj)[2 * s + 1]) : a.lj[s];      // (UNI: sgi[] is never read)
         xi[ci] = pi.x; yi[ci] = pi.y; zi[ci] = pi.z; qi[ci] = pi.w; sgi[ci] = li.x; epi[ci] = li.y;
         fx[ci] = 0.f; fy[ci] = 0.f; fz[ci] = 0.f;
     }
@@ -383,7 +387,9 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     const uint32_t nchunks = DUAL == 1 ? (t_ok ? a.inner_nch[t * 8 + part] : 0u) : (cnt.n_masked + cnt.n_plain) >> 3;
     const uint32_t mbase = a.mchunk_off[t_ok ? t : 0];
     float4* sx = s_xyzq[wave];
-    float2* sl = s_lj[wave];
+    float2* sl = UNI ? nullptr : s_lj[wave];
+    float* const sle = reinterpret_cast<float*>(s_lj) + wave * 64;      // (UNI) the wave's strip: sqrt(24 eps) of the staged j-atoms
+    const float* __restrict__ const lj_eps = reinterpret_cast<const float*>(a.lj) + 1;      // (UNI) the .y of record k at [2 k]
     double elj = 0.0, ecoul = 0.0, evir = 0.0, ecross = 0.0, edudl = 0.0;
     uint32_t own_bits = 0xFFu;   // ENERGY only: bit ci set <=> i-atom (ci, ii) is owned by this rank
     if (ENERGY && !a.energy_all) {
@@ -410,7 +416,8 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
         if ((uint32_t)part < nmc) nmq = a.masks[(size_t)(mbase + part) * 64 + lane];
         if ((uint32_t)part + wv < nchunks) ent_n = entries[e0 + (part + wv) * 8 + (lane >> 3)];
         const uint32_t js = ent.x * MDX_CLUSTER + (lane & 7);
-        nj = a.posq[js]; nl = a.lj[js]; ny = ent.y; njc = ent.x;
+        nj = a.posq[js]; ny = ent.y; njc = ent.x;
+        if (UNI) nl.y = lj_eps[2 * js]; else nl = a.lj[js];
         if (STEP) nf = a.st_fprev[js];
         if (ENERGY && HALF) nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
     }
@@ -461,13 +468,14 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
             nj.y += (float)ky * a.p.shift[1];
             nj.z += (float)kz * a.p.shift[2];
             sx[lane] = nj;
-            sl[lane] = nl;
+            if (UNI) sle[lane] = nl.y; else sl[lane] = nl;
         }
         WAVE_LDS_SYNC();
         if (c + wv < nmc) nmq = a.masks[(size_t)(mbase + c + wv) * 64 + lane];
         if (c + wv < nchunks) {
             const uint32_t js = ent_n.x * MDX_CLUSTER + (lane & 7);
-            nj = a.posq[js]; nl = a.lj[js]; ny = ent_n.y; njc = ent_n.x;
+            nj = a.posq[js]; ny = ent_n.y; njc = ent_n.x;
+            if (UNI) nl.y = lj_eps[2 * js]; else nl = a.lj[js];
             if (STEP) nf = a.st_fprev[js];
             if (ENERGY && HALF) nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
             if (c + 2 * wv < nchunks) ent_n = entries[e0 + (c + 2 * wv) * 8 + (lane >> 3)];
@@ -481,7 +489,7 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
 #pragma unroll 1
         for (int e = 0; e < 8; ++e) {
             const float4 pj = sx[e * 8 + jj];
-            const float2 lj = sl[e * 8 + jj];
+            const float2 lj = UNI ? make_float2(0.f, sle[e * 8 + jj]) : sl[e * 8 + jj];
             const uint32_t im = (__builtin_amdgcn_readlane(cur_y, e * 8) >> 8) & 0xFFu;  // wave-uniform
             if (im == 0) continue;
             uint32_t newm = 0;
@@ -497,12 +505,12 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
                     // 0.0f or NaN: sign-extend bit ci of the exclusion byte over the word (one v_bfe_i32)
                     const float bias = MASKED_CHUNK ? __int_as_float((x8 << (31 - ci)) >> 31) : 0.f;
                     float r2v = 0.f;
-                    constexpr bool ASM_PAIR = NB_ASM_PAIR && !ENERGY && COUL == CM_SHIFTED && !GEOM && SAMECUT && HALF && !ALCH;
+                    constexpr bool ASM_PAIR = NB_ASM_PAIR && !ENERGY && COUL == CM_SHIFTED && !GEOM && SAMECUT && HALF && !ALCH && !UNI;
                     if constexpr (ASM_PAIR)
                         pair_eval_asm<MASKED_CHUNK, prune>(xi[ci], yi[ci], zi[ci], qi[ci], sgi[ci], epi[ci], pj, lj, rc2_s, bias, fx[ci], fy[ci], fz[ci],
                                                            g[0], g[1], g[2], r2v);
                     else
-                    pair_eval<ENERGY, COUL, GEOM, SAMECUT, true, HALF, ALCH, MASKED_CHUNK>(xi[ci], yi[ci], zi[ci], qi[ci], sgi[ci], epi[ci],
+                    pair_eval<ENERGY, COUL, GEOM, SAMECUT, true, HALF, ALCH, MASKED_CHUNK, UNI>(xi[ci], yi[ci], zi[ci], qi[ci], sgi[ci], epi[ci],
                                                                              pj, lj, true, a.p, fx[ci], fy[ci],
                                                                              fz[ci], e1, e2, g, ENERGY ? &e3 : nullptr,
                                                                              (ENERGY && ALCH) ? &e4 : nullptr, bias,
@@ -712,7 +720,7 @@ __device__ __attribute__((noinline)) void nb_cluster_body_call(const NbArgs& a, 
     nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, DUAL, BW>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
 }
 
-template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, int WPT, bool HALF, bool ALCH = false, int DUAL = 0, bool FB = false, int SPLIT = 1>
+template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, int WPT, bool HALF, bool ALCH = false, int DUAL = 0, bool FB = false, int SPLIT = 1, bool UNI = false>
 __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : NB_WAVES)) * 64, ((HALF && NB_HALF_FLUSH) || ENERGY || (DUAL == 5 && NB_STEP_WAVES3)) ? 3 : 4) void nb_cluster_kernel(NbArgs a) {
     if (a.gate && *a.gate > a.thr_bits) {
         // (one launch per step: the stale word travels on, the launches behind this one stay no-ops too)
@@ -724,6 +732,7 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
     static_assert(DUAL != 5 || (WPT == 1 && !FB && SPLIT == 1), "one launch per step: the one-wave-per-tile class");
     static_assert(DUAL != 6 || (WPT == 8 && !FB), "one launch per step: the eight-waves-per-tile class");
     constexpr bool STEP = DUAL == 5 || DUAL == 6;
+    static_assert(!UNI || (!ENERGY && !GEOM && !ALCH && !STEP && !FB && SPLIT == 1 && DUAL <= 3), "the constant-sigma^2 bodies that exist (launch_cluster)");
     static_assert(DUAL == 0 || (HALF && !ENERGY), "the dual list exists for the half-list force kernel");
     static_assert(!FB || DUAL != 0, "the bonded workgroups ride with the dual-list launches");
     constexpr int BW = SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : NB_WAVES);       // waves per workgroup
@@ -737,7 +746,7 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
         return;
     }
     __shared__ float4 s_xyzq[BW][64];
-    __shared__ float2 s_lj[BW][64];
+    __shared__ float2 s_lj[UNI ? (BW + 1) / 2 : BW][64];     // (UNI: one float per j-atom, BW strips of 64 floats)
     __shared__ float s_red[WPT > 1 ? BW : 1][3][64];
     __shared__ float s_ownj[(ENERGY && HALF) ? BW : 1][64];   // 1.0 <=> the staged j-atom is owned here
     __shared__ float4 s_g[HALF ? BW : 1][64];                 // minus the chunk's j-forces (.w: the j-slot), until flushed
@@ -755,22 +764,23 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
     const unsigned long long drain_t0 = wall_clock64();
 #endif
     if (DUAL == 0) {
-        nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 0, BW>(a, true, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
+        nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 0, BW, false, UNI>(a, true, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
     } else {
         const bool owned_prune = (a.force_prune | *a.prune_flag) != 0u;
         const bool want_prune = owned_prune || (a.prune_flag2 && *a.prune_flag2 != 0u);
         if (DUAL >= 3) {        // merged launch: the device picks the body
 #if NB_MERGED_NOINLINE
+            static_assert(!UNI, "the experiment has the general bodies only");
             // (experiment: the two bodies as real functions, so that each keeps the register allocation of its stand-alone kernel)
             if (want_prune) nb_cluster_body_call<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 2, BW>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
             else nb_cluster_body_call<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 1, BW>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
 #else
-            if (want_prune) nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 2, BW, STEP>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
-            else nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 1, BW, STEP>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
+            if (want_prune) nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 2, BW, STEP, UNI>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
+            else nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, 1, BW, STEP, UNI>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
 #endif
         } else {
             if (want_prune != (DUAL == 2)) return;
-            nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, DUAL == 2 ? 2 : 1, BW>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
+            nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, DUAL == 2 ? 2 : 1, BW, false, UNI>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
         }
 #ifdef NB_DRAIN_TRACE
         // every wave: the constant-rate clock at entry and at exit (after its atomics have left), HW_ID and XCC_ID (which SIMD of which
@@ -788,9 +798,27 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
     }
 }
 
+// The launches that exist with a constant-sigma^2 body (UNI; handles with one LJ atom type, `uni`): force-only, Lorentz-Berthelot, not
+// the softened Coulomb - the one-wave half-list kernels (plain list, the dual-list twins, the merged launch) and the full-list
+// kernels of four and eight waves per tile.  Everything else, and every handle that is not eligible, gets the general body.
+// Returns whether the UNI body went out (mdx_pair_body_info).
+template <bool ENERGY, int COUL, bool G, bool S, int WPT, bool HALF, int DUAL>
+static bool launch_cluster(bool uni, dim3 g, dim3 b, uint32_t lds, hipStream_t st, const NbArgs& a) {
+    if constexpr (!ENERGY && !G && COUL != CM_SOFT) {
+        if (uni) {
+            hipLaunchKernelGGL((nb_cluster_kernel<false, COUL, false, S, WPT, HALF, false, DUAL, false, 1, true>), g, b, lds, st, a);
+            return true;
+        }
+    }
+    hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, WPT, HALF, false, DUAL>), g, b, lds, st, a);
+    return false;
+}
+
 template <bool ENERGY, int COUL>
 void launch_variant(mdx_handle* h, const NbArgs& a_in, bool geom, bool samecut) {
     NbArgs a = a_in;
+    const bool uni = h->uni_lj && !h->alch_on && !geom && a.p.uni_c != 0.f;
+    bool uni_used = false;
     const int var = mdx_nb_variant(h);
     // waves per tile: split a tile's list over the 4 waves of its workgroup when the launch has
     // fewer tiles than ~3 per SIMD (the chip holds 4 waves/SIMD of this kernel on 1024 SIMDs)
@@ -897,7 +925,7 @@ void launch_variant(mdx_handle* h, const NbArgs& a_in, bool geom, bool samecut) 
         note(D, wpt == 8 || wpt == 2 || wpt == 1 ? wpt : 4, 1, 0);                                                     \
         if (wpt == 8) hipLaunchKernelGGL((nb_cluster_kernel<false, COUL, G, S, 8, true, false, D>), g, b, lds_pad, h->stream, a); \
         else if (wpt == 2) hipLaunchKernelGGL((nb_cluster_kernel<false, COUL, G, S, 2, true, false, D>), g, b, lds_pad, h->stream, a); \
-        else if (wpt == 1) hipLaunchKernelGGL((nb_cluster_kernel<false, COUL, G, S, 1, true, false, D>), g, b, lds_pad, h->stream, a); \
+        else if (wpt == 1) uni_used = launch_cluster<false, COUL, G, S, 1, true, D>(uni, g, b, lds_pad, h->stream, a);                 \
         else hipLaunchKernelGGL((nb_cluster_kernel<false, COUL, G, S, 4, true, false, D>), g, b, lds_pad, h->stream, a);               \
     } while (0)
 #define NB_LAUNCH(G, S)                                                                                    \
@@ -925,10 +953,10 @@ void launch_variant(mdx_handle* h, const NbArgs& a_in, bool geom, bool samecut) 
         else if (half && a.inner) { if (!a.force_prune) NB_DUAL(G, S, 1); NB_DUAL(G, S, 2); }   /* (a pass the host forces: no twin) */ \
         else if (half && wpt == 8) hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, 8, true>), g, b, lds_pad, h->stream, a); \
         else if (half && wpt == 2) hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, 2, true>), g, b, lds_pad, h->stream, a); \
-        else if (half && wpt == 1) hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, 1, true>), g, b, lds_pad, h->stream, a); \
+        else if (half && wpt == 1) uni_used = launch_cluster<ENERGY, COUL, G, S, 1, true, 0>(uni, g, b, lds_pad, h->stream, a);    \
         else if (half) hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, 4, true>), g, b, lds_pad, h->stream, a); \
-        else if (wpt == 8) hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, 8, false>), g, b, lds_pad, h->stream, a); \
-        else if (wpt == 4) hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, 4, false>), g, b, lds_pad, h->stream, a); \
+        else if (wpt == 8) uni_used = launch_cluster<ENERGY, COUL, G, S, 8, false, 0>(uni, g, b, lds_pad, h->stream, a);           \
+        else if (wpt == 4) uni_used = launch_cluster<ENERGY, COUL, G, S, 4, false, 0>(uni, g, b, lds_pad, h->stream, a);           \
         else hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, 1, false>), g, b, lds_pad, h->stream, a);        \
     } while (0)
     if (geom) { if (samecut) NB_LAUNCH(true, true); else NB_LAUNCH(true, false); }
@@ -936,5 +964,8 @@ void launch_variant(mdx_handle* h, const NbArgs& a_in, bool geom, bool samecut) 
 #undef NB_LAUNCH
 #undef NB_DUAL
 #undef NB_STEP
+    // (mdx_pair_body_info: did the constant-sigma^2 body go out - by the step loop, by anything)
+    if (a.inner || (h->nb_step >= 0 && a.gate)) h->pair_body_step = uni_used ? 1u : 0u;
+    h->pair_body_any = uni_used ? 1u : 0u;
 }
 

@@ -98,7 +98,12 @@ enum { CM_SHIFTED = 0, CM_RF = 1, CM_EWALD = 2, CM_SOFT = 3,
 // (v_bfe_i32 of the mask byte) instead of v_and + v_cmp + s_and, and one step less in the dependent chain in front
 // of the exec-mask branch.  Adding 0.0f is exact: r^2 has the bits of the plain expression.  Requires BRANCHY (the
 // NaN must never reach an accumulator).
-template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, bool BRANCHY, bool HALF = false, bool ALCH = false, bool NANMASK = false>
+//
+// UNI = true (force-only Lorentz-Berthelot flavours of the cluster kernel, handles with ONE Lennard-Jones atom type: mdx_uniform_lj):
+// sigma_ij^2 is the constant p.uni_c - the f32 value (s/2 + s/2)^2 has for any two atoms with a well - instead of an add and a multiply
+// per pair; sgi and lj.x are not read.  A pair with a well-free atom gets the constant too, and its LJ term is multiplied by eps = 0 as
+// before.  Everything behind s2 is the same instructions in the same order: the bits of the general body.
+template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, bool BRANCHY, bool HALF = false, bool ALCH = false, bool NANMASK = false, bool UNI = false>
 __device__ __forceinline__ void pair_eval(float xi, float yi, float zi, float qi, float sgi, float epi,
                                           const float4 pj, const float2 lj, bool allowed, const NbParams& p,
                                           float& fx, float& fy, float& fz, float& elj, float& ecoul,
@@ -106,6 +111,7 @@ __device__ __forceinline__ void pair_eval(float xi, float yi, float zi, float qi
                                           float r2bias = 0.f, float* r2_out = nullptr, float* edudl = nullptr,
                                           const float4* __restrict__ etab = nullptr) {
     static_assert(!NANMASK || BRANCHY, "the NaN-coded exclusion needs the early-out");
+    static_assert(!UNI || (!ENERGY && !GEOM && !ALCH), "the constant-sigma^2 body: force-only, Lorentz-Berthelot, no alchemical window");
     const float dx = xi - pj.x, dy = yi - pj.y, dz = zi - pj.z;   // tgt - src (src/cuda/util.cu:118-140)
     const float r2 = NANMASK ? __builtin_fmaf(dz, dz, __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, r2bias)))
                              : dx * dx + dy * dy + dz * dz;
@@ -114,7 +120,7 @@ __device__ __forceinline__ void pair_eval(float xi, float yi, float zi, float qi
     const bool in_lj = (r2 < p.rc2_lj) && allowed;
     const bool in_c = SAMECUT ? in_lj : ((r2 < p.rc2_coul) && allowed);
     if (BRANCHY && !(in_lj || in_c)) return;
-    const float sig = GEOM ? sgi * lj.x : sgi + lj.x;
+    const float sig = UNI ? 0.f : (GEOM ? sgi * lj.x : sgi + lj.x);
     const float eps_s = epi * lj.y;                 // 24 eps_ij (ALCH: signed)
     const float eps = ALCH ? fabsf(eps_s) : eps_s;
     // ALCH: a pair with exactly one atom in the coupled molecule.  Soft core (Beutler et al. 1994): it interacts at
@@ -144,7 +150,7 @@ __device__ __forceinline__ void pair_eval(float xi, float yi, float zi, float qi
         if (cross && p.sc_al != 0.f) r2e = __builtin_amdgcn_rcpf(rinv * rinv);
     } else rinv = __builtin_amdgcn_rsqf(r2);
     const float rinv2 = rinv * rinv;
-    const float s2 = sig * sig * rinv2;
+    const float s2 = (UNI ? p.uni_c : sig * sig) * rinv2;
     const float s6 = s2 * s2 * s2;
     const float es6 = eps * s6;
 #ifdef NB_EXP_NOLJ

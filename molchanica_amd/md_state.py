@@ -85,6 +85,7 @@ def load_library():
     lib.mdx_get_stats.argtypes = [H, C.POINTER(CStats)]
     lib.mdx_get_skin.argtypes = [H, _fp, C.POINTER(C.c_int)]
     lib.mdx_pair_launch_info.argtypes = [H, _u32p]
+    lib.mdx_pair_body_info.argtypes = [H, _u32p]
     lib.mdx_minimize_energy.argtypes = [H, C.c_uint32, _fp, C.c_float, C.POINTER(CEnergies), _u32p]
     lib.mdx_initialize_velocities.argtypes = [H, C.c_float, C.c_int, C.c_uint64]
     lib.mdx_set_thermostat.argtypes = [H, C.c_int, C.c_float, C.c_float, C.c_uint32, C.c_uint64]
@@ -621,6 +622,13 @@ class MdState:
                 "one_launch_steps": int(out[20]), "kicks_beyond_grant": int(out[21]),
                 # mixed waves per tile of the last dual-list launch of the step loop: units per closing tile (0: none), closing tiles
                 "tail": {"waves_per_tile": int(out[22]), "tiles": int(out[23])}}
+
+    def pair_body_info(self) -> dict:
+        """The constant-sigma^2 body of the pair kernel (handles with one LJ atom type; include/mdx.h: mdx_pair_body_info)."""
+        out = (C.c_uint32 * 4)()
+        _check(load_library().mdx_pair_body_info(self._h, out))
+        return {"eligible": bool(out[0]), "step": bool(out[1]), "any": bool(out[2]), "c_bits": int(out[3]),
+                "c": float(np.array([out[3]], np.uint32).view(np.float32)[0])}
 
     def skin(self):
         """-> (Verlet skin in force, still tuning?)  (MdConfig.skin == 0 lets the library choose it)."""
