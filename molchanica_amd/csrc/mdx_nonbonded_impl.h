@@ -82,9 +82,9 @@ __device__ __forceinline__ void pair_eval_asm(float xi, float yi, float zi, floa
         "v_fmac_f32 %[fx], %[dx], %[t1]\n\t"
         "v_fmac_f32 %[fy], %[dy], %[t1]\n\t"
         "v_fmac_f32 %[fz], %[dz], %[t1]\n\t"
-        "v_fmac_f32 %[g0], %[dx], %[t1]\n\t"
-        "v_fmac_f32 %[g1], %[dy], %[t1]\n\t"
-        "v_fmac_f32 %[g2], %[dz], %[t1]\n\t"
+        "v_fma_f32 %[g0], -%[dx], %[t1], %[g0]\n\t"       // the force on j, with the sign it leaves with
+        "v_fma_f32 %[g1], -%[dy], %[t1], %[g1]\n\t"
+        "v_fma_f32 %[g2], -%[dz], %[t1], %[g2]\n\t"
         "s_mov_b64 exec, -1\n\t"
         : [fx] "+v"(fx), [fy] "+v"(fy), [fz] "+v"(fz), [g0] "+v"(g0), [g1] "+v"(g1), [g2] "+v"(g2), [r2] "+v"(r2),
           [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4)
@@ -212,10 +212,9 @@ __global__ __launch_bounds__(NB_WAVES * 64) void nb_tile_kernel(NbArgs a) {
 // them once per chunk (NB_HALF_FLUSH=1: 0.79 vs 0.66 ms, it needs 137 VGPRs = 3 waves/SIMD);
 // any form of LDS look-ahead of the next entry's j record (+6..8 %, both kernels).
 // The force array must be zero when the kernel starts.
-template <int CTRL>
-__device__ __forceinline__ float dpp_xadd(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
+// What runs once per ENTRY around the cluster pairs is trimmed to the instructions the result needs (mdx_pair_dev.h jforce_reduce8:
+// select the component first, then one mirror add; the reaction accumulates with the sign it leaves with; the atomic's address is a
+// scalar base plus a loop-invariant lane offset; the eps strip has the position strip's stride, one LDS address register for both).
 
 // DUAL (dual pair list, half-list force flavour only): 0 = plain list; 1 = walk the INNER list, a no-op when this step
 // must prune; 2 = the pruning pass (walks the Verlet list, writes the inner list), a no-op unless this step must prune.  The step loop enqueues 1 and 2 back to back
@@ -231,9 +230,9 @@ __device__ __forceinline__ float dpp_xadd(float v) {
 // bonded + kick + drift pass (35 us of a 513 us step at 1 M atoms, 112 B per atom) rides inside this compute-bound launch instead.
 // UNI (handles with one Lennard-Jones atom type, mdx_uniform_lj; force-only Lorentz-Berthelot flavours without STEP): sigma_ij^2 is the
 // constant a.p.uni_c (pair_eval<..., UNI>), so the eight sgi registers, the .x of the j-side pipeline registers and of the per-entry
-// LDS read are gone: the strip s_lj holds ONE float per j-atom, sqrt(24 eps).  The lj[] rows in memory keep both halves.
+// LDS read are gone: of a record of the strip s_lj only .x is used, sqrt(24 eps).  The lj[] rows in memory keep both halves.
 template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, int WPT, bool HALF, bool ALCH, int DUAL, int BW, bool STEP = false, bool UNI = false>
-__device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owned_prune, float4 (*s_xyzq)[64], float2 (*s_lj)[64],
+__device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owned_prune, float4 (*s_xyzq)[64], float4 (*s_lj)[64],
                                                 float (*s_red)[3][64], float (*s_ownj)[64], float4 (*s_g)[64],
                                                 unsigned long long (*s_mask)[64], const float4* __restrict__ etab = nullptr) {
     // the wave index is wave-uniform: say so, and tile number, list bounds and the chunk loop
@@ -387,8 +386,9 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     const uint32_t nchunks = DUAL == 1 ? (t_ok ? a.inner_nch[t * 8 + part] : 0u) : (cnt.n_masked + cnt.n_plain) >> 3;
     const uint32_t mbase = a.mchunk_off[t_ok ? t : 0];
     float4* sx = s_xyzq[wave];
-    float2* sl = UNI ? nullptr : s_lj[wave];
-    float* const sle = reinterpret_cast<float*>(s_lj) + wave * 64;      // (UNI) the wave's strip: sqrt(24 eps) of the staged j-atoms
+    // the wave's Lennard-Jones strip, one record per 16 B like the position strip (the entry loop reads both through ONE address
+    // register, the second at an immediate offset): .x, .y = the j-atom's float2; UNI: .x = its sqrt(24 eps)
+    float4* const sl = s_lj[wave];
     const float* __restrict__ const lj_eps = reinterpret_cast<const float*>(a.lj) + 1;      // (UNI) the .y of record k at [2 k]
     double elj = 0.0, ecoul = 0.0, evir = 0.0, ecross = 0.0, edudl = 0.0;
     uint32_t own_bits = 0xFFu;   // ENERGY only: bit ci set <=> i-atom (ci, ii) is owned by this rank
@@ -422,6 +422,10 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
         if (ENERGY && HALF) nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
     }
     float* const fbase = reinterpret_cast<float*>(a.force);
+    // (HALF) loop invariants of the per-entry j-force tail: which component this lane carries through the last reduction level, and
+    // the byte offset of its word in the j-cluster's eight force rows
+    const bool jsel_x = ii == 0 || ii == 7, jsel_y = ii == 1 || ii == 6;
+    const uint32_t jlane_off = (uint32_t)(jj * 4 + ii) * 4u;
     float4* const sg = s_g[HALF ? wave : 0];
     // Dual pair list.  Normal launch (DUAL 1): the list is the INNER one: cluster pairs that had an atom pair within
     // cutoff + inner_skin at the last pruning pass.  Pruning launch (DUAL 2; forced by the host after a rebuild, or asked
@@ -468,7 +472,8 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
             nj.y += (float)ky * a.p.shift[1];
             nj.z += (float)kz * a.p.shift[2];
             sx[lane] = nj;
-            if (UNI) sle[lane] = nl.y; else sl[lane] = nl;
+            // (once per chunk; the 16-B stride makes this store a 4-way bank conflict)
+            if (UNI) sl[lane].x = nl.y; else *reinterpret_cast<float2*>(&sl[lane]) = nl;
         }
         WAVE_LDS_SYNC();
         if (c + wv < nmc) nmq = a.masks[(size_t)(mbase + c + wv) * 64 + lane];
@@ -489,13 +494,13 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
 #pragma unroll 1
         for (int e = 0; e < 8; ++e) {
             const float4 pj = sx[e * 8 + jj];
-            const float2 lj = UNI ? make_float2(0.f, sle[e * 8 + jj]) : sl[e * 8 + jj];
+            const float2 lj = UNI ? make_float2(0.f, sl[e * 8 + jj].x) : *reinterpret_cast<const float2*>(&sl[e * 8 + jj]);
             const uint32_t im = (__builtin_amdgcn_readlane(cur_y, e * 8) >> 8) & 0xFFu;  // wave-uniform
             if (im == 0) continue;
             uint32_t newm = 0;
             // (as EXCLUDED bits: bit ci set <=> this lane's pair with i-cluster ci is masked out)
             const int x8 = MASKED_CHUNK ? (int)(~(uint32_t)reinterpret_cast<const uint8_t*>(&s_mask[wave][lane])[e]) : 0;
-            float g[3] = {0.f, 0.f, 0.f};
+            float g[3] = {-0.f, -0.f, -0.f};      // the force on j (pair_eval subtracts into it; -0: the negative of a sum that starts at +0)
             float wj = 0.f;
             if (ENERGY && HALF) wj = 0.5f * s_ownj[wave][e * 8 + jj];
 #pragma unroll
@@ -539,23 +544,31 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
                 kept += __popc(newm);
                 if (jj == e) newy |= newm << 8;
             }
-            if (HALF) {
-                // sum over the eight i-lanes of every j-atom: xor 1, xor 2 (quad_perm), then the
-                // other quad of the row half (row_half_mirror) - every lane ends with the total
+            if (HALF && NB_HALF_FLUSH) {
+                // (the experiment keeps the three-register form: every lane ends with the three totals)
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
                     g[d] = dpp_xadd<0xB1>(g[d]);
                     g[d] = dpp_xadd<0x4E>(g[d]);
                     g[d] = dpp_xadd<0x141>(g[d]);
                 }
+                if (ii < 3) reinterpret_cast<float*>(sg)[(e * 8 + jj) * 4 + ii] = ii == 0 ? g[0] : (ii == 1 ? g[1] : g[2]);
+            } else if (HALF) {
+                // sum over the eight i-lanes of every j-atom, in full exec (jforce_reduce8); lanes ii < 3 then hold x, y, z of the
+                // j-atom's force and add it to its row: 24 lanes, one 128-B line, at a wave-uniform base + this lane's offset
+                const float v = jforce_reduce8(g, jsel_x, jsel_y);
+                // (keep the base in scalar registers: the atomic then takes it as its saddr operand with the lane offset beside it;
+                // otherwise fbase + lane offset is hoisted as a 64-bit vector pointer and every entry pays a v_lshl_add_u64)
+                typedef __attribute__((address_space(1))) char gchar;
+                gchar* frow = (gchar*)(fbase + (size_t)__builtin_amdgcn_readlane(cur_jc, e * 8) * (MDX_CLUSTER * 4));
+                asm("" : "+s"(frow));
                 if (ii < 3) {
-                    const float v = ii == 0 ? g[0] : (ii == 1 ? g[1] : g[2]);
-                    if (NB_HALF_FLUSH) reinterpret_cast<float*>(sg)[(e * 8 + jj) * 4 + ii] = -v;
+                    uint32_t off = jlane_off;
+                    asm("" : "+v"(off));      // (the 32-bit offset is widened HERE, where instruction selection sees it beside the atomic)
 #ifdef NB_EXP_NOATOMIC
-                    else if (v == 1.2345e30f) unsafeAtomicAdd(fbase + (size_t)__builtin_amdgcn_readlane(cur_jc, e * 8) * (MDX_CLUSTER * 4) + jj * 4 + ii, -v);
-#else
-                    else unsafeAtomicAdd(fbase + (size_t)__builtin_amdgcn_readlane(cur_jc, e * 8) * (MDX_CLUSTER * 4) + jj * 4 + ii, -v);
+                    if (v == 1.2345e30f)
 #endif
+                    unsafeAtomicAdd((float*)(frow + off), v);
                 }
             }
         }
@@ -714,7 +727,7 @@ __device__ __forceinline__ void bonded_workgroup(const NbArgs& a, uint32_t wg, u
 #define NB_MERGED_NOINLINE 0
 #endif
 template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, int WPT, bool HALF, bool ALCH, int DUAL, int BW>
-__device__ __attribute__((noinline)) void nb_cluster_body_call(const NbArgs& a, const bool owned_prune, float4 (*s_xyzq)[64], float2 (*s_lj)[64],
+__device__ __attribute__((noinline)) void nb_cluster_body_call(const NbArgs& a, const bool owned_prune, float4 (*s_xyzq)[64], float4 (*s_lj)[64],
                                                                float (*s_red)[3][64], float (*s_ownj)[64], float4 (*s_g)[64],
                                                                unsigned long long (*s_mask)[64], const float4* __restrict__ etab = nullptr) {
     nb_cluster_body<ENERGY, COUL, GEOM, SAMECUT, WPT, HALF, ALCH, DUAL, BW>(a, owned_prune, s_xyzq, s_lj, s_red, s_ownj, s_g, s_mask, etab);
@@ -746,7 +759,7 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
         return;
     }
     __shared__ float4 s_xyzq[BW][64];
-    __shared__ float2 s_lj[UNI ? (BW + 1) / 2 : BW][64];     // (UNI: one float per j-atom, BW strips of 64 floats)
+    __shared__ float4 s_lj[BW][64];                           // the position strip's stride (UNI: .x only, else .x and .y of a record)
     __shared__ float s_red[WPT > 1 ? BW : 1][3][64];
     __shared__ float s_ownj[(ENERGY && HALF) ? BW : 1][64];   // 1.0 <=> the staged j-atom is owned here
     __shared__ float4 s_g[HALF ? BW : 1][64];                 // minus the chunk's j-forces (.w: the j-slot), until flushed

@@ -15,6 +15,31 @@ void mdx_fill_nb_params(const mdx_handle* h, NbParams& p, int* mode_out, bool* g
         __builtin_amdgcn_wave_barrier();                       \
     } while (0)
 
+// v + (v of the lane the DPP control word names): 0xB1 = lane ^ 1, 0x4E = lane ^ 2 (quad_perm), 0x141 = row_half_mirror (lane 7 - l
+// of the same eight).  Call it with every lane of the eight switched on: a DPP read of a lane that EXEC has switched off does not
+// return that lane's value.
+template <int CTRL>
+__device__ __forceinline__ float dpp_xadd(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+
+// The half list's j-force reduction: g[] = this lane's x, y, z share of the force on ONE j-atom, the atom's eight lanes (ii = lane & 7)
+// side by side.  Two quad levels per component, then the lane SELECTS the one component it is going to add to memory - x in lanes 0 and
+// 7 (sel_x), y in lanes 1 and 6 (sel_y), z elsewhere: the two masks are loop invariants of the caller - and ONE row_half_mirror add
+// finishes it: lane ii < 3 returns the total of component ii, (quad sum of its own quad) + (quad sum of lane 7 - ii's), the two
+// operands the three-register form adds.  Lanes 3 .. 7 return sums nobody reads.  Nine instructions (6 quad adds, 2 selects, 1 mirror
+// add) where the three-register form compiled to fourteen (6, then 3 DPP moves, 3 adds, 2 selects).
+__device__ __forceinline__ float jforce_reduce8(const float g[3], const bool sel_x, const bool sel_y) {
+    float q[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) q[d] = dpp_xadd<0x4E>(dpp_xadd<0xB1>(g[d]));
+    float v = dpp_xadd<0x141>(sel_x ? q[0] : (sel_y ? q[1] : q[2]));
+    // pin the add where all eight lanes run: left alone, the compiler sinks it into the caller's `ii < 3` region and leaves a
+    // v_mov_b32_dpp behind (two instructions, and the three-register form's eight came about the same way)
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 struct NbArgs {
     uint32_t T;
     const float4* posq; const float2* lj;
@@ -185,7 +210,8 @@ __device__ __forceinline__ void pair_eval(float xi, float yi, float zi, float qi
         fs *= cross ? ascale * w * w : 1.0f;
     }
     fx += fs * dx; fy += fs * dy; fz += fs * dz;
-    if (HALF) { g[0] += fs * dx; g[1] += fs * dy; g[2] += fs * dz; }   // minus the force on j
+    // the force on j, with the sign it leaves with (g[] starts at -0.0f: every sum is the exact negative of the +fs form's)
+    if (HALF) { g[0] = __builtin_fmaf(-fs, dx, g[0]); g[1] = __builtin_fmaf(-fs, dy, g[1]); g[2] = __builtin_fmaf(-fs, dz, g[2]); }
     if (ENERGY) {
         const float e_l = es6 * (s6 - 1.0f) * (1.0f / 6.0f);  // 4 eps (s12 - s6)
         float e_c;
