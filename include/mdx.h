@@ -605,7 +605,8 @@ int      mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, uint32_t
  * rounded values reproduces poses_out to about 1e-6 of the molecule's extent only -, status_out[p], evals_out[p].
  * A pose gives the same bits (poses, rows, rigid, status, evals) alone or in a batch of any size, at any place in it.  Pass every pose
  * as one whole molecule: centroid, torque and inertia are taken of the coordinates as given.  The gradient carries no bond, angle or
- * dihedral term of the ligand, so the refinement is rigid; with tolerances of 0 every pose runs until it stalls or max_evals is spent. */
+ * dihedral term of the ligand, so the refinement is rigid (mdx_refine_poses_flex below lets the ligand's rotatable bonds relax as
+ * well); with tolerances of 0 every pose runs until it stalls or max_evals is spent. */
 typedef struct { uint32_t max_evals; float f_tol, tau_tol, h_start, h_max; } mdx_refine_opts;
 #define MDX_REFINE_CONVERGED 0u
 #define MDX_REFINE_MAX_EVALS 1u
@@ -617,6 +618,52 @@ int      mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_
                           float* rows_out_or_null /* [n_poses][n_groups] */, uint32_t n_groups, float* rigid_out_or_null /* [n_poses][6] */,
                           float* xform_out_or_null /* [n_poses][7]: q (w, x, y, z), t */, uint32_t* status_out_or_null /* [n_poses] */,
                           uint32_t* evals_out_or_null /* [n_poses] */);
+
+/* ---- flexible refinement: the same descent with the ligand's torsion angles as further coordinates -------------------------------
+ * Preconditions, refusals, the treatment of the handle, the status values, MDX_REFINE_MAX_EVALS_CAP, the defaults of h_start and h_max
+ * and the chunks of 256 poses are those of mdx_refine_poses; a refused call writes nothing, and a pose gives the same bits alone or in
+ * a batch of any size, at any place in it.  With n_torsions == 0 and flags == 0 every shared output is bit for bit what
+ * mdx_refine_poses returns.
+ *
+ * Torsions.  The ligand's bond graph is the bonds and constraints given at creation that lie inside the range.  Torsion k names a
+ * bond {a, b} (ligand-local indices); removing it must split the ligand in two, and the part without `root` is the moving set M_k,
+ * b_k its end of the bond, a_k the other.  The sets are then nested or disjoint, so dY/dtheta_k is a rigid rotation of M_k about the
+ * axis as it finally stands.  MDX_EPARAM also for (mdx_last_error names the torsion): n_torsions > MDX_POSE_MAX_TORSIONS;
+ * torsion_bonds NULL with n_torsions > 0; root >= count; an index >= count; a == b; the pair is not bonded; a bond listed twice;
+ * removing the bond leaves a and b connected (a ring bond); M_k or its complement is a single atom (a leaf bond); the range's bond
+ * graph is not connected (asked only where n_torsions > 0); tors_tol negative or not finite; unknown flag bits.
+ *
+ * The stepper is the rigid one with these additions (fp64, atoms in order, then torsions in order; theta = 0 at the start):
+ *   coords      B(theta) = X0 in fp64 with the torsions applied in caller order, each a Rodrigues rotation of M_k by theta_k about the
+ *               unit axis u from a_k to b_k of the coordinates as they then stand: p <- b + r cos + (u x r) sin + u (u . r)(1 - cos),
+ *               r = p - b; theta_k == 0 (and an axis of zero length) is skipped.  b_i = B_i - mean(B), coords(q, t, theta)_i =
+ *               fp32(c0 + t + R(q) b_i): every trial is an image of the INPUT, rounded once, and with theta = 0 it is coords(q, t) bit for bit.
+ *   evaluation  r, the fp32 forces f_i^nb and rigid as in mdx_refine_poses.  With MDX_FLEX_DIHEDRALS (and without
+ *               MDX_OVR_BONDED_DISABLED) E_dih = fp32(sum over the dihedral terms inside the range, in the system's list order, of
+ *               v (1 + cos(n phi - phase))), in fp64 of the fp32 trial, phi = atan2((B x A) . G / |G|, A . B) with F = x0 - x1,
+ *               G = x1 - x2, H = x3 - x2 (minimum image), A = F x G, B = H x G; a term with |A|^2 or |B|^2 < 1e-24 or |G| < 1e-12 is left
+ *               out.  f_i^dih = the fp64 force of those terms on atom i, the terms that name i in list order.  Otherwise both are 0.
+ *               S = sum_b (double) r[b] + (double) E_dih, f_i = (double) f_i^nb + f_i^dih.  A non-finite E_dih or f^dih counts as non-finite.
+ *               Accept, reject, stall and the growth of h are unchanged.
+ *   direction   v, omega, c, r_i, I as before (the dihedral forces carry no net force or torque).  Per torsion, of the accepted Y:
+ *               u_k = (Y_b - Y_a) / |Y_b - Y_a|, arm_ki = u_k x (Y_i - Y_b) for i in M_k, g_k = sum_{i in M_k} arm_ki . (f_i - v)
+ *               = -dS/dtheta_k (the -v pays for the recentring), J_k = sum_{i in M_k} |arm_ki|^2, omega_k = g_k / (J_k + 1e-6 J_k + 1e-12).
+ *               u_i = v + omega x r_i + sum_k ([i in M_k] omega_k arm_ki - (1/n) omega_k sum_{j in M_k} arm_kj), m = max_i |u_i|.
+ *   converged   |rigid[0:3]| <= f_tol, |rigid[3:6]| <= tau_tol and max_k |g_k| <= tors_tol (kcal/mol/rad), or m == 0.
+ *   next trial  s = h / m; t_try, q_try as before; theta_try,k = theta_k + s omega_k.
+ * Outputs of the accepted state: poses_out, rows_out, rigid_out, status, evals as in mdx_refine_poses; xform_out[p] = (q, t, theta)
+ * rounded to fp32; dih_out[p] = E_dih; tgrad_out[p][k] = fp32(g_k).  Not part of it: ring flexibility, bond and angle terms (constant
+ * under torsion moves), other directions than steepest descent, decomposed handles, alchemical windows, ligands above 256 atoms. */
+#define MDX_POSE_MAX_TORSIONS 32
+#define MDX_FLEX_DIHEDRALS 1u     /* flags: add the ligand's dihedral terms to the objective and the gradient */
+typedef struct { uint32_t max_evals; float f_tol, tau_tol, tors_tol, h_start, h_max; uint32_t flags; } mdx_flex_opts;
+int      mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses /* [n_poses][count][3] */,
+                               uint32_t root, uint32_t n_torsions, const uint32_t* torsion_bonds /* [n_torsions][2], ligand-local */,
+                               const mdx_flex_opts* opts, float* poses_out /* [n_poses][count][3] */,
+                               float* rows_out_or_null /* [n_poses][n_groups] */, uint32_t n_groups, float* rigid_out_or_null /* [n_poses][6] */,
+                               float* xform_out_or_null /* [n_poses][7 + n_torsions]: q, t, theta */, float* dih_out_or_null /* [n_poses] */,
+                               float* tgrad_out_or_null /* [n_poses][n_torsions] */, uint32_t* status_out_or_null /* [n_poses] */,
+                               uint32_t* evals_out_or_null /* [n_poses] */);
 
 /* ---- multi-GPU: one periodic box spatially decomposed over the GPUs of a node (the reference is
  * single-device, src/util.rs:1086 `CudaContext::new(0)`, so this is new capability, not parity) -------------------

@@ -199,6 +199,28 @@ public:
                                r.status.data(), r.evals.data()));
         return r;
     }
+    /// mdx_refine_poses_flex: the same descent with the ligand's torsion angles as further coordinates.  torsion_bonds holds pairs of
+    /// ligand-local atoms, each a bond whose removal splits the ligand; the side without `root` turns.
+    struct FlexRefinedPoses {
+        std::vector<float> poses, rows, rigid, xform;      ///< as RefinedPoses; xform [n][7 + n_torsions] = q, t, torsion angles (rad)
+        std::vector<float> dih, tgrad;                     ///< [n] dihedral energy, [n][n_torsions] -dS/dtheta - of the accepted state
+        std::vector<uint32_t> status, evals;
+    };
+    FlexRefinedPoses refine_poses_flex(uint32_t first, uint32_t count, const std::vector<float>& poses, uint32_t root,
+                                       const std::vector<uint32_t>& torsion_bonds, const mdx_flex_opts& opts) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        if (count == 0 || poses.size() % (3 * (size_t)count) != 0) throw std::invalid_argument("refine_poses_flex: poses must hold [n_poses][count][3] floats");
+        if (torsion_bonds.size() % 2 != 0) throw std::invalid_argument("refine_poses_flex: torsion_bonds must hold [n_torsions][2] atom indices");
+        const uint32_t n = (uint32_t)(poses.size() / (3 * (size_t)count)), t = (uint32_t)(torsion_bonds.size() / 2);
+        FlexRefinedPoses r;
+        r.poses.assign(poses.size(), 0.f); r.rows.assign((size_t)n * g, 0.f); r.rigid.assign((size_t)n * 6, 0.f);
+        r.xform.assign((size_t)n * (7 + t), 0.f); r.dih.assign(n, 0.f); r.tgrad.assign((size_t)n * t, 0.f);
+        r.status.assign(n, 0u); r.evals.assign(n, 0u);
+        check(mdx_refine_poses_flex(h_, first, count, n, poses.data(), root, t, t ? torsion_bonds.data() : nullptr, &opts, r.poses.data(),
+                                    r.rows.data(), g, r.rigid.data(), r.xform.data(), r.dih.data(), r.tgrad.data(), r.status.data(),
+                                    r.evals.data()));
+        return r;
+    }
 
     /// `md.cell = SimBox::new(lo, hi)` + `md.rebuild_spatial_caches()` (sol_shrinking_box.rs:600-603, 632).
     void set_cell(const SimBox& b) { check(mdx_set_box(h_, b.bounds_low.data(), b.bounds_high.data())); }

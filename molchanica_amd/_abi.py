@@ -27,6 +27,8 @@ POS, VEL, FORCE = 0, 1, 2
 POSE_MAX_ATOMS = 256   # MDX_POSE_MAX_ATOMS: the largest ligand mdx_score_poses takes
 REFINE_CONVERGED, REFINE_MAX_EVALS, REFINE_STALLED, REFINE_NONFINITE = 0, 1, 2, 3      # MDX_REFINE_*: status of a refined pose
 REFINE_MAX_EVALS_CAP = 4096      # MDX_REFINE_MAX_EVALS_CAP
+POSE_MAX_TORSIONS = 32           # MDX_POSE_MAX_TORSIONS: the most torsions mdx_refine_poses_flex takes
+FLEX_DIHEDRALS = 0x1             # MDX_FLEX_DIHEDRALS
 
 _fp = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
@@ -67,6 +69,12 @@ class CConfig(C.Structure):
 class CRefineOpts(C.Structure):
     """mdx_refine_opts"""
     _fields_ = [("max_evals", C.c_uint32), ("f_tol", C.c_float), ("tau_tol", C.c_float), ("h_start", C.c_float), ("h_max", C.c_float)]
+
+
+class CFlexOpts(C.Structure):
+    """mdx_flex_opts"""
+    _fields_ = [("max_evals", C.c_uint32), ("f_tol", C.c_float), ("tau_tol", C.c_float), ("tors_tol", C.c_float), ("h_start", C.c_float),
+                ("h_max", C.c_float), ("flags", C.c_uint32)]
 
 
 class CEnergies(C.Structure):

@@ -290,6 +290,9 @@ struct DeviceState {
     double* ps_fslab = nullptr; float* ps_fout = nullptr; float* ps_rigid = nullptr;
     // mdx_refine_poses: frozen words, state records, accepted coordinates / rows / rigid and the input poses of one chunk (RefineLayout)
     void* ps_refine = nullptr;
+    // mdx_refine_poses_flex: the same block with the flexible state records and the per-term dihedral energies (FlexLayout); the table of
+    // one torsion list: moving-set masks, the ligand's dihedral terms and the per-atom lists into them (FlexTable)
+    void* ps_flex = nullptr; void* ps_flex_tab = nullptr;
 };
 
 struct MdxDecomp;   // mdx_comm.h: the handle is one rank of a spatially decomposed box
@@ -357,6 +360,9 @@ struct mdx_handle {
     // mdx_score_poses (mdx_poses.hip): the range and the group map the intra-ligand table was built for, its group, its 1-4 records
     bool ps_valid = false; uint32_t ps_first = 0, ps_count = 0, ps_group = 0, ps_n14 = 0; uint64_t ps_epoch = 0;
     size_t ps_cap_stage = 0, ps_cap_slab = 0, ps_cap_fslab = 0, ps_cap_refine = 0;
+    // mdx_refine_poses_flex: what ps_flex_tab was built for (with ps_first / ps_count / ps_epoch) and how many dihedral terms it holds
+    bool fx_valid = false; uint32_t fx_first = 0, fx_count = 0, fx_root = 0, fx_flags = 0, fx_terms = 0; uint64_t fx_epoch = 0;
+    std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0;
     bool alch_on = false; double alch_lambda = 0.0; uint32_t alch_lo = 0, alch_hi = 0;
     float sc_alpha = 0.5f, sc_sigma_min = 3.0f;   // soft core of the alchemical window (mdx_set_alchemical_softcore)
     std::vector<double> foreign_lams;             // mdx_set_foreign_lambdas (survives window changes; empty: none)
@@ -458,6 +464,7 @@ struct mdx_handle {
     std::vector<uint8_t> hb_heavy; float hb_dmax = 2.5f, hb_angle_min = 120.f;
     std::vector<uint32_t> hb_donor_of;   // [N] heavy atom a hydrogen is bound to (MDX_INVALID: not a donor hydrogen)
     std::vector<uint32_t> h_bond_pairs;  // bonds + constraints as given at creation (pairs), for the donor table
+    std::vector<uint32_t> h_dih_idx; std::vector<float> h_dih_v, h_dih_phase; std::vector<int32_t> h_dih_n;   // dihedral terms as given at creation, in list order (mdx_refine_poses_flex)
     std::vector<Snapshot> snapshots;
     DeviceState d;
     StepCtl* h_ctl = nullptr;  // pinned (+ 64 bytes: the sequence word of the chunk-end readback)

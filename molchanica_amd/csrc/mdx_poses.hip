@@ -47,6 +47,7 @@
 #include "mdx_bonded_dev.h"
 #include "mdx_pair_dev.h"
 #include "mdx_refine_step.h"
+#include "mdx_flex_step.h"
 #include <cmath>
 #include <cstring>
 
@@ -747,6 +748,397 @@ extern "C" int mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, u
     if (rows_out_or_null) std::memcpy(rows_out_or_null, rres.data(), sizeof(float) * rres.size());
     if (rigid_out_or_null) std::memcpy(rigid_out_or_null, gres.data(), sizeof(float) * gres.size());
     if (xform_out_or_null) std::memcpy(xform_out_or_null, xres.data(), sizeof(float) * xres.size());
+    if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
+    if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
+    return MDX_OK;
+}
+
+// ---- mdx_refine_poses_flex: the same loop with the ligand's torsion angles as further coordinates (mdx_flex_step.h) ---------------------
+// The table of one (range, torsion list, flags): the torsions with their moving-set masks, the ligand's dihedral terms in the system's
+// list order, and per ligand atom the (term, role) entries that name it, in list order too - the atom-owned gather.
+struct FlexTable {
+    size_t tor, dih, aoff, aent, end;
+    FlexTable(uint32_t count, uint32_t n_terms) {
+        tor = 0;
+        dih = sizeof(mdx_fx_torsion) * MDX_FX_MAX_TORSIONS;
+        aoff = dih + sizeof(mdx_fx_dihedral) * n_terms;
+        aent = aoff + sizeof(uint32_t) * (count + 1u);
+        end = aent + sizeof(uint32_t) * 4u * (size_t)n_terms;
+    }
+};
+
+#define FLEX_TERM_WORDS 13u      // per dihedral term and evaluation: energy, then the forces on its four atoms
+
+struct FlexArgs {
+    uint32_t count, G, T, n_terms;
+    float* stage;
+    const double* slab; const double* fslab;
+    uint32_t* frozen; mdx_fx_state* st;
+    float* x0; float* y; float* row; float* rigid;
+    double* eterm;                 // [poses of the chunk][n_terms][13]: energy and the four atoms' forces of every term at this evaluation
+    const mdx_fx_torsion* tor; const mdx_fx_dihedral* dih; const uint32_t* aoff; const uint32_t* aent;
+    double box[3];                 // periodic axes (0: none), as the force pass has them
+    mdx_fx_opts o;
+};
+
+// One evaluation of every live pose ends here.  Up to the decision this is pose_refine_step_kernel statement by statement; added are the
+// dihedral gather (thread i: the terms that name atom i, in list order; the terms' energies go through eterm and are added by one thread
+// in list order), g_k / J_k (thread k, members in atom order), the torsion part of the atom field, and the trial builder: B(theta) in LDS
+// with one barrier per non-zero torsion, then the rigid image of it.
+__global__ __launch_bounds__(256) void pose_flex_step_kernel(FlexArgs a) {
+    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_f[MDX_POSE_MAX_ATOMS][3], s_c[3], s_I[6], s_R[9], s_m[4];
+    __shared__ double s_g[MDX_FX_MAX_TORSIONS], s_J[MDX_FX_MAX_TORSIONS], s_A[MDX_FX_MAX_TORSIONS][3], s_u[MDX_FX_MAX_TORSIONS][3],
+                      s_sh[MDX_FX_MAX_TORSIONS][3], s_wk[MDX_FX_MAX_TORSIONS], s_cs[MDX_FX_MAX_TORSIONS], s_sn[MDX_FX_MAX_TORSIONS], s_bc[3];
+    __shared__ float s_row[256], s_rigid[6], s_edih;
+    __shared__ mdx_fx_state s_st;
+    __shared__ mdx_fx_torsion s_tor[MDX_FX_MAX_TORSIONS];
+    __shared__ uint32_t s_bad, s_flags;
+    const uint32_t tid = threadIdx.x, pose = blockIdx.x, count = a.count, T = a.T;
+    if (a.frozen[pose] != 0u) return;      // (uniform over the workgroup, before any barrier)
+    {
+        const uint32_t* src = (const uint32_t*)(a.st + pose);
+        for (uint32_t i = tid; i < sizeof(mdx_fx_state) / 4u; i += 256u) ((uint32_t*)&s_st)[i] = src[i];
+        for (uint32_t i = tid; i < T * (uint32_t)(sizeof(mdx_fx_torsion) / 4u); i += 256u) ((uint32_t*)s_tor)[i] = ((const uint32_t*)a.tor)[i];
+    }
+    if (tid == 0u) s_bad = 0u;
+    __syncthreads();
+    bool bad = false;
+    if (tid < a.G) {
+        const double* s = a.slab + (size_t)pose * (POSE_UNITS + 1u) * a.G + tid;
+        double v = 0.0;
+        for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * a.G];
+        const float r = (float)v;
+        s_row[tid] = r;
+        bad = !isfinite(r);
+    }
+    const size_t at = ((size_t)pose * count + tid) * 3u;
+    if (tid < count) {
+        const double* s = a.fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
+        for (uint32_t c = 0; c < 3u; ++c) {
+            double v = 0.0;
+            for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * count * 3u + c];
+            s_v[tid][c] = v; s_x[tid][c] = (double)a.stage[at + c];
+            s_f[tid][c] = (double)(float)v;      // (the fp32 force mdx_pose_forces returns: what a host loop has)
+            bad = bad || !isfinite((float)v);
+        }
+    }
+    if (bad) s_bad = 1u;      // (every writer stores the same word)
+    __syncthreads();
+    if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
+    // the ligand's dihedral terms, one term per thread: its energy and its four forces go through eterm
+    double* eterm = a.eterm + (size_t)pose * a.n_terms * FLEX_TERM_WORDS;
+    const double box[3] = {a.box[0], a.box[1], a.box[2]};
+    for (uint32_t t = tid; t < a.n_terms; t += 256u) {
+        double f[4][3];
+        double* o = eterm + (size_t)t * FLEX_TERM_WORDS;
+        o[0] = fx_dihedral(&s_x[0][0], a.dih[t], box, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { o[1 + 3 * r] = f[r][0]; o[2 + 3 * r] = f[r][1]; o[3 + 3 * r] = f[r][2]; }
+    }
+    __syncthreads();
+    if (tid < 6u) s_rigid[tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
+    if (tid >= 64u && tid < 70u) s_I[tid - 64u] = rf_inertia(&s_x[0][0], count, s_c, tid - 64u);      // (a wave of its own, beside rigid)
+    if (tid == 128u) {      // the energies in list order
+        double e = 0.0;
+        for (uint32_t t = 0; t < a.n_terms; ++t) e += eterm[(size_t)t * FLEX_TERM_WORDS];
+        s_edih = (float)e;
+    }
+    if (tid < count && a.n_terms) {
+        // thread i: the forces of the terms that name atom i, in list order - the atom-owned gather
+        double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+        for (uint32_t e = a.aoff[tid]; e < a.aoff[tid + 1u]; ++e) {
+            const uint32_t w = a.aent[e];
+            const double* o = eterm + (size_t)(w >> 2) * FLEX_TERM_WORDS + 1u + 3u * (w & 3u);
+            f0 += o[0]; f1 += o[1]; f2 += o[2];
+        }
+        if (!isfinite(f0) || !isfinite(f1) || !isfinite(f2)) s_bad = 1u;
+        s_f[tid][0] += f0; s_f[tid][1] += f1; s_f[tid][2] += f2;
+    }
+    __syncthreads();
+    if (tid < T) {
+        const double n = (double)count;
+        const double v[3] = {(double)s_rigid[0] / n, (double)s_rigid[1] / n, (double)s_rigid[2] / n};
+        fx_gradient(&s_x[0][0], &s_f[0][0], count, v, s_tor[tid], s_u[tid], s_g[tid], s_J[tid], s_A[tid]);
+    }
+    __syncthreads();
+    if (tid == 0u) {
+        bool finite = s_bad == 0u && isfinite(s_edih);
+        for (int k = 0; k < 6; ++k) finite = finite && isfinite(s_rigid[k]);
+        double S = 0.0, gmax = 0.0;
+        for (uint32_t b = 0; b < a.G; ++b) S += (double)s_row[b];
+        S += (double)s_edih;
+        for (uint32_t k = 0; k < T; ++k) {
+            const double g = fabs(s_g[k]);
+            finite = finite && isfinite(g);
+            gmax = g > gmax ? g : gmax;
+        }
+        if (s_st.rf.evals == 0u) fx_start(s_st, s_c, a.o.rf.h_start);      // (the record was zeroed: the trial is the input pose)
+        const uint32_t fl = fx_decide(s_st, a.o, T, S, finite, s_rigid, gmax);
+        if (fl & MDX_RF_STORE) {
+            s_st.edih = s_edih;
+            for (uint32_t k = 0; k < T; ++k) s_st.g[k] = s_g[k];
+        }
+        if (fl == MDX_RF_STORE) rf_direction(s_st.rf, count, s_rigid, s_I);
+        s_flags = fl;
+    }
+    if (tid >= 64u && tid < 64u + T) {      // (a wave beside thread 0's: used only if the trial is stored and the pose goes on)
+        const uint32_t k = tid - 64u;
+        s_wk[k] = fx_omega(s_g[k], s_J[k]);
+        fx_shift(s_wk[k], s_A[k], count, s_sh[k]);
+    }
+    __syncthreads();
+    if (s_flags == MDX_RF_STORE && tid < T) s_st.wk[tid] = s_wk[tid];      // (read again only after the next barrier)
+    const bool first = s_st.rf.evals == 1u;
+    uint32_t fl = s_flags;
+    if (fl & MDX_RF_STORE) {
+        if (tid < count)
+            for (uint32_t c = 0; c < 3u; ++c) a.y[at + c] = a.stage[at + c];
+        if (tid < a.G) a.row[(size_t)pose * a.G + tid] = s_row[tid];
+        if (tid < 6u) a.rigid[(size_t)pose * 6u + tid] = s_rigid[tid];
+    }
+    if (first && tid < count)
+        for (uint32_t c = 0; c < 3u; ++c) a.x0[at + c] = a.stage[at + c];
+    if (fl == MDX_RF_STORE) {
+        // the largest atom speed of the new direction (a maximum: exact in any order)
+        double m = 0.0;
+        if (tid < count) m = fx_speed(s_st.rf.v, s_st.rf.w, s_c, &s_x[0][0], tid, T, s_tor, s_u, s_wk, s_sh);
+#pragma unroll
+        for (int k = 32; k > 0; k >>= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
+        if ((tid & 63u) == 0u) s_m[tid >> 6] = m;
+        __syncthreads();
+        if (tid == 0u) {
+            double mm = s_m[0];
+            for (int k = 1; k < 4; ++k) mm = s_m[k] > mm ? s_m[k] : mm;
+            s_flags = fl = fl | rf_set_speed(s_st.rf, mm);
+        }
+        __syncthreads();
+        fl = s_flags;
+    }
+    if (!(fl & MDX_RF_FROZEN)) {
+        if (tid == 0u) {
+            fx_trial(s_st, T);
+            rf_rotation(s_st.rf.qt, s_R);
+        }
+        // B(theta_try) from the input pose: s_x is free now
+        if (tid < count)
+            for (uint32_t c = 0; c < 3u; ++c) s_x[tid][c] = (double)a.x0[at + c];
+        __syncthreads();
+        if (tid < T) { s_cs[tid] = cos(s_st.tht[tid]); s_sn[tid] = sin(s_st.tht[tid]); }
+        __syncthreads();
+        for (uint32_t k = 0; k < T; ++k) {
+            const double th = s_st.tht[k];
+            if (th == 0.0) continue;      // (uniform over the workgroup)
+            const mdx_fx_torsion& t = s_tor[k];
+            double u[3];
+            const bool turns = fx_axis(&s_x[0][0], t, u);      // (atoms a and b: not written in this round)
+            if (turns && tid < count && tid != t.b && fx_member(t.mask, tid)) {
+                const double b[3] = {s_x[t.b][0], s_x[t.b][1], s_x[t.b][2]};
+                fx_rotate(u, b, s_cs[k], s_sn[k], s_x[tid]);
+            }
+            __syncthreads();
+        }
+        if (tid < 3u) s_bc[tid] = rf_mean(&s_x[0][0], count, tid);
+    }
+    __syncthreads();
+    {
+        uint32_t* dst = (uint32_t*)(a.st + pose);
+        for (uint32_t i = tid; i < sizeof(mdx_fx_state) / 4u; i += 256u) dst[i] = ((const uint32_t*)&s_st)[i];
+    }
+    if (fl & MDX_RF_FROZEN) {
+        if (tid == 0u) a.frozen[pose] = 1u;
+        return;
+    }
+    if (tid < count) {
+        float y[3];
+        fx_coords(s_st.rf.c0, s_st.rf.tt, s_R, s_x[tid], s_bc, y);
+        for (uint32_t c = 0; c < 3u; ++c) a.stage[at + c] = y[c];
+    }
+}
+
+// The flexible block of a chunk of n poses: RefineLayout with the larger state record, and the terms' energies behind it
+struct FlexLayout {
+    size_t frozen, state, y, row, rigid, x0, eterm, end;
+    FlexLayout(uint32_t n, size_t per_pose, uint32_t G, uint32_t n_terms) {
+        frozen = 0;
+        state = ((sizeof(uint32_t) * n + 15u) / 16u) * 16u;
+        y = state + sizeof(mdx_fx_state) * n;
+        row = y + sizeof(float) * per_pose * n;
+        rigid = row + sizeof(float) * (size_t)G * n;
+        x0 = rigid + sizeof(float) * 6u * n;
+        eterm = ((x0 + sizeof(float) * per_pose * n + 15u) / 16u) * 16u;
+        end = eterm + sizeof(double) * FLEX_TERM_WORDS * (size_t)n_terms * n;
+    }
+};
+
+// What can be refused of a torsion list on the host's copy of the topology alone: the range's bonds, the moving sides.  tor: [n_torsions]
+static int flex_graph(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t root, uint32_t n_torsions,
+                      const uint32_t* tb, std::vector<mdx_fx_torsion>& tor) {
+    std::vector<uint32_t> bonds;
+    for (size_t k = 0; k + 1 < h->h_bond_pairs.size(); k += 2) {
+        const uint32_t p = h->h_bond_pairs[k], q = h->h_bond_pairs[k + 1];
+        if (p >= first && p - first < count && q >= first && q - first < count) { bonds.push_back(p - first); bonds.push_back(q - first); }
+    }
+    tor.assign(MDX_FX_MAX_TORSIONS, mdx_fx_torsion{});
+    uint32_t bad = 0;
+    const int rc = fx_moving_sides(count, (uint32_t)(bonds.size() / 2), bonds.data(), root, n_torsions, tb, tor.data(), &bad);
+    const std::string t = who + ": torsion " + std::to_string(bad);
+    switch (rc) {
+    case MDX_FX_OK: return MDX_OK;
+    case MDX_FX_E_ROOT: FAIL(MDX_EPARAM, who + ": root must be an atom of the range (root < count)");
+    case MDX_FX_E_INDEX: FAIL(MDX_EPARAM, t + " names an atom index >= count");
+    case MDX_FX_E_SELF: FAIL(MDX_EPARAM, t + " names the same atom twice");
+    case MDX_FX_E_NOT_BONDED: FAIL(MDX_EPARAM, t + ": the two atoms are not bonded");
+    case MDX_FX_E_TWICE: FAIL(MDX_EPARAM, t + ": the bond is listed twice");
+    case MDX_FX_E_RING: FAIL(MDX_EPARAM, t + ": removing the bond leaves its ends connected (a ring bond)");
+    case MDX_FX_E_LEAF: FAIL(MDX_EPARAM, t + ": one side of the bond is a single atom (a leaf bond: the torsion moves nothing)");
+    default: FAIL(MDX_EPARAM, who + ": the bond graph of the range is not connected");
+    }
+}
+
+// The table on the device, once per (range, group epoch, root, torsion list, flags)
+static int flex_table(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t root, uint32_t n_torsions,
+                      const uint32_t* tb, uint32_t flags, const std::vector<mdx_fx_torsion>& tor) {
+    DeviceState& d = h->d;
+    const std::vector<uint32_t> key(tb, tb + 2 * (size_t)n_torsions);
+    if (h->fx_valid && h->fx_first == first && h->fx_count == count && h->fx_epoch == h->grp_epoch && h->fx_root == root &&
+        h->fx_flags == flags && h->fx_bonds == key) return MDX_OK;
+    h->fx_valid = false;
+    std::vector<mdx_fx_dihedral> dih;
+    const bool on = (flags & MDX_FLEX_DIHEDRALS) != 0u && (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) == 0u;
+    for (size_t k = 0; on && k < h->h_dih_v.size(); ++k) {
+        const uint32_t* at = h->h_dih_idx.data() + 4 * k;
+        uint32_t in = 0;
+        for (int r = 0; r < 4; ++r) in += (at[r] >= first && at[r] - first < count) ? 1u : 0u;
+        if (in == 0u) continue;
+        if (in != 4u) FAIL(MDX_EPARAM, who + ": a dihedral term links the range to an atom outside it");
+        dih.push_back(mdx_fx_dihedral{{at[0] - first, at[1] - first, at[2] - first, at[3] - first}, (double)h->h_dih_v[k],
+                                      (double)h->h_dih_phase[k], (double)h->h_dih_n[k]});
+    }
+    const uint32_t n_terms = (uint32_t)dih.size();
+    if (n_terms >= (1u << 30)) FAIL(MDX_EPARAM, who + ": too many dihedral terms in the range");
+    std::vector<uint32_t> aoff(count + 1u, 0u), aent(4u * (size_t)n_terms);
+    for (const mdx_fx_dihedral& t : dih)
+        for (int r = 0; r < 4; ++r) aoff[t.at[r] + 1u]++;
+    for (uint32_t i = 0; i < count; ++i) aoff[i + 1u] += aoff[i];
+    std::vector<uint32_t> cur(aoff.begin(), aoff.end() - 1);
+    for (uint32_t k = 0; k < n_terms; ++k)
+        for (uint32_t r = 0; r < 4u; ++r) aent[cur[dih[k].at[r]]++] = (k << 2) | r;
+    const FlexTable lay(count, n_terms);
+    std::vector<unsigned char> img(lay.end, 0);
+    std::memcpy(img.data() + lay.tor, tor.data(), sizeof(mdx_fx_torsion) * MDX_FX_MAX_TORSIONS);
+    if (n_terms) std::memcpy(img.data() + lay.dih, dih.data(), sizeof(mdx_fx_dihedral) * n_terms);
+    std::memcpy(img.data() + lay.aoff, aoff.data(), sizeof(uint32_t) * aoff.size());
+    if (n_terms) std::memcpy(img.data() + lay.aent, aent.data(), sizeof(uint32_t) * aent.size());
+    if (h->ps_cap_flex_tab < lay.end) {
+        if (d.ps_flex_tab) { (void)hipFree(d.ps_flex_tab); d.ps_flex_tab = nullptr; }
+        h->ps_cap_flex_tab = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_flex_tab, lay.end));
+        h->ps_cap_flex_tab = lay.end;
+    }
+    HIP_TRY(hipMemcpyAsync(d.ps_flex_tab, img.data(), lay.end, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->fx_valid = true; h->fx_first = first; h->fx_count = count; h->fx_epoch = h->grp_epoch; h->fx_root = root; h->fx_flags = flags;
+    h->fx_bonds = key; h->fx_terms = n_terms;
+    return MDX_OK;
+}
+
+extern "C" int mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, uint32_t root,
+                                     uint32_t n_torsions, const uint32_t* torsion_bonds, const mdx_flex_opts* opts, float* poses_out,
+                                     float* rows_out_or_null, uint32_t n_groups, float* rigid_out_or_null, float* xform_out_or_null,
+                                     float* dih_out_or_null, float* tgrad_out_or_null, uint32_t* status_out_or_null,
+                                     uint32_t* evals_out_or_null) {
+    const std::string who = "mdx_refine_poses_flex";
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_poses == 0) return MDX_OK;
+    if (!poses || !poses_out || !opts) FAIL(MDX_EPARAM, "null argument");
+    if (n_torsions > MDX_POSE_MAX_TORSIONS) FAIL(MDX_EPARAM, who + ": n_torsions exceeds MDX_POSE_MAX_TORSIONS (32)");
+    if (n_torsions && !torsion_bonds) FAIL(MDX_EPARAM, who + ": null torsion_bonds with n_torsions > 0");
+    if (opts->max_evals == 0 || opts->max_evals > MDX_REFINE_MAX_EVALS_CAP) FAIL(MDX_EPARAM, who + ": max_evals must be in 1..MDX_REFINE_MAX_EVALS_CAP (4096)");
+    for (float v : {opts->f_tol, opts->tau_tol, opts->tors_tol, opts->h_start, opts->h_max})
+        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": a tolerance or step length is negative or not finite");
+    if (opts->flags & ~MDX_FLEX_DIHEDRALS) FAIL(MDX_EPARAM, who + ": unknown flag bits");
+    mdx_fx_opts o{{(double)opts->f_tol, (double)opts->tau_tol, opts->h_start > 0.f ? (double)opts->h_start : 0.01,
+                   opts->h_max > 0.f ? (double)opts->h_max : 0.2}, (double)opts->tors_tol};
+    if (o.rf.h_start > o.rf.h_max) FAIL(MDX_EPARAM, who + ": h_start exceeds h_max");
+    // the torsion list against the host's copy of the bonds - once the range itself has passed the checks pose_setup opens with
+    if (count == 0 || count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, who + ": count must be in 1..MDX_POSE_MAX_ATOMS (256)");
+    if ((uint64_t)first + count > h->N) FAIL(MDX_EPARAM, "atom range out of bounds");
+    std::vector<mdx_fx_torsion> tor;
+    MDX_TRY(flex_graph(h, who, first, count, root, n_torsions, torsion_bonds, tor));
+    PoseArgs a{};
+    int mode = 0; bool geom = false;
+    MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, true, a, mode, geom));
+    MDX_TRY(flex_table(h, who, first, count, root, n_torsions, torsion_bonds, opts->flags, tor));
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t G = h->n_grp, T = n_torsions, n_terms = h->fx_terms;
+    const size_t per_pose = 3 * (size_t)count;
+    const size_t need = FlexLayout(POSE_CHUNK, per_pose, G, n_terms).end;
+    if (h->ps_cap_flex < need) {
+        if (d.ps_flex) { (void)hipFree(d.ps_flex); d.ps_flex = nullptr; }
+        h->ps_cap_flex = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_flex, need));
+        h->ps_cap_flex = need;
+    }
+    const uint32_t X = 7u + T;
+    std::vector<float> yres(per_pose * n_poses), rres((size_t)n_poses * G), gres(6u * (size_t)n_poses), xres((size_t)X * n_poses),
+        dres(n_poses), tres((size_t)T * n_poses);
+    std::vector<uint32_t> sres(n_poses), eres(n_poses);
+    std::vector<unsigned char> back;
+    const FlexTable tab(count, n_terms);
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
+        const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
+        const FlexLayout lay(n, per_pose, G, n_terms);
+        unsigned char* blk = (unsigned char*)d.ps_flex;
+        const unsigned char* tb = (const unsigned char*)d.ps_flex_tab;
+        FlexArgs r{};
+        r.count = count; r.G = G; r.T = T; r.n_terms = n_terms; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
+        r.frozen = (uint32_t*)(blk + lay.frozen); r.st = (mdx_fx_state*)(blk + lay.state);
+        r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
+        r.eterm = (double*)(blk + lay.eterm);
+        r.tor = (const mdx_fx_torsion*)(tb + tab.tor); r.dih = (const mdx_fx_dihedral*)(tb + tab.dih);
+        r.aoff = (const uint32_t*)(tb + tab.aoff); r.aent = (const uint32_t*)(tb + tab.aent);
+        for (int k = 0; k < 3; ++k) r.box[k] = (double)a.box[k];
+        r.o = o;
+        a.frozen = r.frozen;
+        HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(blk, 0, lay.y, st));
+        mdx_prof_begin(h, 0);
+        for (uint32_t k = 0; k < opts->max_evals; ++k) {
+            switch (mode) {
+            case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, true, true); break;
+            case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, true, true); break;
+            case CM_RF: launch_poses<CM_RF>(h, a, geom, n, true, true); break;
+            default: launch_poses<CM_EWALD>(h, a, geom, n, true, true); break;
+            }
+            hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, st, r);
+        }
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        back.resize(lay.x0 - lay.state);
+        HIP_TRY(hipMemcpyAsync(back.data(), blk + lay.state, back.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const unsigned char* b0 = back.data() - lay.state;
+        std::memcpy(yres.data() + per_pose * p0, b0 + lay.y, sizeof(float) * per_pose * n);
+        std::memcpy(rres.data() + (size_t)p0 * G, b0 + lay.row, sizeof(float) * (size_t)G * n);
+        std::memcpy(gres.data() + 6u * (size_t)p0, b0 + lay.rigid, sizeof(float) * 6u * n);
+        for (uint32_t k = 0; k < n; ++k) {
+            const mdx_fx_state* s = (const mdx_fx_state*)(b0 + lay.state + sizeof(mdx_fx_state) * k);
+            sres[p0 + k] = s->rf.frozen ? s->rf.status : MDX_REFINE_MAX_EVALS;
+            eres[p0 + k] = s->rf.evals;
+            float* x = xres.data() + (size_t)X * (p0 + k);
+            for (int c = 0; c < 4; ++c) x[c] = (float)s->rf.q[c];
+            for (int c = 0; c < 3; ++c) x[4 + c] = (float)s->rf.t[c];
+            for (uint32_t c = 0; c < T; ++c) { x[7u + c] = (float)s->th[c]; tres[(size_t)T * (p0 + k) + c] = (float)s->g[c]; }
+            dres[p0 + k] = s->edih;
+        }
+    }
+    std::memcpy(poses_out, yres.data(), sizeof(float) * yres.size());
+    if (rows_out_or_null) std::memcpy(rows_out_or_null, rres.data(), sizeof(float) * rres.size());
+    if (rigid_out_or_null) std::memcpy(rigid_out_or_null, gres.data(), sizeof(float) * gres.size());
+    if (xform_out_or_null) std::memcpy(xform_out_or_null, xres.data(), sizeof(float) * xres.size());
+    if (dih_out_or_null) std::memcpy(dih_out_or_null, dres.data(), sizeof(float) * dres.size());
+    if (tgrad_out_or_null && T) std::memcpy(tgrad_out_or_null, tres.data(), sizeof(float) * tres.size());
     if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
     if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
     return MDX_OK;

@@ -17,8 +17,8 @@ import os
 
 import numpy as np
 
-from ._abi import (CCommDiag, CHBond, CConfig, CEnergies, CRefineOpts, CStats, CSystem, FORCE, MDX_EDEVICE, MDX_ENAN, MDX_EOOM,
-                   MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, VEL, MdConfig, MdSystem)
+from ._abi import (CCommDiag, CFlexOpts, CHBond, CConfig, CEnergies, CRefineOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, MDX_EDEVICE,
+                   MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, VEL, MdConfig, MdSystem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDX_LIB") or os.path.join(_HERE, "libmdx.so")   # MDX_LIB: A/B builds of the same ABI
@@ -172,6 +172,8 @@ def load_library():
     lib.mdx_pose_forces.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, _fp, C.c_uint32, _fp, _fp]
     lib.mdx_refine_poses.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, C.POINTER(CRefineOpts), _fp, _fp, C.c_uint32, _fp, _fp,
                                      _u32p, _u32p]
+    lib.mdx_refine_poses_flex.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _u32p, C.POINTER(CFlexOpts), _fp,
+                                          _fp, C.c_uint32, _fp, _fp, _fp, _fp, _u32p, _u32p]
     _lib = lib
     return lib
 
@@ -345,6 +347,49 @@ class MdState:
                                     r.ctypes.data_as(_fp), n, t.ctypes.data_as(_fp), x.ctypes.data_as(_fp), st.ctypes.data_as(_u32p),
                                     ev.ctypes.data_as(_u32p)))
         return y, (r[:, :n] if n else r[:, :0]), t, x, st, ev
+
+    def refine_poses_flex(self, first: int, poses, root: int, torsion_bonds, max_evals: int, f_tol: float, tau_tol: float, tors_tol: float,
+                          h_start: float = 0.0, h_max: float = 0.0, dihedrals: bool = True):
+        """`mdx_refine_poses_flex`: refine_poses() with the ligand's torsion angles as further coordinates (include/mdx.h states the
+        stepper).  torsion_bonds: integer [T, 2], ligand-local atom pairs, T <= POSE_MAX_TORSIONS - each a bond whose removal splits the
+        ligand; the side without `root` turns.  tors_tol kcal/mol/rad bounds the torsion gradient of a converged pose; dihedrals: the
+        ligand's dihedral terms are part of the objective and the gradient.
+        -> (poses_out, rows, rigid, xform [P, 7 + T] f32: quaternion, translation, torsion angles (rad), dih [P] f32: the dihedral
+        energy, tgrad [P, T] f32: -dS/dtheta, status, evals), all of the accepted state.  The handle is left as it is."""
+        if not isinstance(poses, np.ndarray) or poses.dtype != np.float32:
+            raise ParamError("refine_poses_flex: poses must be a float32 ndarray [P, count, 3]")
+        if poses.ndim != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= POSE_MAX_ATOMS:
+            raise ParamError(f"refine_poses_flex: poses must have shape [P, count, 3] with 1 <= count <= {POSE_MAX_ATOMS}, got {poses.shape}")
+        if int(first) < 0 or int(first) + poses.shape[1] > self.n_atoms:
+            raise ParamError("refine_poses_flex: atom range out of bounds")
+        tb = np.asarray(torsion_bonds)
+        if tb.size == 0:
+            tb = np.zeros((0, 2), np.uint32)
+        if tb.dtype.kind not in "iu" or tb.ndim != 2 or tb.shape[1] != 2 or tb.shape[0] > POSE_MAX_TORSIONS:
+            raise ParamError(f"refine_poses_flex: torsion_bonds must be integers [T, 2] with T <= {POSE_MAX_TORSIONS}")
+        if (tb < 0).any() or (tb >= poses.shape[1]).any() or not 0 <= int(root) < poses.shape[1]:
+            raise ParamError("refine_poses_flex: root and torsion_bonds are ligand-local atom indices (< count)")
+        lib = load_library()
+        a = np.ascontiguousarray(poses)
+        tb = np.ascontiguousarray(tb, dtype=np.uint32)
+        T = tb.shape[0]
+        n = int(lib.mdx_energy_group_count(self._h))
+        P = a.shape[0]
+        opts = CFlexOpts(int(max_evals), float(f_tol), float(tau_tol), float(tors_tol), float(h_start), float(h_max),
+                         FLEX_DIHEDRALS if dihedrals else 0)
+        y = np.zeros(a.shape, dtype=np.float32)
+        r = np.zeros((P, max(n, 1)), dtype=np.float32)
+        t = np.zeros((P, 6), dtype=np.float32)
+        x = np.zeros((P, 7 + T), dtype=np.float32)
+        e = np.zeros(P, dtype=np.float32)
+        g = np.zeros((P, max(T, 1)), dtype=np.float32)
+        st = np.zeros(P, dtype=np.uint32)
+        ev = np.zeros(P, dtype=np.uint32)
+        _check(lib.mdx_refine_poses_flex(self._h, int(first), a.shape[1], P, a.ctypes.data_as(_fp), int(root), T, tb.ctypes.data_as(_u32p),
+                                         C.byref(opts), y.ctypes.data_as(_fp), r.ctypes.data_as(_fp), n, t.ctypes.data_as(_fp),
+                                         x.ctypes.data_as(_fp), e.ctypes.data_as(_fp), g.ctypes.data_as(_fp), st.ctypes.data_as(_u32p),
+                                         ev.ctypes.data_as(_u32p)))
+        return y, (r[:, :n] if n else r[:, :0]), t, x, e, g[:, :T], st, ev
 
     # -- position restraints (include/mdx.h: E = k max(0, |x - r0| - b)^2) ------------------------------------------------
     def set_position_restraints(self, idx, ref=None, k=1.0, flat_bottom=None):
