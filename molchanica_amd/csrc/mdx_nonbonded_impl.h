@@ -204,10 +204,12 @@ __global__ __launch_bounds__(NB_WAVES * 64) void nb_tile_kernel(NbArgs a) {
 // HALF = true (variant 5) walks a half list: a cluster pair lives in ONE tile's list, the force on
 // the i-atoms accumulates in registers as before and the reaction on the eight j-atoms of an entry
 // is summed over the eight i-lanes with three DPP steps and leaves as ONE 24-lane f32 atomic
-// (x, y, z of 8 consecutive float4 records = 128 contiguous bytes).  Measured on gfx950
-// (tools/ubench/atomic_jforce.hip, atomic_flush.hip): the L2 retires ~250 G f32 atomic words/s, so the
-// 88 M words of a 1 M-atom half list need 0.35 ms of it - hidden behind 0.6 ms of arithmetic as long
-// as no instruction shape hits the same 128-B line twice in a row (x, then y, then z of the same
+// (x, y, z of 8 consecutive float4 records = 128 contiguous bytes).  The budget of these atomics is REQUESTS, not words: gfx950
+// executes an f32 atomic at the memory side and every wave-instruction leaves L2 as one uncached 64-B request per 64-B segment it
+// touches, at ~1.3 TB/s of requests chip-wide.  A 1 M-atom inner walk issues 2.33 M entry atomics of two segments each (298 MB) plus
+// the tiles' i-force write-back, 361 MB in all before the write-back was shaped to its rows (iforce_add_rows: 16 requests per unit
+// instead of 48) and 316 MB since: 0.24 ms at the full rate beside ~0.3 ms of VALU issue, the two floors level.
+// No instruction shape may hit the same 128-B line twice in a row (x, then y, then z of the same
 // atoms is 3x slower).  Measured and rejected: collecting a chunk's j-forces in LDS and flushing
 // them once per chunk (NB_HALF_FLUSH=1: 0.79 vs 0.66 ms, it needs 137 VGPRs = 3 waves/SIMD);
 // any form of LDS look-ahead of the next entry's j record (+6..8 %, both kernels).
@@ -627,6 +629,8 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
         if (jj == ci) { ox = x; oy = y; oz = z; }
     }
     float* const fi = fbase + (size_t)(t * MDX_TILE + lane) * 4;
+    // (the one-launch-per-step bodies keep the strided form: two of them, at 128 VGPRs, would pay for the strip's round trip with scratch)
+    constexpr bool IFORCE_ROWS = HALF && NB_IFORCE_ROWS && !STEP;
     if (prune && t_ok) {
         // pad the last compacted chunk with null entries (imask 0), publish this wave's loop bound
         const uint32_t nfull = (wcur + 7u) >> 3;
@@ -664,11 +668,14 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
             ox = s_red[w0][0][lane]; oy = s_red[w0][1][lane]; oz = s_red[w0][2][lane];
 #pragma unroll
             for (int w = 1; w < (SPLIT > 1 ? BW : WPT); ++w) { ox += s_red[w0 + w][0][lane]; oy += s_red[w0 + w][1][lane]; oz += s_red[w0 + w][2][lane]; }
-            if (HALF) { unsafeAtomicAdd(fi, ox); unsafeAtomicAdd(fi + 1, oy); unsafeAtomicAdd(fi + 2, oz); }
+            // (HALF: the tile's rows as four contiguous 256-B atomics through this wave's own strip, mdx_pair_dev.h iforce_add_rows)
+            if (IFORCE_ROWS) iforce_add_rows(fbase + (size_t)t * (MDX_TILE * 4), sx, lane, ox, oy, oz);
+            else if (HALF) { unsafeAtomicAdd(fi, ox); unsafeAtomicAdd(fi + 1, oy); unsafeAtomicAdd(fi + 2, oz); }
             else a.force[t * MDX_TILE + lane] = make_float4(ox, oy, oz, 0.f);
         }
     } else {
-        if (HALF) { unsafeAtomicAdd(fi, ox); unsafeAtomicAdd(fi + 1, oy); unsafeAtomicAdd(fi + 2, oz); }
+        if (IFORCE_ROWS) iforce_add_rows(fbase + (size_t)t * (MDX_TILE * 4), sx, lane, ox, oy, oz);
+        else if (HALF) { unsafeAtomicAdd(fi, ox); unsafeAtomicAdd(fi + 1, oy); unsafeAtomicAdd(fi + 2, oz); }
         else a.force[t * MDX_TILE + lane] = make_float4(ox, oy, oz, 0.f);
     }
     if (ENERGY) {

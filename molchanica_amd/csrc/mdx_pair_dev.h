@@ -40,6 +40,27 @@ __device__ __forceinline__ float jforce_reduce8(const float g[3], const bool sel
     return v;
 }
 
+#ifndef NB_IFORCE_ROWS
+#define NB_IFORCE_ROWS 1      // 1: a half-list tile's i-forces leave as four contiguous 256-B atomics (iforce_add_rows); 0: three strided ones
+#endif
+
+// The half list's i-force write-back: lane = atom of the tile, (ox, oy, oz) its force, `rows` the tile's 64 float4 force rows (1 KiB).
+// Written as rows + 4 lane + {0, 1, 2}, each of the three atomics touches all sixteen 64-B segments of the rows: 48 memory-side
+// requests for 16 segments of data.  Here the wave parks (ox, oy, oz, 0) in its position strip - free once the chunk loop is done - and
+// lane l of instruction k adds word 64 k + l of the strip to word 64 k + l of the rows: four instructions of 256 contiguous bytes, 16
+// requests.  Lanes with (l & 3) == 3 sit on the .w words and stay off: .w is not this kernel's to touch (STEP keeps a weight there).
+// The same addends reach the same words.  Call it wave-uniformly, behind a WAVE_LDS_SYNC (or a barrier) that ends the strip's last use.
+__device__ __forceinline__ void iforce_add_rows(float* __restrict__ rows, float4* strip, const int lane, const float ox, const float oy, const float oz) {
+    strip[lane] = make_float4(ox, oy, oz, 0.f);
+    WAVE_LDS_SYNC();
+    const float* const w = reinterpret_cast<const float*>(strip);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float v = w[k * 64 + lane];
+        if ((lane & 3) != 3) unsafeAtomicAdd(rows + k * 64 + lane, v);
+    }
+}
+
 struct NbArgs {
     uint32_t T;
     const float4* posq; const float2* lj;
