@@ -665,6 +665,55 @@ int      mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t count, ui
                                float* tgrad_out_or_null /* [n_poses][n_torsions] */, uint32_t* status_out_or_null /* [n_poses] */,
                                uint32_t* evals_out_or_null /* [n_poses] */);
 
+/* ---- pose search: per walker an iterated local search around the flexible refinement - perturb, refine, accept or reject, keep the best --
+ * What a host loop of one mdx_refine_poses_flex call per round with the move and the decision below would produce, without its round
+ * trips: per chunk of 256 walkers the library enqueues n_rounds x (1 + 2 max_evals) + 1 launches and waits once.  Preconditions,
+ * refusals and the treatment of the handle are those of mdx_refine_poses_flex with opts->refine as its options (the handle is not
+ * changed; a refused call writes nothing); n_walkers == 0 succeeds and does nothing.  MDX_EPARAM also for: starts, best_out or opts NULL;
+ * n_rounds == 0 or > MDX_SEARCH_MAX_ROUNDS; n_rounds x max_evals > 65536 (the launch queue); trans_amp, rot_amp, tors_amp or kT negative
+ * or not finite; tors_amp > pi; no move enabled (every amplitude 0, or only tors_amp > 0 with n_torsions == 0).
+ *
+ * Random numbers.  Walker w has a 64-bit stream id: streams[w], or w itself where streams is NULL.  Round r of the walker owns one
+ * splitmix64 stream (state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB;
+ * output z ^ z >> 31) whose start state is s0 = M(M(M(seed) ^ id) ^ r), M(x) = the output of one step from state x.  u01 = ((x >> 11) +
+ * 0.5) 2^-53 of an output x, in fp64.  A round takes 51 draws at fixed places, whatever the outcome: draw 0 the coordinate, draws
+ * 1 .. 48 sixteen points of the cube, draw 49 the torsion's angle, draw 50 the acceptance variate.  Nothing depends on the walker's place
+ * in the batch or on the batch's size.
+ *
+ * Round 0 has no move: starts[w] is refined as mdx_refine_poses_flex refines it and becomes the current and the best state.  If it ends
+ * MDX_REFINE_NONFINITE, S_cur = S_best = +inf and current and best are the input pose (with whatever row and E_dih were computed); the
+ * first finite round replaces both.
+ * Round r >= 1, fp64:
+ *   move        the enabled coordinates are, in this order, the translation (trans_amp > 0), the rotation (rot_amp > 0) and the
+ *               n_torsions torsions (tors_amp > 0): n_choices of them; j = min(floor(u_0 n_choices), n_choices - 1).
+ *               ball: p = the first of the sixteen points (2 u_{1+3i} - 1, 2 u_{2+3i} - 1, 2 u_{3+3i} - 1), i = 0 .. 15, with
+ *               (p_x^2 + p_y^2) + p_z^2 <= 1; if there is none, p = 0.  Translation: dt = trans_amp p.  Rotation: the rotation vector
+ *               rot_amp p (radians).  Torsion k: dtheta_k = (2 u_49 - 1) tors_amp.  Whatever is not moved is 0.
+ *   new start   X0' = coords(dq, dt, dtheta) of mdx_refine_poses_flex with the walker's current pose Y_cur (fp32) as the input X0:
+ *               c0 = the mean of Y_cur, dq = the next-trial rule with s = 1, omega = the rotation vector and q = identity (the rotation
+ *               by |omega| about omega / |omega|, normalised; the identity for omega = 0), B(dtheta) and its mean as there, rounded to fp32 once.
+ *   refinement  exactly what mdx_refine_poses_flex does to X0' with opts->refine: Y, row, E_dih, status and evaluation count of its
+ *               accepted state, S_new = sum_b (double) row[b] + (double) E_dih.
+ *   decision    a round that ends MDX_REFINE_NONFINITE is rejected.  Otherwise it is accepted when S_new < S_cur, or when kT > 0 and
+ *               u_50 < exp(-(S_new - S_cur) / kT) ("uphill").  On accept (Y_cur, S_cur) <- (Y, S_new), and when S_new < S_best, strictly,
+ *               best <- the round's (Y, row, rigid, E_dih, S_new, r).
+ * Outputs, of the best round: best_out[w] = its Y, best_rows_out[w] = its row, best_score_out[w] = S_best (fp64; +inf if no round was
+ * finite), best_dih_out[w] = its E_dih, best_round_out[w] = r, stats_out[w] = (rounds >= 1 accepted, of those accepted uphill, non-finite
+ * rounds with round 0 among them, evaluations of all rounds).  With n_rounds == 1, best_out, best_rows_out and best_dih_out are
+ * poses_out, rows_out and dih_out of mdx_refine_poses_flex bit for bit.  A walker gives the same bits alone or in a batch of any size,
+ * at any place in it, given the same stream id; a search of R rounds and one of R' > R rounds agree on every round < R.
+ * Not part of it: receptor or ring flexibility, other local optimisers, clustering of the results, exchange between walkers,
+ * continuing a search across calls, decomposed handles, alchemical windows, ligands above 256 atoms or 32 torsions. */
+#define MDX_SEARCH_MAX_ROUNDS 1024u
+typedef struct { uint32_t n_rounds; float trans_amp, rot_amp, tors_amp, kT; uint64_t seed; mdx_flex_opts refine; } mdx_search_opts;
+int      mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_walkers, const float* starts /* [n_walkers][count][3] */,
+                          const uint64_t* streams_or_null /* [n_walkers] */, uint32_t root, uint32_t n_torsions,
+                          const uint32_t* torsion_bonds /* [n_torsions][2], ligand-local */, const mdx_search_opts* opts,
+                          float* best_out /* [n_walkers][count][3] */, float* best_rows_out_or_null /* [n_walkers][n_groups] */,
+                          uint32_t n_groups, double* best_score_out_or_null /* [n_walkers]: S */, float* best_dih_out_or_null /* [n_walkers] */,
+                          uint32_t* best_round_out_or_null /* [n_walkers] */,
+                          uint32_t* stats_out_or_null /* [n_walkers][4]: rounds accepted, accepted uphill, non-finite rounds, evaluations in total */);
+
 /* ---- multi-GPU: one periodic box spatially decomposed over the GPUs of a node (the reference is
  * single-device, src/util.rs:1086 `CudaContext::new(0)`, so this is new capability, not parity) -------------------
  * One rank (process or thread) per GPU.  Every rank creates a handle from the SAME global system (static per-atom data

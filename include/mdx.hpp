@@ -221,6 +221,28 @@ public:
                                     r.evals.data()));
         return r;
     }
+    /// mdx_search_poses: per walker an iterated local search around refine_poses_flex - perturb, refine, accept or reject by Metropolis,
+    /// keep the best (the rule is stated in mdx.h).  streams: empty (walker w draws from stream w) or one stream id per walker.
+    struct SearchedPoses {
+        std::vector<float> poses, rows, dih;               ///< [n][count][3], [n][n_groups], [n] - of every walker's best round
+        std::vector<double> score;                         ///< [n] S = the row's sum + the dihedral energy
+        std::vector<uint32_t> best_round, stats;           ///< [n], [n][4]: rounds accepted, accepted uphill, non-finite rounds, evaluations
+    };
+    SearchedPoses search_poses(uint32_t first, uint32_t count, const std::vector<float>& starts, const std::vector<uint64_t>& streams,
+                               uint32_t root, const std::vector<uint32_t>& torsion_bonds, const mdx_search_opts& opts) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        if (count == 0 || starts.size() % (3 * (size_t)count) != 0) throw std::invalid_argument("search_poses: starts must hold [n_walkers][count][3] floats");
+        if (torsion_bonds.size() % 2 != 0) throw std::invalid_argument("search_poses: torsion_bonds must hold [n_torsions][2] atom indices");
+        const uint32_t n = (uint32_t)(starts.size() / (3 * (size_t)count)), t = (uint32_t)(torsion_bonds.size() / 2);
+        if (!streams.empty() && streams.size() != n) throw std::invalid_argument("search_poses: streams must be empty or hold one id per walker");
+        SearchedPoses r;
+        r.poses.assign(starts.size(), 0.f); r.rows.assign((size_t)n * g, 0.f); r.dih.assign(n, 0.f); r.score.assign(n, 0.0);
+        r.best_round.assign(n, 0u); r.stats.assign((size_t)n * 4, 0u);
+        check(mdx_search_poses(h_, first, count, n, starts.data(), streams.empty() ? nullptr : streams.data(), root, t,
+                               t ? torsion_bonds.data() : nullptr, &opts, r.poses.data(), r.rows.data(), g, r.score.data(), r.dih.data(),
+                               r.best_round.data(), r.stats.data()));
+        return r;
+    }
 
     /// `md.cell = SimBox::new(lo, hi)` + `md.rebuild_spatial_caches()` (sol_shrinking_box.rs:600-603, 632).
     void set_cell(const SimBox& b) { check(mdx_set_box(h_, b.bounds_low.data(), b.bounds_high.data())); }

@@ -29,6 +29,7 @@ REFINE_CONVERGED, REFINE_MAX_EVALS, REFINE_STALLED, REFINE_NONFINITE = 0, 1, 2, 
 REFINE_MAX_EVALS_CAP = 4096      # MDX_REFINE_MAX_EVALS_CAP
 POSE_MAX_TORSIONS = 32           # MDX_POSE_MAX_TORSIONS: the most torsions mdx_refine_poses_flex takes
 FLEX_DIHEDRALS = 0x1             # MDX_FLEX_DIHEDRALS
+SEARCH_MAX_ROUNDS = 1024         # MDX_SEARCH_MAX_ROUNDS: the most rounds mdx_search_poses takes
 
 _fp = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
@@ -75,6 +76,12 @@ class CFlexOpts(C.Structure):
     """mdx_flex_opts"""
     _fields_ = [("max_evals", C.c_uint32), ("f_tol", C.c_float), ("tau_tol", C.c_float), ("tors_tol", C.c_float), ("h_start", C.c_float),
                 ("h_max", C.c_float), ("flags", C.c_uint32)]
+
+
+class CSearchOpts(C.Structure):
+    """mdx_search_opts"""
+    _fields_ = [("n_rounds", C.c_uint32), ("trans_amp", C.c_float), ("rot_amp", C.c_float), ("tors_amp", C.c_float), ("kT", C.c_float),
+                ("seed", C.c_uint64), ("refine", CFlexOpts)]
 
 
 class CEnergies(C.Structure):

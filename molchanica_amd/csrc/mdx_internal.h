@@ -293,6 +293,8 @@ struct DeviceState {
     // mdx_refine_poses_flex: the same block with the flexible state records and the per-term dihedral energies (FlexLayout); the table of
     // one torsion list: moving-set masks, the ligand's dihedral terms and the per-atom lists into them (FlexTable)
     void* ps_flex = nullptr; void* ps_flex_tab = nullptr;
+    // mdx_search_poses: the search records, current and best coordinates, best rows / rigid and stream ids of one chunk (SearchLayout)
+    void* ps_search = nullptr;
 };
 
 struct MdxDecomp;   // mdx_comm.h: the handle is one rank of a spatially decomposed box
@@ -362,7 +364,7 @@ struct mdx_handle {
     size_t ps_cap_stage = 0, ps_cap_slab = 0, ps_cap_fslab = 0, ps_cap_refine = 0;
     // mdx_refine_poses_flex: what ps_flex_tab was built for (with ps_first / ps_count / ps_epoch) and how many dihedral terms it holds
     bool fx_valid = false; uint32_t fx_first = 0, fx_count = 0, fx_root = 0, fx_flags = 0, fx_terms = 0; uint64_t fx_epoch = 0;
-    std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0;
+    std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0, ps_cap_search = 0;
     bool alch_on = false; double alch_lambda = 0.0; uint32_t alch_lo = 0, alch_hi = 0;
     float sc_alpha = 0.5f, sc_sigma_min = 3.0f;   // soft core of the alchemical window (mdx_set_alchemical_softcore)
     std::vector<double> foreign_lams;             // mdx_set_foreign_lambdas (survives window changes; empty: none)
@@ -689,13 +691,8 @@ static inline double mdx_dof(const mdx_handle* h) {
     return d < 1.0 ? 1.0 : d;
 }
 
-// counter-based RNG shared (bit for bit) with the oracle
-__host__ __device__ static inline uint64_t mdx_splitmix64(uint64_t* s) {
-    uint64_t z = (*s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// counter-based RNG shared (bit for bit) with the oracle: mdx_splitmix64
+#include "mdx_splitmix64.h"
 
 // rocprof markers: roctxRangePush / roctxRangePop around the phases of the step loop, so that
 // `rocprofv3 --marker-trace` shows rebuild / halo / force phases beside the kernels.  librocprofiler-sdk-roctx (or the older

@@ -44,10 +44,17 @@
 //       pose_force_sum_kernel does, accepts or rejects the trial from the pose's state record, and writes the next trial into the
 //       staging buffer the force flavour reads.  A pose that has finished sets its word in frozen[]; the REFINE instantiation of
 //       pose_score_kernel reads it before anything else and the whole workgroup returns, as the step kernel's does.
+//
+// mdx_refine_poses_flex: the same loop with the ligand's torsion angles as further coordinates (pose_flex_step_kernel, mdx_flex_step.h).
+//
+// mdx_search_poses: n_rounds of that loop per walker with pose_search_kernel between two of them (mdx_search_step.h): it decides the
+// round that ended - Metropolis on the refinement's objective, current and best pose in the walker's search record - and perturbs the
+// current pose into the staging buffer for the next; n_rounds x (1 + 2 max_evals) + 1 launches per chunk, one read-back, one wait.
 #include "mdx_bonded_dev.h"
 #include "mdx_pair_dev.h"
 #include "mdx_refine_step.h"
 #include "mdx_flex_step.h"
+#include "mdx_search_step.h"
 #include <cmath>
 #include <cstring>
 
@@ -1042,6 +1049,68 @@ static int flex_table(mdx_handle* h, const std::string& who, uint32_t first, uin
     return MDX_OK;
 }
 
+// What mdx_refine_poses_flex and mdx_search_poses share ahead of their loops: the checks of the torsion list and the options, the
+// refusals and buffers of pose_setup, the table and the block of a chunk
+static int flex_begin(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, uint32_t root,
+                      uint32_t n_torsions, const uint32_t* torsion_bonds, const mdx_flex_opts* opts, uint32_t n_groups, PoseArgs& a, int& mode,
+                      bool& geom, mdx_fx_opts& o) {
+    if (n_torsions > MDX_POSE_MAX_TORSIONS) FAIL(MDX_EPARAM, who + ": n_torsions exceeds MDX_POSE_MAX_TORSIONS (32)");
+    if (n_torsions && !torsion_bonds) FAIL(MDX_EPARAM, who + ": null torsion_bonds with n_torsions > 0");
+    if (opts->max_evals == 0 || opts->max_evals > MDX_REFINE_MAX_EVALS_CAP) FAIL(MDX_EPARAM, who + ": max_evals must be in 1..MDX_REFINE_MAX_EVALS_CAP (4096)");
+    for (float v : {opts->f_tol, opts->tau_tol, opts->tors_tol, opts->h_start, opts->h_max})
+        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": a tolerance or step length is negative or not finite");
+    if (opts->flags & ~MDX_FLEX_DIHEDRALS) FAIL(MDX_EPARAM, who + ": unknown flag bits");
+    o = mdx_fx_opts{{(double)opts->f_tol, (double)opts->tau_tol, opts->h_start > 0.f ? (double)opts->h_start : 0.01,
+                     opts->h_max > 0.f ? (double)opts->h_max : 0.2}, (double)opts->tors_tol};
+    if (o.rf.h_start > o.rf.h_max) FAIL(MDX_EPARAM, who + ": h_start exceeds h_max");
+    // the torsion list against the host's copy of the bonds - once the range itself has passed the checks pose_setup opens with
+    if (count == 0 || count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, who + ": count must be in 1..MDX_POSE_MAX_ATOMS (256)");
+    if ((uint64_t)first + count > h->N) FAIL(MDX_EPARAM, "atom range out of bounds");
+    std::vector<mdx_fx_torsion> tor;
+    MDX_TRY(flex_graph(h, who, first, count, root, n_torsions, torsion_bonds, tor));
+    MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, true, a, mode, geom));
+    MDX_TRY(flex_table(h, who, first, count, root, n_torsions, torsion_bonds, opts->flags, tor));
+    DeviceState& d = h->d;
+    const size_t need = FlexLayout(POSE_CHUNK, 3 * (size_t)count, h->n_grp, h->fx_terms).end;
+    if (h->ps_cap_flex < need) {
+        if (d.ps_flex) { (void)hipFree(d.ps_flex); d.ps_flex = nullptr; }
+        h->ps_cap_flex = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_flex, need));
+        h->ps_cap_flex = need;
+    }
+    return MDX_OK;
+}
+
+// the step kernel's arguments for a chunk laid out by `lay`
+static FlexArgs flex_args(mdx_handle* h, const PoseArgs& a, uint32_t count, uint32_t T, const FlexLayout& lay, const mdx_fx_opts& o) {
+    DeviceState& d = h->d;
+    const uint32_t n_terms = h->fx_terms;
+    const FlexTable tab(count, n_terms);
+    unsigned char* blk = (unsigned char*)d.ps_flex;
+    const unsigned char* tb = (const unsigned char*)d.ps_flex_tab;
+    FlexArgs r{};
+    r.count = count; r.G = h->n_grp; r.T = T; r.n_terms = n_terms; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
+    r.frozen = (uint32_t*)(blk + lay.frozen); r.st = (mdx_fx_state*)(blk + lay.state);
+    r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
+    r.eterm = (double*)(blk + lay.eterm);
+    r.tor = (const mdx_fx_torsion*)(tb + tab.tor); r.dih = (const mdx_fx_dihedral*)(tb + tab.dih);
+    r.aoff = (const uint32_t*)(tb + tab.aoff); r.aent = (const uint32_t*)(tb + tab.aent);
+    for (int k = 0; k < 3; ++k) r.box[k] = (double)a.box[k];
+    r.o = o;
+    return r;
+}
+
+// one evaluation of a chunk: the REFINE force pass, then the flexible step kernel
+static void flex_evaluate(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, const FlexArgs& r) {
+    switch (mode) {
+    case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, true, true); break;
+    case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, true, true); break;
+    case CM_RF: launch_poses<CM_RF>(h, a, geom, n, true, true); break;
+    default: launch_poses<CM_EWALD>(h, a, geom, n, true, true); break;
+    }
+    hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
+}
+
 extern "C" int mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, uint32_t root,
                                      uint32_t n_torsions, const uint32_t* torsion_bonds, const mdx_flex_opts* opts, float* poses_out,
                                      float* rows_out_or_null, uint32_t n_groups, float* rigid_out_or_null, float* xform_out_or_null,
@@ -1051,68 +1120,29 @@ extern "C" int mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t cou
     if (!h) FAIL(MDX_EPARAM, "null handle");
     if (n_poses == 0) return MDX_OK;
     if (!poses || !poses_out || !opts) FAIL(MDX_EPARAM, "null argument");
-    if (n_torsions > MDX_POSE_MAX_TORSIONS) FAIL(MDX_EPARAM, who + ": n_torsions exceeds MDX_POSE_MAX_TORSIONS (32)");
-    if (n_torsions && !torsion_bonds) FAIL(MDX_EPARAM, who + ": null torsion_bonds with n_torsions > 0");
-    if (opts->max_evals == 0 || opts->max_evals > MDX_REFINE_MAX_EVALS_CAP) FAIL(MDX_EPARAM, who + ": max_evals must be in 1..MDX_REFINE_MAX_EVALS_CAP (4096)");
-    for (float v : {opts->f_tol, opts->tau_tol, opts->tors_tol, opts->h_start, opts->h_max})
-        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": a tolerance or step length is negative or not finite");
-    if (opts->flags & ~MDX_FLEX_DIHEDRALS) FAIL(MDX_EPARAM, who + ": unknown flag bits");
-    mdx_fx_opts o{{(double)opts->f_tol, (double)opts->tau_tol, opts->h_start > 0.f ? (double)opts->h_start : 0.01,
-                   opts->h_max > 0.f ? (double)opts->h_max : 0.2}, (double)opts->tors_tol};
-    if (o.rf.h_start > o.rf.h_max) FAIL(MDX_EPARAM, who + ": h_start exceeds h_max");
-    // the torsion list against the host's copy of the bonds - once the range itself has passed the checks pose_setup opens with
-    if (count == 0 || count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, who + ": count must be in 1..MDX_POSE_MAX_ATOMS (256)");
-    if ((uint64_t)first + count > h->N) FAIL(MDX_EPARAM, "atom range out of bounds");
-    std::vector<mdx_fx_torsion> tor;
-    MDX_TRY(flex_graph(h, who, first, count, root, n_torsions, torsion_bonds, tor));
     PoseArgs a{};
     int mode = 0; bool geom = false;
-    MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, true, a, mode, geom));
-    MDX_TRY(flex_table(h, who, first, count, root, n_torsions, torsion_bonds, opts->flags, tor));
+    mdx_fx_opts o{};
+    MDX_TRY(flex_begin(h, who, first, count, n_poses, poses, root, n_torsions, torsion_bonds, opts, n_groups, a, mode, geom, o));
     DeviceState& d = h->d;
     hipStream_t st = h->stream;
     const uint32_t G = h->n_grp, T = n_torsions, n_terms = h->fx_terms;
     const size_t per_pose = 3 * (size_t)count;
-    const size_t need = FlexLayout(POSE_CHUNK, per_pose, G, n_terms).end;
-    if (h->ps_cap_flex < need) {
-        if (d.ps_flex) { (void)hipFree(d.ps_flex); d.ps_flex = nullptr; }
-        h->ps_cap_flex = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_flex, need));
-        h->ps_cap_flex = need;
-    }
     const uint32_t X = 7u + T;
     std::vector<float> yres(per_pose * n_poses), rres((size_t)n_poses * G), gres(6u * (size_t)n_poses), xres((size_t)X * n_poses),
         dres(n_poses), tres((size_t)T * n_poses);
     std::vector<uint32_t> sres(n_poses), eres(n_poses);
     std::vector<unsigned char> back;
-    const FlexTable tab(count, n_terms);
     for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
         const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
         const FlexLayout lay(n, per_pose, G, n_terms);
         unsigned char* blk = (unsigned char*)d.ps_flex;
-        const unsigned char* tb = (const unsigned char*)d.ps_flex_tab;
-        FlexArgs r{};
-        r.count = count; r.G = G; r.T = T; r.n_terms = n_terms; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
-        r.frozen = (uint32_t*)(blk + lay.frozen); r.st = (mdx_fx_state*)(blk + lay.state);
-        r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
-        r.eterm = (double*)(blk + lay.eterm);
-        r.tor = (const mdx_fx_torsion*)(tb + tab.tor); r.dih = (const mdx_fx_dihedral*)(tb + tab.dih);
-        r.aoff = (const uint32_t*)(tb + tab.aoff); r.aent = (const uint32_t*)(tb + tab.aent);
-        for (int k = 0; k < 3; ++k) r.box[k] = (double)a.box[k];
-        r.o = o;
+        const FlexArgs r = flex_args(h, a, count, T, lay, o);
         a.frozen = r.frozen;
         HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(blk, 0, lay.y, st));
         mdx_prof_begin(h, 0);
-        for (uint32_t k = 0; k < opts->max_evals; ++k) {
-            switch (mode) {
-            case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, true, true); break;
-            case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, true, true); break;
-            case CM_RF: launch_poses<CM_RF>(h, a, geom, n, true, true); break;
-            default: launch_poses<CM_EWALD>(h, a, geom, n, true, true); break;
-            }
-            hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, st, r);
-        }
+        for (uint32_t k = 0; k < opts->max_evals; ++k) flex_evaluate(h, a, mode, geom, n, r);
         mdx_prof_end(h);
         HIP_TRY(hipGetLastError());
         back.resize(lay.x0 - lay.state);
@@ -1141,5 +1171,195 @@ extern "C" int mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t cou
     if (tgrad_out_or_null && T) std::memcpy(tgrad_out_or_null, tres.data(), sizeof(float) * tres.size());
     if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
     if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
+    return MDX_OK;
+}
+
+// ---- mdx_search_poses: an iterated local search per walker around the loop above (mdx_search_step.h) ------------------------------------
+// The search block of a chunk of n walkers: [records | best coordinates | best rows | best rigid | current coordinates | stream ids];
+// records .. best rigid come back in one copy at the chunk's end.
+struct SearchLayout {
+    size_t rec, best_y, best_row, best_rigid, cur_y, streams, end;
+    SearchLayout(uint32_t n, size_t per_pose, uint32_t G) {
+        rec = 0;
+        best_y = sizeof(mdx_sr_record) * n;
+        best_row = best_y + sizeof(float) * per_pose * n;
+        best_rigid = best_row + sizeof(float) * (size_t)G * n;
+        cur_y = best_rigid + sizeof(float) * 6u * n;
+        streams = ((cur_y + sizeof(float) * per_pose * n + 15u) / 16u) * 16u;
+        end = streams + sizeof(uint64_t) * n;
+    }
+};
+
+struct SearchArgs {
+    uint32_t count, G, T, pad;
+    float* stage; uint32_t* frozen; mdx_fx_state* st;              // what the refinement starts from: staged pose, frozen word, state record
+    const float* y; const float* row; const float* rigid;          // what it ended with: its accepted coordinates, row and rigid
+    const mdx_fx_torsion* tor;
+    const uint64_t* streams; mdx_sr_record* rec;
+    float* cur_y; float* best_y; float* best_row; float* best_rigid;
+    mdx_sr_opts o;
+};
+
+// Launched with round index r between two refinements, one workgroup per walker: it decides round r - 1 (r >= 1) from what the
+// refinement left - thread 0 takes the decision, the threads copy the accepted coordinates (and, for a new best, row and rigid) into the
+// walker's search record - and, for r < n_rounds, starts round r: thread 0 draws the move and forms (dq, dt), B(dtheta) is built in LDS
+// from the current pose with one barrier per non-zero torsion as pose_flex_step_kernel builds a trial, every thread writes its atom of
+// X0' into the staging buffer, and the walker's state record and frozen word are zeroed ("evaluation 0: the trial is the input").
+// Round 0 has no move: the staged pose is the caller's.  Plain stores only.
+__global__ __launch_bounds__(256) void pose_search_kernel(SearchArgs a, uint32_t r) {
+    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_c[3], s_bc[3], s_R[9], s_t[3], s_th[MDX_FX_MAX_TORSIONS], s_cs[MDX_FX_MAX_TORSIONS],
+                      s_sn[MDX_FX_MAX_TORSIONS];
+    __shared__ uint32_t s_fl;
+    const uint32_t tid = threadIdx.x, walker = blockIdx.x, count = a.count, T = a.T;
+    const size_t at = ((size_t)walker * count + tid) * 3u;
+    uint32_t fl = 0u;
+    if (r >= 1u) {
+        if (tid == 0u) {
+            const mdx_fx_state* s = a.st + walker;
+            mdx_sr_record rec = a.rec[walker];
+            const bool finite = !(s->rf.frozen != 0u && s->rf.status == MDX_RF_NONFINITE);
+            s_fl = sr_decide(rec, a.o, r - 1u, s->rf.S, finite, s->edih, s->rf.evals, sr_stream(a.o.seed, a.streams[walker], r - 1u));
+            a.rec[walker] = rec;
+        }
+        __syncthreads();
+        fl = s_fl;
+        if (fl & MDX_SR_BEST) {
+            if (tid < count)
+                for (uint32_t c = 0; c < 3u; ++c) a.best_y[at + c] = a.y[at + c];
+            if (tid < a.G) a.best_row[(size_t)walker * a.G + tid] = a.row[(size_t)walker * a.G + tid];
+            if (tid < 6u) a.best_rigid[(size_t)walker * 6u + tid] = a.rigid[(size_t)walker * 6u + tid];
+        }
+    }
+    if (r >= a.o.n_rounds) {      // (uniform over the grid: the last launch only decides)
+        if ((fl & MDX_SR_ACCEPT) && tid < count)
+            for (uint32_t c = 0; c < 3u; ++c) a.cur_y[at + c] = a.y[at + c];
+        return;
+    }
+    if (r >= 1u) {
+        // the current pose: the round just accepted, or the record's
+        const float* src = (fl & MDX_SR_ACCEPT) ? a.y : a.cur_y;
+        if (tid < count)
+            for (uint32_t c = 0; c < 3u; ++c) {
+                const float v = src[at + c];
+                s_x[tid][c] = (double)v;
+                if (fl & MDX_SR_ACCEPT) a.cur_y[at + c] = v;
+            }
+        if (tid < MDX_FX_MAX_TORSIONS) s_th[tid] = 0.0;
+        __syncthreads();
+        if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
+        if (tid == 64u) {      // (a wave beside the centroid's)
+            mdx_sr_move mv;
+            double q[4];
+            sr_move(a.o, T, sr_stream(a.o.seed, a.streams[walker], r), mv);
+            sr_xform(mv, q, s_t);
+            rf_rotation(q, s_R);
+            if (mv.kind == MDX_SR_TORSION) { s_th[mv.torsion] = mv.dtheta; s_cs[mv.torsion] = cos(mv.dtheta); s_sn[mv.torsion] = sin(mv.dtheta); }
+        }
+        __syncthreads();
+        for (uint32_t k = 0; k < T; ++k) {
+            if (s_th[k] == 0.0) continue;      // (uniform over the workgroup)
+            const mdx_fx_torsion& t = a.tor[k];      // (read where it lies: at most one torsion is turned per round)
+            double u[3];
+            const bool turns = fx_axis(&s_x[0][0], t, u);      // (atoms a and b: not written in this round)
+            if (turns && tid < count && tid != t.b && fx_member(t.mask, tid)) {
+                const double b[3] = {s_x[t.b][0], s_x[t.b][1], s_x[t.b][2]};
+                fx_rotate(u, b, s_cs[k], s_sn[k], s_x[tid]);
+            }
+            __syncthreads();
+        }
+        if (tid < 3u) s_bc[tid] = rf_mean(&s_x[0][0], count, tid);
+        __syncthreads();
+        if (tid < count) {
+            float y[3];
+            fx_coords(s_c, s_t, s_R, s_x[tid], s_bc, y);
+            for (uint32_t c = 0; c < 3u; ++c) a.stage[at + c] = y[c];
+        }
+    }
+    uint32_t* dst = (uint32_t*)(a.st + walker);
+    for (uint32_t i = tid; i < sizeof(mdx_fx_state) / 4u; i += 256u) dst[i] = 0u;
+    if (tid == 0u) a.frozen[walker] = 0u;
+}
+
+extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_walkers, const float* starts,
+                                const uint64_t* streams_or_null, uint32_t root, uint32_t n_torsions, const uint32_t* torsion_bonds,
+                                const mdx_search_opts* opts, float* best_out, float* best_rows_out_or_null, uint32_t n_groups,
+                                double* best_score_out_or_null, float* best_dih_out_or_null, uint32_t* best_round_out_or_null,
+                                uint32_t* stats_out_or_null) {
+    const std::string who = "mdx_search_poses";
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_walkers == 0) return MDX_OK;
+    if (!starts || !best_out || !opts) FAIL(MDX_EPARAM, "null argument");
+    if (opts->n_rounds == 0 || opts->n_rounds > MDX_SEARCH_MAX_ROUNDS) FAIL(MDX_EPARAM, who + ": n_rounds must be in 1..MDX_SEARCH_MAX_ROUNDS (1024)");
+    if ((uint64_t)opts->n_rounds * opts->refine.max_evals > 65536u) FAIL(MDX_EPARAM, who + ": n_rounds x max_evals exceeds 65536");
+    for (float v : {opts->trans_amp, opts->rot_amp, opts->tors_amp, opts->kT})
+        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": an amplitude or kT is negative or not finite");
+    if (opts->tors_amp > 3.14159265358979323846f) FAIL(MDX_EPARAM, who + ": tors_amp exceeds pi");      // (the fp32 nearest to pi passes)
+    mdx_sr_opts so{(double)opts->trans_amp, (double)opts->rot_amp, (double)opts->tors_amp, (double)opts->kT, opts->seed, opts->n_rounds, 0u};
+    if (n_torsions <= MDX_POSE_MAX_TORSIONS && sr_choices(so, n_torsions) == 0u)
+        FAIL(MDX_EPARAM, who + ": no move is enabled (every amplitude is 0, or only tors_amp with no torsion)");
+    PoseArgs a{};
+    int mode = 0; bool geom = false;
+    mdx_fx_opts o{};
+    MDX_TRY(flex_begin(h, who, first, count, n_walkers, starts, root, n_torsions, torsion_bonds, &opts->refine, n_groups, a, mode, geom, o));
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t G = h->n_grp, T = n_torsions, n_terms = h->fx_terms;
+    const size_t per_pose = 3 * (size_t)count;
+    const size_t need = SearchLayout(POSE_CHUNK, per_pose, G).end;
+    if (h->ps_cap_search < need) {
+        if (d.ps_search) { (void)hipFree(d.ps_search); d.ps_search = nullptr; }
+        h->ps_cap_search = 0;
+        HIP_TRY(hipMalloc((void**)&d.ps_search, need));
+        h->ps_cap_search = need;
+    }
+    std::vector<float> yres(per_pose * n_walkers), rres((size_t)n_walkers * G), dres(n_walkers);
+    std::vector<double> scres(n_walkers);
+    std::vector<uint32_t> brres(n_walkers), stres(4u * (size_t)n_walkers);
+    std::vector<uint64_t> ids(std::min(n_walkers, POSE_CHUNK));
+    std::vector<unsigned char> back;
+    for (uint32_t p0 = 0; p0 < n_walkers; p0 += POSE_CHUNK) {
+        const uint32_t n = std::min(POSE_CHUNK, n_walkers - p0);
+        const FlexLayout lay(n, per_pose, G, n_terms);
+        const SearchLayout sl(n, per_pose, G);
+        unsigned char* sb = (unsigned char*)d.ps_search;
+        const FlexArgs r = flex_args(h, a, count, T, lay, o);
+        a.frozen = r.frozen;
+        SearchArgs s{};
+        s.count = count; s.G = G; s.T = T; s.stage = d.ps_stage; s.frozen = r.frozen; s.st = r.st; s.y = r.y; s.row = r.row; s.rigid = r.rigid;
+        s.tor = r.tor; s.streams = (const uint64_t*)(sb + sl.streams); s.rec = (mdx_sr_record*)(sb + sl.rec);
+        s.cur_y = (float*)(sb + sl.cur_y); s.best_y = (float*)(sb + sl.best_y); s.best_row = (float*)(sb + sl.best_row);
+        s.best_rigid = (float*)(sb + sl.best_rigid);
+        s.o = so;
+        for (uint32_t k = 0; k < n; ++k) ids[k] = streams_or_null ? streams_or_null[p0 + k] : (uint64_t)(p0 + k);
+        HIP_TRY(hipMemcpyAsync(d.ps_stage, starts + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(sb + sl.streams, ids.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
+        mdx_prof_begin(h, 0);
+        for (uint32_t rd = 0; rd < opts->n_rounds; ++rd) {
+            hipLaunchKernelGGL(pose_search_kernel, dim3(n), dim3(256), 0, st, s, rd);
+            for (uint32_t k = 0; k < opts->refine.max_evals; ++k) flex_evaluate(h, a, mode, geom, n, r);
+        }
+        hipLaunchKernelGGL(pose_search_kernel, dim3(n), dim3(256), 0, st, s, opts->n_rounds);
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        back.resize(sl.cur_y - sl.rec);
+        HIP_TRY(hipMemcpyAsync(back.data(), sb + sl.rec, back.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));      // (ids is free again: the upload above has completed)
+        const unsigned char* b0 = back.data();
+        std::memcpy(yres.data() + per_pose * p0, b0 + sl.best_y, sizeof(float) * per_pose * n);
+        std::memcpy(rres.data() + (size_t)p0 * G, b0 + sl.best_row, sizeof(float) * (size_t)G * n);
+        for (uint32_t k = 0; k < n; ++k) {
+            mdx_sr_record rec;
+            std::memcpy(&rec, b0 + sl.rec + sizeof(mdx_sr_record) * k, sizeof(rec));
+            scres[p0 + k] = rec.S_best; dres[p0 + k] = rec.edih_best; brres[p0 + k] = rec.best_round;
+            uint32_t* c = stres.data() + 4u * (size_t)(p0 + k);
+            c[0] = rec.accepted; c[1] = rec.uphill; c[2] = rec.nonfinite; c[3] = rec.evals;
+        }
+    }
+    std::memcpy(best_out, yres.data(), sizeof(float) * yres.size());
+    if (best_rows_out_or_null) std::memcpy(best_rows_out_or_null, rres.data(), sizeof(float) * rres.size());
+    if (best_score_out_or_null) std::memcpy(best_score_out_or_null, scres.data(), sizeof(double) * scres.size());
+    if (best_dih_out_or_null) std::memcpy(best_dih_out_or_null, dres.data(), sizeof(float) * dres.size());
+    if (best_round_out_or_null) std::memcpy(best_round_out_or_null, brres.data(), sizeof(uint32_t) * brres.size());
+    if (stats_out_or_null) std::memcpy(stats_out_or_null, stres.data(), sizeof(uint32_t) * stres.size());
     return MDX_OK;
 }

@@ -17,8 +17,8 @@ import os
 
 import numpy as np
 
-from ._abi import (CCommDiag, CFlexOpts, CHBond, CConfig, CEnergies, CRefineOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, MDX_EDEVICE,
-                   MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, VEL, MdConfig, MdSystem)
+from ._abi import (CCommDiag, CFlexOpts, CHBond, CConfig, CEnergies, CRefineOpts, CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE,
+                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, VEL, MdConfig, MdSystem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDX_LIB") or os.path.join(_HERE, "libmdx.so")   # MDX_LIB: A/B builds of the same ABI
@@ -174,6 +174,8 @@ def load_library():
                                      _u32p, _u32p]
     lib.mdx_refine_poses_flex.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, C.c_uint32, C.c_uint32, _u32p, C.POINTER(CFlexOpts), _fp,
                                           _fp, C.c_uint32, _fp, _fp, _fp, _fp, _u32p, _u32p]
+    lib.mdx_search_poses.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, _u32p,
+                                     C.POINTER(CSearchOpts), _fp, _fp, C.c_uint32, C.POINTER(C.c_double), _fp, _u32p, _u32p]
     _lib = lib
     return lib
 
@@ -390,6 +392,59 @@ class MdState:
                                          x.ctypes.data_as(_fp), e.ctypes.data_as(_fp), g.ctypes.data_as(_fp), st.ctypes.data_as(_u32p),
                                          ev.ctypes.data_as(_u32p)))
         return y, (r[:, :n] if n else r[:, :0]), t, x, e, g[:, :T], st, ev
+
+    def search_poses(self, first: int, starts, root: int, torsion_bonds, n_rounds: int, trans_amp: float, rot_amp: float, tors_amp: float,
+                     kT: float, seed: int, max_evals: int, f_tol: float, tau_tol: float, tors_tol: float, h_start: float = 0.0,
+                     h_max: float = 0.0, dihedrals: bool = True, streams=None):
+        """`mdx_search_poses`: per walker an iterated local search on the device - round 0 refines starts[w] as refine_poses_flex()
+        does; every later round perturbs the walker's current pose (a translation within trans_amp A, a rotation within rot_amp rad
+        or one torsion by up to tors_amp rad, chosen uniformly among the enabled coordinates), refines it with the same options and
+        accepts it by Metropolis at kT kcal/mol (0: downhill only) - include/mdx.h states the rule.  starts: float32 [W, count, 3];
+        streams: None (walker w draws from stream w) or unsigned integers [W], the walkers' stream ids; seed: 64 bits.
+        -> (best [W, count, 3] f32, rows [W, n_groups] f32, score [W] f64: S = sum of the row + the dihedral energy, dih [W] f32,
+        best_round [W] u32, stats [W, 4] u32: rounds accepted, accepted uphill, non-finite rounds, evaluations), all of the best
+        round.  The handle is left as it is."""
+        if not isinstance(starts, np.ndarray) or starts.dtype != np.float32:
+            raise ParamError("search_poses: starts must be a float32 ndarray [W, count, 3]")
+        if starts.ndim != 3 or starts.shape[2] != 3 or not 1 <= starts.shape[1] <= POSE_MAX_ATOMS:
+            raise ParamError(f"search_poses: starts must have shape [W, count, 3] with 1 <= count <= {POSE_MAX_ATOMS}, got {starts.shape}")
+        if int(first) < 0 or int(first) + starts.shape[1] > self.n_atoms:
+            raise ParamError("search_poses: atom range out of bounds")
+        tb = np.asarray(torsion_bonds)
+        if tb.size == 0:
+            tb = np.zeros((0, 2), np.uint32)
+        if tb.dtype.kind not in "iu" or tb.ndim != 2 or tb.shape[1] != 2 or tb.shape[0] > POSE_MAX_TORSIONS:
+            raise ParamError(f"search_poses: torsion_bonds must be integers [T, 2] with T <= {POSE_MAX_TORSIONS}")
+        if (tb < 0).any() or (tb >= starts.shape[1]).any() or not 0 <= int(root) < starts.shape[1]:
+            raise ParamError("search_poses: root and torsion_bonds are ligand-local atom indices (< count)")
+        a = np.ascontiguousarray(starts)
+        W = a.shape[0]
+        ids = None
+        if streams is not None:
+            ids = np.asarray(streams)
+            if ids.dtype.kind not in "iu" or ids.shape != (W,) or (ids < 0).any():
+                raise ParamError("search_poses: streams must be unsigned integers [W]")
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        if not 0 <= int(seed) < 1 << 64 or int(n_rounds) < 0 or int(max_evals) < 0:
+            raise ParamError("search_poses: seed must fit 64 bits; n_rounds and max_evals are counts")
+        lib = load_library()
+        tb = np.ascontiguousarray(tb, dtype=np.uint32)
+        T = tb.shape[0]
+        n = int(lib.mdx_energy_group_count(self._h))
+        opts = CSearchOpts(int(n_rounds), float(trans_amp), float(rot_amp), float(tors_amp), float(kT), int(seed),
+                           CFlexOpts(int(max_evals), float(f_tol), float(tau_tol), float(tors_tol), float(h_start), float(h_max),
+                                     FLEX_DIHEDRALS if dihedrals else 0))
+        y = np.zeros(a.shape, dtype=np.float32)
+        r = np.zeros((W, max(n, 1)), dtype=np.float32)
+        sc = np.zeros(W, dtype=np.float64)
+        e = np.zeros(W, dtype=np.float32)
+        br = np.zeros(W, dtype=np.uint32)
+        stt = np.zeros((W, 4), dtype=np.uint32)
+        _check(lib.mdx_search_poses(self._h, int(first), a.shape[1], W, a.ctypes.data_as(_fp),
+                                    None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint64)), int(root), T, tb.ctypes.data_as(_u32p),
+                                    C.byref(opts), y.ctypes.data_as(_fp), r.ctypes.data_as(_fp), n, sc.ctypes.data_as(C.POINTER(C.c_double)),
+                                    e.ctypes.data_as(_fp), br.ctypes.data_as(_u32p), stt.ctypes.data_as(_u32p)))
+        return y, (r[:, :n] if n else r[:, :0]), sc, e, br, stt
 
     # -- position restraints (include/mdx.h: E = k max(0, |x - r0| - b)^2) ------------------------------------------------
     def set_position_restraints(self, idx, ref=None, k=1.0, flat_bottom=None):
