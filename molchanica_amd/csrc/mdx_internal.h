@@ -288,10 +288,9 @@ struct DeviceState {
     uint8_t* ps_cls = nullptr; void* ps_p14 = nullptr; float* ps_stage = nullptr; double* ps_slab = nullptr; double* ps_rows = nullptr;
     // mdx_pose_forces: the units' fp64 partial forces [chunk][units][count][3], the summed forces [chunk][count][3], net force and torque [chunk][6]
     double* ps_fslab = nullptr; float* ps_fout = nullptr; float* ps_rigid = nullptr;
-    // mdx_refine_poses: frozen words, state records, accepted coordinates / rows / rigid and the input poses of one chunk (RefineLayout)
-    void* ps_refine = nullptr;
-    // mdx_refine_poses_flex: the same block with the flexible state records and the per-term dihedral energies (FlexLayout); the table of
-    // one torsion list: moving-set masks, the ligand's dihedral terms and the per-atom lists into them (FlexTable)
+    // mdx_refine_poses / mdx_refine_poses_flex: frozen words, state records (rigid or flexible), accepted coordinates / rows / rigid, the
+    // input poses and the per-term dihedral energies of one chunk (StepLayout), grown to what the call needs; the table of one torsion
+    // list: moving-set masks, the ligand's dihedral terms and the per-atom lists into them (FlexTable)
     void* ps_flex = nullptr; void* ps_flex_tab = nullptr;
     // mdx_search_poses: the search records, current and best coordinates, best rows / rigid and stream ids of one chunk (SearchLayout)
     void* ps_search = nullptr;
@@ -361,7 +360,7 @@ struct mdx_handle {
     uint64_t grp_epoch = 0;                                                       // ... counts the calls: what was derived from a map knows its age
     // mdx_score_poses (mdx_poses.hip): the range and the group map the intra-ligand table was built for, its group, its 1-4 records
     bool ps_valid = false; uint32_t ps_first = 0, ps_count = 0, ps_group = 0, ps_n14 = 0; uint64_t ps_epoch = 0;
-    size_t ps_cap_stage = 0, ps_cap_slab = 0, ps_cap_fslab = 0, ps_cap_refine = 0;
+    size_t ps_cap_stage = 0, ps_cap_slab = 0, ps_cap_fslab = 0;      // bytes of ps_stage, ps_slab (ps_rows with it), ps_fslab (ps_fout, ps_rigid)
     // mdx_refine_poses_flex: what ps_flex_tab was built for (with ps_first / ps_count / ps_epoch) and how many dihedral terms it holds
     bool fx_valid = false; uint32_t fx_first = 0, fx_count = 0, fx_root = 0, fx_flags = 0, fx_terms = 0; uint64_t fx_epoch = 0;
     std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0, ps_cap_search = 0;

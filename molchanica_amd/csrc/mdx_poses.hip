@@ -40,16 +40,25 @@
 // mdx_refine_poses: a rigid-body steepest descent of every pose of the batch with its own adaptive step length (the rule of
 // mdx_minimize_energy carried over to rigid motions; mdx_refine_step.h holds its arithmetic), max_evals x (the force flavour,
 // pose_refine_step_kernel) per chunk on the stream, one read-back and one wait at the end.
-//   pose_refine_step_kernel  one workgroup per pose.  It adds the units' rows and forces as the two sum kernels do, forms rigid as
+//   pose_step<FLEX>  the body of both step kernels, one workgroup per pose (pose_refine_step_kernel is pose_step<false>,
+//       pose_flex_step_kernel is pose_step<true>: two plain kernels, one body).  It adds the units' rows and forces as the two sum kernels do, forms rigid as
 //       pose_force_sum_kernel does, accepts or rejects the trial from the pose's state record, and writes the next trial into the
 //       staging buffer the force flavour reads.  A pose that has finished sets its word in frozen[]; the REFINE instantiation of
 //       pose_score_kernel reads it before anything else and the whole workgroup returns, as the step kernel's does.
 //
-// mdx_refine_poses_flex: the same loop with the ligand's torsion angles as further coordinates (pose_flex_step_kernel, mdx_flex_step.h).
+// mdx_refine_poses_flex: the same loop with the ligand's torsion angles as further coordinates (pose_flex_step_kernel,
+// mdx_flex_step.h): the torsion and dihedral parts of pose_step, compiled in by `if constexpr (FLEX)`.
 //
 // mdx_search_poses: n_rounds of that loop per walker with pose_search_kernel between two of them (mdx_search_step.h): it decides the
 // round that ended - Metropolis on the refinement's objective, current and best pose in the walker's search record - and perturbs the
 // current pose into the staging buffer for the next; n_rounds x (1 + 2 max_evals) + 1 launches per chunk, one read-back, one wait.
+//
+// What is written once: the unit-order sum of a slab (pose_units_sum: the four kernels that add the 17 units take it from there, which
+// is why rows_out / rigid_out of a refinement are the bits mdx_score_poses / mdx_pose_forces return), the stages of an evaluation
+// (step_gather, step_store, step_max_speed; centroid, rigid and inertia stand once in pose_step), the B(theta) loop
+// (pose_build_torsions: the flexible step kernel and the search kernel), and on the host the Coulomb dispatch (pose_launch),
+// buffer growth (pose_grow), the block of a chunk (StepLayout), the option checks (refine_opts_check) and the chunk loop with its
+// unpacker (refine_chunks, refine_unpack).
 #include "mdx_bonded_dev.h"
 #include "mdx_pair_dev.h"
 #include "mdx_refine_step.h"
@@ -57,6 +66,7 @@
 #include "mdx_search_step.h"
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #define FAIL(code, msg) do { mdx_set_error(msg); return (code); } while (0)
 
@@ -302,14 +312,18 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
         }
 }
 
+// one element of a pose's slab, its POSE_UNITS + 1 partial sums added in unit order: the only place that order is written
+__device__ __forceinline__ double pose_units_sum(const double* s, size_t stride) {
+    double v = 0.0;
+    for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * stride];
+    return v;
+}
+
 __global__ __launch_bounds__(256) void pose_sum_kernel(uint32_t n, uint32_t G, const double* __restrict__ slab, double* __restrict__ rows) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * G) return;
     const uint32_t pose = i / G, b = i - pose * G;
-    const double* s = slab + (size_t)pose * (POSE_UNITS + 1u) * G + b;
-    double v = 0.0;
-    for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * G];
-    rows[i] = v;
+    rows[i] = pose_units_sum(slab + (size_t)pose * (POSE_UNITS + 1u) * G + b, G);
 }
 
 // component k of (sum_i f_i, sum_i (x_i - c) x f_i), atoms in order: the one statement both kernels below take rigid from
@@ -331,8 +345,7 @@ __global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, con
         const double* s = fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
         const size_t at = ((size_t)pose * count + tid) * 3u;
         for (uint32_t c = 0; c < 3u; ++c) {
-            double v = 0.0;
-            for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * count * 3u + c];
+            const double v = pose_units_sum(s + c, (size_t)count * 3u);
             s_v[tid][c] = v; s_x[tid][c] = (double)poses[at + c];
             forces[at + c] = (float)v;
         }
@@ -347,111 +360,264 @@ __global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, con
     if (tid < 6u) rigid[(size_t)pose * 6u + tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
 }
 
-struct RefineArgs {
-    uint32_t count, G;
+#define FLEX_TERM_WORDS 13u      // per dihedral term and evaluation: energy, then the forces on its four atoms
+
+// The step kernel's arguments, both instantiations; the rigid one leaves T, n_terms, eterm and the table pointers zero.
+struct StepArgs {
+    uint32_t count, G, T, n_terms;
     float* stage;                  // [poses of the chunk][count][3]: the trial the force flavour evaluated; receives the next one
     const double* slab; const double* fslab;
-    uint32_t* frozen; mdx_rf_state* st;
+    uint32_t* frozen; void* st;    // st: [poses of the chunk] mdx_rf_state (rigid) or mdx_fx_state (flexible)
     float* x0;                     // [..][count][3] the input poses (kept at evaluation 0)
     float* y; float* row; float* rigid;      // the accepted state: coordinates [..][count][3], row [..][G], rigid [..][6]
-    mdx_rf_opts o;
+    double* eterm;                 // [poses of the chunk][n_terms][13]: energy and the four atoms' forces of every term at this evaluation
+    const mdx_fx_torsion* tor; const mdx_fx_dihedral* dih; const uint32_t* aoff; const uint32_t* aent;
+    double box[3];                 // periodic axes (0: none), as the force pass has them
+    mdx_fx_opts o;
 };
 
-// One evaluation of every live pose ends here: rows and forces of the 17 units added in unit order and rounded where pose_sum_kernel /
-// pose_run and pose_force_sum_kernel round them, rigid by the statement of pose_force_sum_kernel, then the stepper of mdx_refine_step.h.
-// Thread 0 takes the decisions (a few dozen fp64 operations); the sums over atoms run one component per thread, in atom order.
-__global__ __launch_bounds__(256) void pose_refine_step_kernel(RefineArgs a) {
-    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_c[3], s_I[6], s_R[9], s_m[4];
-    __shared__ float s_row[256], s_rigid[6];
-    __shared__ mdx_rf_state s_st;
-    __shared__ uint32_t s_bad, s_flags;
-    const uint32_t tid = threadIdx.x, pose = blockIdx.x, count = a.count;
-    if (a.frozen[pose] != 0u) return;      // (uniform over the workgroup, before any barrier)
-    if (tid == 0u) { s_bad = 0u; s_st = a.st[pose]; }
-    __syncthreads();
+__device__ __forceinline__ mdx_rf_state& rf_of(mdx_rf_state& s) { return s; }
+__device__ __forceinline__ mdx_rf_state& rf_of(mdx_fx_state& s) { return s.rf; }
+
+// ---- the stages of one evaluation (LDS arrays are the caller's) ----
+// Rows and forces of the 17 units added in unit order and rounded where pose_sum_kernel / pose_run and pose_force_sum_kernel round
+// them, the staged trial in fp64; WITH_F (flexible): s_f takes the fp32 force mdx_pose_forces returns - what a host loop has.
+// A non-finite value raises *s_bad.  Ends with a barrier.
+template <bool WITH_F>
+__device__ __forceinline__ void step_gather(const StepArgs& a, uint32_t pose, uint32_t tid, float* s_row, double (*s_v)[3], double (*s_x)[3],
+                                            double (*s_f)[3], uint32_t* s_bad) {
+    const uint32_t count = a.count;
     bool bad = false;
     if (tid < a.G) {
-        const double* s = a.slab + (size_t)pose * (POSE_UNITS + 1u) * a.G + tid;
-        double v = 0.0;
-        for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * a.G];
-        const float r = (float)v;
+        const float r = (float)pose_units_sum(a.slab + (size_t)pose * (POSE_UNITS + 1u) * a.G + tid, a.G);
         s_row[tid] = r;
         bad = !isfinite(r);
     }
-    const size_t at = ((size_t)pose * count + tid) * 3u;
     if (tid < count) {
         const double* s = a.fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
+        const size_t at = ((size_t)pose * count + tid) * 3u;
         for (uint32_t c = 0; c < 3u; ++c) {
-            double v = 0.0;
-            for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * count * 3u + c];
+            const double v = pose_units_sum(s + c, (size_t)count * 3u);
             s_v[tid][c] = v; s_x[tid][c] = (double)a.stage[at + c];
+            if constexpr (WITH_F) s_f[tid][c] = (double)(float)v;
             bad = bad || !isfinite((float)v);
         }
     }
-    if (bad) s_bad = 1u;      // (every writer stores the same word)
+    if (bad) *s_bad = 1u;      // (every writer stores the same word)
     __syncthreads();
+}
+
+// the accepted state leaves for the chunk's block: coordinates, row and rigid of a stored trial; the input pose at evaluation 1
+__device__ __forceinline__ void step_store(const StepArgs& a, uint32_t pose, uint32_t tid, uint32_t fl, bool first, const float* s_row,
+                                           const float* s_rigid) {
+    const size_t at = ((size_t)pose * a.count + tid) * 3u;
+    if (fl & MDX_RF_STORE) {
+        if (tid < a.count)
+            for (uint32_t c = 0; c < 3u; ++c) a.y[at + c] = a.stage[at + c];
+        if (tid < a.G) a.row[(size_t)pose * a.G + tid] = s_row[tid];
+        if (tid < 6u) a.rigid[(size_t)pose * 6u + tid] = s_rigid[tid];
+    }
+    if (first && tid < a.count)
+        for (uint32_t c = 0; c < 3u; ++c) a.x0[at + c] = a.stage[at + c];
+}
+
+// the largest atom speed of the new direction (a maximum: exact in any order) from every thread's m; thread 0 hands it to
+// rf_set_speed.  Two barriers; returns the flags with rf_set_speed's.
+__device__ __forceinline__ uint32_t step_max_speed(double m, uint32_t tid, uint32_t fl, mdx_rf_state& rf, double* s_m, uint32_t* s_flags) {
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
+    if ((tid & 63u) == 0u) s_m[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0u) {
+        double mm = s_m[0];
+        for (int k = 1; k < 4; ++k) mm = s_m[k] > mm ? s_m[k] : mm;
+        *s_flags = fl | rf_set_speed(rf, mm);
+    }
+    __syncthreads();
+    return *s_flags;
+}
+
+// B(theta) in place: s_x holds the pose in fp64; the torsions in order, each a rotation of its moving set about its axis as the
+// coordinates then stand (fx_build with the atoms over the threads).  One barrier per non-zero torsion: the axis of torsion k depends on
+// the rotations before it, and the axis atoms are not written in their own round.  tor may lie in LDS or in global memory.
+__device__ __forceinline__ void pose_build_torsions(double (*s_x)[3], const mdx_fx_torsion* tor, const double* th, const double* cs,
+                                                    const double* sn, uint32_t T, uint32_t count, uint32_t tid) {
+    for (uint32_t k = 0; k < T; ++k) {
+        if (th[k] == 0.0) continue;      // (uniform over the workgroup)
+        const mdx_fx_torsion& t = tor[k];
+        double u[3];
+        const bool turns = fx_axis(&s_x[0][0], t, u);
+        if (turns && tid < count && tid != t.b && fx_member(t.mask, tid)) {
+            const double b[3] = {s_x[t.b][0], s_x[t.b][1], s_x[t.b][2]};
+            fx_rotate(u, b, cs[k], sn[k], s_x[tid]);
+        }
+        __syncthreads();
+    }
+}
+
+// One evaluation of every live pose ends here: gather, frame, then the stepper of mdx_refine_step.h (FLEX: mdx_flex_step.h).  Thread 0
+// takes the decisions (a few dozen fp64 operations); the sums over atoms run one component per thread, in atom order.
+// FLEX adds the dihedral terms (thread t: term t, its energy and four forces through eterm; one thread adds the energies in list order
+// while thread i gathers the forces of the terms that name atom i, in list order), g_k / J_k (thread k, members in atom order), the
+// torsion part of the atom field, and the trial builder: B(theta) in LDS from the input pose, then the rigid image of it.  The rigid
+// instantiation names none of the FLEX arrays (they take no LDS there) and forms the next trial from x0 by rf_coords.
+template <bool FLEX>
+__device__ __forceinline__ void pose_step(const StepArgs& a) {
+    using State = typename std::conditional<FLEX, mdx_fx_state, mdx_rf_state>::type;
+    // s_f, s_g .. s_bc, s_edih and s_tor are FLEX only.  The rigid instantiation must read and write none of them (s_f is handed to
+    // step_gather<false>, which does not touch it): an array nobody uses takes no LDS, and that is all that keeps the rigid kernel at
+    // 13,752 B and 8 workgroups per CU.  After a change here, read "LDS Size" of both instantiations in the
+    // -Rpass-analysis=kernel-resource-usage remarks (13,752 / 26,088 B).  The order of the declarations is the LDS layout's.
+    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_f[MDX_POSE_MAX_ATOMS][3], s_c[3], s_I[6], s_R[9], s_m[4];
+    __shared__ double s_g[MDX_FX_MAX_TORSIONS], s_J[MDX_FX_MAX_TORSIONS], s_A[MDX_FX_MAX_TORSIONS][3], s_u[MDX_FX_MAX_TORSIONS][3],
+                      s_sh[MDX_FX_MAX_TORSIONS][3], s_wk[MDX_FX_MAX_TORSIONS], s_cs[MDX_FX_MAX_TORSIONS], s_sn[MDX_FX_MAX_TORSIONS], s_bc[3];
+    __shared__ float s_row[256], s_rigid[6], s_edih;
+    __shared__ State s_st;
+    __shared__ mdx_fx_torsion s_tor[MDX_FX_MAX_TORSIONS];
+    __shared__ uint32_t s_bad, s_flags;
+    const uint32_t tid = threadIdx.x, pose = blockIdx.x, count = a.count, T = a.T;
+    if (a.frozen[pose] != 0u) return;      // (uniform over the workgroup, before any barrier)
+    uint32_t* const rec = (uint32_t*)((State*)a.st + pose);
+    for (uint32_t i = tid; i < sizeof(State) / 4u; i += 256u) ((uint32_t*)&s_st)[i] = rec[i];
+    if constexpr (FLEX)
+        for (uint32_t i = tid; i < T * (uint32_t)(sizeof(mdx_fx_torsion) / 4u); i += 256u) ((uint32_t*)s_tor)[i] = ((const uint32_t*)a.tor)[i];
+    if (tid == 0u) s_bad = 0u;
+    __syncthreads();
+    mdx_rf_state& rf = rf_of(s_st);
+    step_gather<FLEX>(a, pose, tid, s_row, s_v, s_x, s_f, &s_bad);      // (s_f: written under FLEX only)
+    // centroid | barrier | rigid by the statement of pose_force_sum_kernel beside the six inertia sums on a wave of their own; the
+    // FLEX parts share those two intervals, so the three statements stand here and not in a helper
     if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
+    double* eterm = nullptr;
+    if constexpr (FLEX) {
+        // the ligand's dihedral terms, one term per thread: its energy and its four forces go through eterm
+        eterm = a.eterm + (size_t)pose * a.n_terms * FLEX_TERM_WORDS;
+        const double box[3] = {a.box[0], a.box[1], a.box[2]};
+        for (uint32_t t = tid; t < a.n_terms; t += 256u) {
+            double f[4][3];
+            double* o = eterm + (size_t)t * FLEX_TERM_WORDS;
+            o[0] = fx_dihedral(&s_x[0][0], a.dih[t], box, f);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { o[1 + 3 * r] = f[r][0]; o[2 + 3 * r] = f[r][1]; o[3 + 3 * r] = f[r][2]; }
+        }
+    }
     __syncthreads();
     if (tid < 6u) s_rigid[tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
-    if (tid >= 64u && tid < 70u) s_I[tid - 64u] = rf_inertia(&s_x[0][0], count, s_c, tid - 64u);      // (a wave of its own, beside rigid)
+    if (tid >= 64u && tid < 70u) s_I[tid - 64u] = rf_inertia(&s_x[0][0], count, s_c, tid - 64u);
+    if constexpr (FLEX) {
+        if (tid == 128u) {      // the energies in list order
+            double e = 0.0;
+            for (uint32_t t = 0; t < a.n_terms; ++t) e += eterm[(size_t)t * FLEX_TERM_WORDS];
+            s_edih = (float)e;
+        }
+        if (tid < count && a.n_terms) {
+            // thread i: the forces of the terms that name atom i, in list order - the atom-owned gather
+            double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+            for (uint32_t e = a.aoff[tid]; e < a.aoff[tid + 1u]; ++e) {
+                const uint32_t w = a.aent[e];
+                const double* o = eterm + (size_t)(w >> 2) * FLEX_TERM_WORDS + 1u + 3u * (w & 3u);
+                f0 += o[0]; f1 += o[1]; f2 += o[2];
+            }
+            if (!isfinite(f0) || !isfinite(f1) || !isfinite(f2)) s_bad = 1u;
+            s_f[tid][0] += f0; s_f[tid][1] += f1; s_f[tid][2] += f2;
+        }
+        __syncthreads();
+        if (tid < T) {
+            const double n = (double)count;
+            const double v[3] = {(double)s_rigid[0] / n, (double)s_rigid[1] / n, (double)s_rigid[2] / n};
+            fx_gradient(&s_x[0][0], &s_f[0][0], count, v, s_tor[tid], s_u[tid], s_g[tid], s_J[tid], s_A[tid]);
+        }
+    }
     __syncthreads();
     if (tid == 0u) {
         bool finite = s_bad == 0u;
         for (int k = 0; k < 6; ++k) finite = finite && isfinite(s_rigid[k]);
         double S = 0.0;
         for (uint32_t b = 0; b < a.G; ++b) S += (double)s_row[b];
-        if (s_st.evals == 0u) rf_start(s_st, s_c, a.o.h_start);      // (the record was zeroed: the trial is the input pose)
-        const uint32_t fl = rf_decide(s_st, a.o, S, finite, s_rigid);
-        if (fl == MDX_RF_STORE) rf_direction(s_st, count, s_rigid, s_I);
+        uint32_t fl;
+        if constexpr (FLEX) {
+            double gmax = 0.0;
+            finite = finite && isfinite(s_edih);      // (here: read ahead of the row sum, the evaluation measured 0.3 us slower)
+            S += (double)s_edih;
+            for (uint32_t k = 0; k < T; ++k) {
+                const double g = fabs(s_g[k]);
+                finite = finite && isfinite(g);
+                gmax = g > gmax ? g : gmax;
+            }
+            if (rf.evals == 0u) fx_start(s_st, s_c, a.o.rf.h_start);      // (the record was zeroed: the trial is the input pose)
+            fl = fx_decide(s_st, a.o, T, S, finite, s_rigid, gmax);
+            if (fl & MDX_RF_STORE) {
+                s_st.edih = s_edih;
+                for (uint32_t k = 0; k < T; ++k) s_st.g[k] = s_g[k];
+            }
+        } else {
+            if (rf.evals == 0u) rf_start(rf, s_c, a.o.rf.h_start);        // (likewise)
+            fl = rf_decide(rf, a.o.rf, S, finite, s_rigid);
+        }
+        if (fl == MDX_RF_STORE) rf_direction(rf, count, s_rigid, s_I);
         s_flags = fl;
     }
+    if constexpr (FLEX)
+        if (tid >= 64u && tid < 64u + T) {      // (a wave beside thread 0's: used only if the trial is stored and the pose goes on)
+            const uint32_t k = tid - 64u;
+            s_wk[k] = fx_omega(s_g[k], s_J[k]);
+            fx_shift(s_wk[k], s_A[k], count, s_sh[k]);
+        }
     __syncthreads();
-    const bool first = s_st.evals == 1u;
+    if constexpr (FLEX)
+        if (s_flags == MDX_RF_STORE && tid < T) s_st.wk[tid] = s_wk[tid];      // (read again only after the next barrier)
     uint32_t fl = s_flags;
-    if (fl & MDX_RF_STORE) {
-        if (tid < count)
-            for (uint32_t c = 0; c < 3u; ++c) a.y[at + c] = a.stage[at + c];
-        if (tid < a.G) a.row[(size_t)pose * a.G + tid] = s_row[tid];
-        if (tid < 6u) a.rigid[(size_t)pose * 6u + tid] = s_rigid[tid];
-    }
-    if (first && tid < count)
-        for (uint32_t c = 0; c < 3u; ++c) a.x0[at + c] = a.stage[at + c];
+    step_store(a, pose, tid, fl, rf.evals == 1u, s_row, s_rigid);
     if (fl == MDX_RF_STORE) {
-        // the largest atom speed of the new direction (a maximum: exact in any order)
         double m = 0.0;
         if (tid < count) {
-            const double r[3] = {s_x[tid][0] - s_c[0], s_x[tid][1] - s_c[1], s_x[tid][2] - s_c[2]};
-            m = rf_speed(s_st.v, s_st.w, r);
+            if constexpr (FLEX) m = fx_speed(rf.v, rf.w, s_c, &s_x[0][0], tid, T, s_tor, s_u, s_wk, s_sh);
+            else {
+                const double r[3] = {s_x[tid][0] - s_c[0], s_x[tid][1] - s_c[1], s_x[tid][2] - s_c[2]};
+                m = rf_speed(rf.v, rf.w, r);
+            }
         }
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
-        if ((tid & 63u) == 0u) s_m[tid >> 6] = m;
-        __syncthreads();
+        fl = step_max_speed(m, tid, fl, rf, s_m, &s_flags);
+    }
+    const size_t at = ((size_t)pose * count + tid) * 3u;
+    if (!(fl & MDX_RF_FROZEN)) {
         if (tid == 0u) {
-            double mm = s_m[0];
-            for (int k = 1; k < 4; ++k) mm = s_m[k] > mm ? s_m[k] : mm;
-            s_flags = fl = fl | rf_set_speed(s_st, mm);
+            if constexpr (FLEX) fx_trial(s_st, T); else rf_trial(rf);
+            rf_rotation(rf.qt, s_R);
         }
-        __syncthreads();
-        fl = s_flags;
-    }
-    if (fl & MDX_RF_FROZEN) {
-        if (tid == 0u) { a.st[pose] = s_st; a.frozen[pose] = 1u; }
-        return;
-    }
-    if (tid == 0u) {
-        rf_trial(s_st);
-        rf_rotation(s_st.qt, s_R);
-        a.st[pose] = s_st;
+        if constexpr (FLEX) {
+            // B(theta_try) from the input pose: s_x is free now
+            if (tid < count)
+                for (uint32_t c = 0; c < 3u; ++c) s_x[tid][c] = (double)a.x0[at + c];
+            __syncthreads();
+            if (tid < T) { s_cs[tid] = cos(s_st.tht[tid]); s_sn[tid] = sin(s_st.tht[tid]); }
+            __syncthreads();
+            pose_build_torsions(s_x, s_tor, s_st.tht, s_cs, s_sn, T, count, tid);
+            if (tid < 3u) s_bc[tid] = rf_mean(&s_x[0][0], count, tid);
+        }
     }
     __syncthreads();
+    for (uint32_t i = tid; i < sizeof(State) / 4u; i += 256u) rec[i] = ((const uint32_t*)&s_st)[i];
+    if (fl & MDX_RF_FROZEN) {
+        if (tid == 0u) a.frozen[pose] = 1u;
+        return;
+    }
     if (tid < count) {
-        const float x0[3] = {a.x0[at], a.x0[at + 1u], a.x0[at + 2u]};
         float y[3];
-        rf_coords(s_st.c0, s_st.tt, s_R, x0, y);
+        if constexpr (FLEX) fx_coords(rf.c0, rf.tt, s_R, s_x[tid], s_bc, y);
+        else {
+            const float x0[3] = {a.x0[at], a.x0[at + 1u], a.x0[at + 2u]};
+            rf_coords(rf.c0, rf.tt, s_R, x0, y);
+        }
         for (uint32_t c = 0; c < 3u; ++c) a.stage[at + c] = y[c];
     }
 }
+
+// The two step kernels: one body, two plain kernels under the names they had as separate copies.  (A kernel template
+// pose_step_kernel<FLEX> gave the same instructions but left its instantiations behind the 24 pose_score_kernel ones in the code
+// object; it measured 0.5 % slower in the flexible arm and no cause was found in the instructions - DESIGN.md 7h.)
+__global__ __launch_bounds__(256) void pose_refine_step_kernel(StepArgs a) { pose_step<false>(a); }
+__global__ __launch_bounds__(256) void pose_flex_step_kernel(StepArgs a) { pose_step<true>(a); }
 
 template <int COUL>
 static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force, bool refine = false) {
@@ -466,6 +632,28 @@ static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n
         else hipLaunchKernelGGL((pose_score_kernel<COUL, false, true>), g, b, lds, h->stream, a);
     } else if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, false>), g, b, 0, h->stream, a);
     else hipLaunchKernelGGL((pose_score_kernel<COUL, false, false>), g, b, 0, h->stream, a);
+}
+
+// the pose pass of n poses under the handle's Coulomb treatment
+static void pose_launch(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, bool force, bool refine) {
+    switch (mode) {
+    case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, force, refine); break;
+    case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, force, refine); break;
+    case CM_RF: launch_poses<CM_RF>(h, a, geom, n, force, refine); break;
+    default: launch_poses<CM_EWALD>(h, a, geom, n, force, refine); break;
+    }
+}
+
+// A device buffer grows to `need` bytes: free, zero the capacity, hipMalloc, set the capacity - a failure leaves the capacity 0 and the
+// pointer null, so the next call starts over.  Buffers that share a capacity: the followers grow on a zero capacity of their own
+// behind the test of the shared one, the leader last with the shared one.
+static int pose_grow(void** p, size_t& cap, size_t need) {
+    if (cap >= need) return MDX_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    cap = 0;
+    HIP_TRY(hipMalloc(p, need));
+    cap = need;
+    return MDX_OK;
 }
 
 // The ligand's own pairs, once per (range, group map): who is excluded, who is a scaled 1-4 pair and with what parameters - from the
@@ -517,10 +705,9 @@ static int pose_table(mdx_handle* h, const std::string& who, uint32_t first, uin
             if (skip14 || pi >= prm.size()) continue;      // (bonded terms disabled: the matrix leaves the scaled pairs out too)
             p14.push_back(Pose14{i, b, prm[pi].x, prm[pi].y, prm[pi].z});
         }
-    if (d.ps_cls) { (void)hipFree(d.ps_cls); d.ps_cls = nullptr; }
-    if (d.ps_p14) { (void)hipFree(d.ps_p14); d.ps_p14 = nullptr; }
-    HIP_TRY(hipMalloc((void**)&d.ps_cls, cls.size()));
-    HIP_TRY(hipMalloc((void**)&d.ps_p14, sizeof(Pose14) * std::max<size_t>(p14.size(), 1)));
+    size_t c0 = 0, c1 = 0;      // (a new table: both buffers are made anew)
+    MDX_TRY(pose_grow((void**)&d.ps_cls, c0, cls.size()));
+    MDX_TRY(pose_grow(&d.ps_p14, c1, sizeof(Pose14) * std::max<size_t>(p14.size(), 1)));
     HIP_TRY(hipMemcpyAsync(d.ps_cls, cls.data(), cls.size(), hipMemcpyHostToDevice, st));
     if (!p14.empty()) HIP_TRY(hipMemcpyAsync(d.ps_p14, p14.data(), sizeof(Pose14) * p14.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -559,29 +746,21 @@ static int pose_setup(mdx_handle* h, const std::string& who, uint32_t first, uin
     }
     MDX_TRY(mdx_ensure_ready(h));          // what the matrix would see: list, constraints and virtual sites of the current state
     DeviceState& d = h->d;
-    const uint32_t chunk = std::min(n_poses, POSE_CHUNK);
-    if (h->ps_cap_stage < per_pose * chunk) {
-        if (d.ps_stage) { (void)hipFree(d.ps_stage); d.ps_stage = nullptr; }
-        h->ps_cap_stage = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_stage, sizeof(float) * per_pose * POSE_CHUNK));
-        h->ps_cap_stage = per_pose * POSE_CHUNK;
-    }
-    if (h->ps_cap_slab < (size_t)G) {
-        if (d.ps_slab) { (void)hipFree(d.ps_slab); d.ps_slab = nullptr; }
-        if (d.ps_rows) { (void)hipFree(d.ps_rows); d.ps_rows = nullptr; }
+    // capacities in bytes, every buffer for a whole chunk; ps_rows shares ps_slab's, ps_fout and ps_rigid share ps_fslab's
+    const size_t slab = sizeof(double) * (size_t)POSE_CHUNK * (POSE_UNITS + 1u) * G, fslab = sizeof(double) * (size_t)POSE_CHUNK * (POSE_UNITS + 1u) * per_pose;
+    MDX_TRY(pose_grow((void**)&d.ps_stage, h->ps_cap_stage, sizeof(float) * per_pose * POSE_CHUNK));
+    if (h->ps_cap_slab < slab) {
+        size_t c = 0;
         h->ps_cap_slab = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_slab, sizeof(double) * (size_t)POSE_CHUNK * (POSE_UNITS + 1u) * G));
-        HIP_TRY(hipMalloc((void**)&d.ps_rows, sizeof(double) * (size_t)POSE_CHUNK * G));
-        h->ps_cap_slab = G;
+        MDX_TRY(pose_grow((void**)&d.ps_rows, c, sizeof(double) * (size_t)POSE_CHUNK * G));
+        MDX_TRY(pose_grow((void**)&d.ps_slab, h->ps_cap_slab, slab));
     }
-    if (force && h->ps_cap_fslab < per_pose) {
-        if (d.ps_fslab) { (void)hipFree(d.ps_fslab); d.ps_fslab = nullptr; }
-        if (d.ps_fout) { (void)hipFree(d.ps_fout); d.ps_fout = nullptr; }
+    if (force && h->ps_cap_fslab < fslab) {
+        size_t c0 = 0, c1 = 0;
         h->ps_cap_fslab = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_fslab, sizeof(double) * (size_t)POSE_CHUNK * (POSE_UNITS + 1u) * per_pose));
-        HIP_TRY(hipMalloc((void**)&d.ps_fout, sizeof(float) * (size_t)POSE_CHUNK * per_pose));
-        if (!d.ps_rigid) HIP_TRY(hipMalloc((void**)&d.ps_rigid, sizeof(float) * (size_t)POSE_CHUNK * 6u));
-        h->ps_cap_fslab = per_pose;
+        MDX_TRY(pose_grow((void**)&d.ps_fout, c0, sizeof(float) * (size_t)POSE_CHUNK * per_pose));
+        MDX_TRY(pose_grow((void**)&d.ps_rigid, c1, sizeof(float) * (size_t)POSE_CHUNK * 6u));
+        MDX_TRY(pose_grow((void**)&d.ps_fslab, h->ps_cap_fslab, fslab));
     }
     a = PoseArgs{};
     bool samecut = false;
@@ -617,12 +796,7 @@ static int pose_run(mdx_handle* h, const std::string& who, uint32_t first, uint3
         const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
         HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
         mdx_prof_begin(h, 0);
-        switch (mode) {
-        case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, force); break;
-        case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, force); break;
-        case CM_RF: launch_poses<CM_RF>(h, a, geom, n, force); break;
-        default: launch_poses<CM_EWALD>(h, a, geom, n, force); break;
-        }
+        pose_launch(h, a, mode, geom, n, force, false);
         hipLaunchKernelGGL(pose_sum_kernel, dim3((n * G + 255u) / 256u), dim3(256), 0, st, n, G, d.ps_slab, d.ps_rows);
         if (force) hipLaunchKernelGGL(pose_force_sum_kernel, dim3(n), dim3(256), 0, st, count, d.ps_stage, d.ps_fslab, d.ps_fout, d.ps_rigid);
         mdx_prof_end(h);
@@ -664,103 +838,24 @@ extern "C" int mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, ui
     return pose_run(h, "mdx_pose_forces", first, count, n_poses, poses, rows_or_null, n_groups, forces, rigid_or_null);
 }
 
-// The refinement's own device block of a chunk of n poses: [frozen words | state records | accepted coordinates | rows | rigid |
-// input poses]; the first two are zeroed at the start of the chunk, records .. rigid come back in one copy at its end.
-struct RefineLayout {
-    size_t frozen, state, y, row, rigid, x0, end;
-    RefineLayout(uint32_t n, size_t per_pose, uint32_t G) {
+// ---- mdx_refine_poses and mdx_refine_poses_flex: one loop, the rigid and the flexible state record ---------------------------------------
+// The refinement's device block of a chunk of n poses (ps_flex): [frozen words | state records | accepted coordinates | rows | rigid |
+// input poses | the dihedral terms' energies and forces]; the first two are zeroed at the start of the chunk, records .. rigid come
+// back in one copy at its end.  state_bytes is sizeof(mdx_rf_state) or sizeof(mdx_fx_state); the rigid refinement has no terms.
+struct StepLayout {
+    size_t frozen, state, y, row, rigid, x0, eterm, end;
+    StepLayout(uint32_t n, size_t per_pose, uint32_t G, size_t state_bytes, uint32_t n_terms) {
         frozen = 0;
         state = ((sizeof(uint32_t) * n + 15u) / 16u) * 16u;
-        y = state + sizeof(mdx_rf_state) * n;
+        y = state + state_bytes * n;
         row = y + sizeof(float) * per_pose * n;
         rigid = row + sizeof(float) * (size_t)G * n;
         x0 = rigid + sizeof(float) * 6u * n;
-        end = x0 + sizeof(float) * per_pose * n;
+        eterm = ((x0 + sizeof(float) * per_pose * n + 15u) / 16u) * 16u;
+        end = eterm + sizeof(double) * FLEX_TERM_WORDS * (size_t)n_terms * n;
     }
 };
 
-extern "C" int mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses,
-                                const mdx_refine_opts* opts, float* poses_out, float* rows_out_or_null, uint32_t n_groups,
-                                float* rigid_out_or_null, float* xform_out_or_null, uint32_t* status_out_or_null,
-                                uint32_t* evals_out_or_null) {
-    const std::string who = "mdx_refine_poses";
-    if (!h) FAIL(MDX_EPARAM, "null handle");
-    if (n_poses == 0) return MDX_OK;
-    if (!poses || !poses_out || !opts) FAIL(MDX_EPARAM, "null argument");
-    if (opts->max_evals == 0 || opts->max_evals > MDX_REFINE_MAX_EVALS_CAP) FAIL(MDX_EPARAM, who + ": max_evals must be in 1..MDX_REFINE_MAX_EVALS_CAP (4096)");
-    for (float v : {opts->f_tol, opts->tau_tol, opts->h_start, opts->h_max})
-        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": a tolerance or step length is negative or not finite");
-    mdx_rf_opts o{(double)opts->f_tol, (double)opts->tau_tol, opts->h_start > 0.f ? (double)opts->h_start : 0.01,
-                  opts->h_max > 0.f ? (double)opts->h_max : 0.2};
-    if (o.h_start > o.h_max) FAIL(MDX_EPARAM, who + ": h_start exceeds h_max");
-    PoseArgs a{};
-    int mode = 0; bool geom = false;
-    MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, true, a, mode, geom));
-    DeviceState& d = h->d;
-    hipStream_t st = h->stream;
-    const uint32_t G = h->n_grp;
-    const size_t per_pose = 3 * (size_t)count;
-    const size_t need = RefineLayout(POSE_CHUNK, per_pose, G).end;
-    if (h->ps_cap_refine < need) {
-        if (d.ps_refine) { (void)hipFree(d.ps_refine); d.ps_refine = nullptr; }
-        h->ps_cap_refine = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_refine, need));
-        h->ps_cap_refine = need;
-    }
-    std::vector<float> yres(per_pose * n_poses), rres((size_t)n_poses * G), gres(6u * (size_t)n_poses), xres(7u * (size_t)n_poses);
-    std::vector<uint32_t> sres(n_poses), eres(n_poses);
-    std::vector<unsigned char> back;
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
-        const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
-        const RefineLayout lay(n, per_pose, G);
-        unsigned char* blk = (unsigned char*)d.ps_refine;
-        RefineArgs r{};
-        r.count = count; r.G = G; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
-        r.frozen = (uint32_t*)(blk + lay.frozen); r.st = (mdx_rf_state*)(blk + lay.state);
-        r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
-        r.o = o;
-        a.frozen = r.frozen;
-        HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(blk, 0, lay.y, st));
-        mdx_prof_begin(h, 0);
-        for (uint32_t k = 0; k < opts->max_evals; ++k) {
-            switch (mode) {
-            case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, true, true); break;
-            case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, true, true); break;
-            case CM_RF: launch_poses<CM_RF>(h, a, geom, n, true, true); break;
-            default: launch_poses<CM_EWALD>(h, a, geom, n, true, true); break;
-            }
-            hipLaunchKernelGGL(pose_refine_step_kernel, dim3(n), dim3(256), 0, st, r);
-        }
-        mdx_prof_end(h);
-        HIP_TRY(hipGetLastError());
-        back.resize(lay.x0 - lay.state);
-        HIP_TRY(hipMemcpyAsync(back.data(), blk + lay.state, back.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const unsigned char* b0 = back.data() - lay.state;
-        std::memcpy(yres.data() + per_pose * p0, b0 + lay.y, sizeof(float) * per_pose * n);
-        std::memcpy(rres.data() + (size_t)p0 * G, b0 + lay.row, sizeof(float) * (size_t)G * n);
-        std::memcpy(gres.data() + 6u * (size_t)p0, b0 + lay.rigid, sizeof(float) * 6u * n);
-        for (uint32_t k = 0; k < n; ++k) {
-            mdx_rf_state s;
-            std::memcpy(&s, b0 + lay.state + sizeof(mdx_rf_state) * k, sizeof(s));
-            sres[p0 + k] = s.frozen ? s.status : MDX_REFINE_MAX_EVALS;
-            eres[p0 + k] = s.evals;
-            float* x = xres.data() + 7u * (size_t)(p0 + k);
-            for (int c = 0; c < 4; ++c) x[c] = (float)s.q[c];
-            for (int c = 0; c < 3; ++c) x[4 + c] = (float)s.t[c];
-        }
-    }
-    std::memcpy(poses_out, yres.data(), sizeof(float) * yres.size());
-    if (rows_out_or_null) std::memcpy(rows_out_or_null, rres.data(), sizeof(float) * rres.size());
-    if (rigid_out_or_null) std::memcpy(rigid_out_or_null, gres.data(), sizeof(float) * gres.size());
-    if (xform_out_or_null) std::memcpy(xform_out_or_null, xres.data(), sizeof(float) * xres.size());
-    if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
-    if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
-    return MDX_OK;
-}
-
-// ---- mdx_refine_poses_flex: the same loop with the ligand's torsion angles as further coordinates (mdx_flex_step.h) ---------------------
 // The table of one (range, torsion list, flags): the torsions with their moving-set masks, the ligand's dihedral terms in the system's
 // list order, and per ligand atom the (term, role) entries that name it, in list order too - the atom-owned gather.
 struct FlexTable {
@@ -774,208 +869,137 @@ struct FlexTable {
     }
 };
 
-#define FLEX_TERM_WORDS 13u      // per dihedral term and evaluation: energy, then the forces on its four atoms
-
-struct FlexArgs {
-    uint32_t count, G, T, n_terms;
-    float* stage;
-    const double* slab; const double* fslab;
-    uint32_t* frozen; mdx_fx_state* st;
-    float* x0; float* y; float* row; float* rigid;
-    double* eterm;                 // [poses of the chunk][n_terms][13]: energy and the four atoms' forces of every term at this evaluation
-    const mdx_fx_torsion* tor; const mdx_fx_dihedral* dih; const uint32_t* aoff; const uint32_t* aent;
-    double box[3];                 // periodic axes (0: none), as the force pass has them
-    mdx_fx_opts o;
-};
-
-// One evaluation of every live pose ends here.  Up to the decision this is pose_refine_step_kernel statement by statement; added are the
-// dihedral gather (thread i: the terms that name atom i, in list order; the terms' energies go through eterm and are added by one thread
-// in list order), g_k / J_k (thread k, members in atom order), the torsion part of the atom field, and the trial builder: B(theta) in LDS
-// with one barrier per non-zero torsion, then the rigid image of it.
-__global__ __launch_bounds__(256) void pose_flex_step_kernel(FlexArgs a) {
-    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_f[MDX_POSE_MAX_ATOMS][3], s_c[3], s_I[6], s_R[9], s_m[4];
-    __shared__ double s_g[MDX_FX_MAX_TORSIONS], s_J[MDX_FX_MAX_TORSIONS], s_A[MDX_FX_MAX_TORSIONS][3], s_u[MDX_FX_MAX_TORSIONS][3],
-                      s_sh[MDX_FX_MAX_TORSIONS][3], s_wk[MDX_FX_MAX_TORSIONS], s_cs[MDX_FX_MAX_TORSIONS], s_sn[MDX_FX_MAX_TORSIONS], s_bc[3];
-    __shared__ float s_row[256], s_rigid[6], s_edih;
-    __shared__ mdx_fx_state s_st;
-    __shared__ mdx_fx_torsion s_tor[MDX_FX_MAX_TORSIONS];
-    __shared__ uint32_t s_bad, s_flags;
-    const uint32_t tid = threadIdx.x, pose = blockIdx.x, count = a.count, T = a.T;
-    if (a.frozen[pose] != 0u) return;      // (uniform over the workgroup, before any barrier)
-    {
-        const uint32_t* src = (const uint32_t*)(a.st + pose);
-        for (uint32_t i = tid; i < sizeof(mdx_fx_state) / 4u; i += 256u) ((uint32_t*)&s_st)[i] = src[i];
-        for (uint32_t i = tid; i < T * (uint32_t)(sizeof(mdx_fx_torsion) / 4u); i += 256u) ((uint32_t*)s_tor)[i] = ((const uint32_t*)a.tor)[i];
-    }
-    if (tid == 0u) s_bad = 0u;
-    __syncthreads();
-    bool bad = false;
-    if (tid < a.G) {
-        const double* s = a.slab + (size_t)pose * (POSE_UNITS + 1u) * a.G + tid;
-        double v = 0.0;
-        for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * a.G];
-        const float r = (float)v;
-        s_row[tid] = r;
-        bad = !isfinite(r);
-    }
-    const size_t at = ((size_t)pose * count + tid) * 3u;
-    if (tid < count) {
-        const double* s = a.fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
-        for (uint32_t c = 0; c < 3u; ++c) {
-            double v = 0.0;
-            for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * count * 3u + c];
-            s_v[tid][c] = v; s_x[tid][c] = (double)a.stage[at + c];
-            s_f[tid][c] = (double)(float)v;      // (the fp32 force mdx_pose_forces returns: what a host loop has)
-            bad = bad || !isfinite((float)v);
-        }
-    }
-    if (bad) s_bad = 1u;      // (every writer stores the same word)
-    __syncthreads();
-    if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
-    // the ligand's dihedral terms, one term per thread: its energy and its four forces go through eterm
-    double* eterm = a.eterm + (size_t)pose * a.n_terms * FLEX_TERM_WORDS;
-    const double box[3] = {a.box[0], a.box[1], a.box[2]};
-    for (uint32_t t = tid; t < a.n_terms; t += 256u) {
-        double f[4][3];
-        double* o = eterm + (size_t)t * FLEX_TERM_WORDS;
-        o[0] = fx_dihedral(&s_x[0][0], a.dih[t], box, f);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { o[1 + 3 * r] = f[r][0]; o[2 + 3 * r] = f[r][1]; o[3 + 3 * r] = f[r][2]; }
-    }
-    __syncthreads();
-    if (tid < 6u) s_rigid[tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
-    if (tid >= 64u && tid < 70u) s_I[tid - 64u] = rf_inertia(&s_x[0][0], count, s_c, tid - 64u);      // (a wave of its own, beside rigid)
-    if (tid == 128u) {      // the energies in list order
-        double e = 0.0;
-        for (uint32_t t = 0; t < a.n_terms; ++t) e += eterm[(size_t)t * FLEX_TERM_WORDS];
-        s_edih = (float)e;
-    }
-    if (tid < count && a.n_terms) {
-        // thread i: the forces of the terms that name atom i, in list order - the atom-owned gather
-        double f0 = 0.0, f1 = 0.0, f2 = 0.0;
-        for (uint32_t e = a.aoff[tid]; e < a.aoff[tid + 1u]; ++e) {
-            const uint32_t w = a.aent[e];
-            const double* o = eterm + (size_t)(w >> 2) * FLEX_TERM_WORDS + 1u + 3u * (w & 3u);
-            f0 += o[0]; f1 += o[1]; f2 += o[2];
-        }
-        if (!isfinite(f0) || !isfinite(f1) || !isfinite(f2)) s_bad = 1u;
-        s_f[tid][0] += f0; s_f[tid][1] += f1; s_f[tid][2] += f2;
-    }
-    __syncthreads();
-    if (tid < T) {
-        const double n = (double)count;
-        const double v[3] = {(double)s_rigid[0] / n, (double)s_rigid[1] / n, (double)s_rigid[2] / n};
-        fx_gradient(&s_x[0][0], &s_f[0][0], count, v, s_tor[tid], s_u[tid], s_g[tid], s_J[tid], s_A[tid]);
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        bool finite = s_bad == 0u && isfinite(s_edih);
-        for (int k = 0; k < 6; ++k) finite = finite && isfinite(s_rigid[k]);
-        double S = 0.0, gmax = 0.0;
-        for (uint32_t b = 0; b < a.G; ++b) S += (double)s_row[b];
-        S += (double)s_edih;
-        for (uint32_t k = 0; k < T; ++k) {
-            const double g = fabs(s_g[k]);
-            finite = finite && isfinite(g);
-            gmax = g > gmax ? g : gmax;
-        }
-        if (s_st.rf.evals == 0u) fx_start(s_st, s_c, a.o.rf.h_start);      // (the record was zeroed: the trial is the input pose)
-        const uint32_t fl = fx_decide(s_st, a.o, T, S, finite, s_rigid, gmax);
-        if (fl & MDX_RF_STORE) {
-            s_st.edih = s_edih;
-            for (uint32_t k = 0; k < T; ++k) s_st.g[k] = s_g[k];
-        }
-        if (fl == MDX_RF_STORE) rf_direction(s_st.rf, count, s_rigid, s_I);
-        s_flags = fl;
-    }
-    if (tid >= 64u && tid < 64u + T) {      // (a wave beside thread 0's: used only if the trial is stored and the pose goes on)
-        const uint32_t k = tid - 64u;
-        s_wk[k] = fx_omega(s_g[k], s_J[k]);
-        fx_shift(s_wk[k], s_A[k], count, s_sh[k]);
-    }
-    __syncthreads();
-    if (s_flags == MDX_RF_STORE && tid < T) s_st.wk[tid] = s_wk[tid];      // (read again only after the next barrier)
-    const bool first = s_st.rf.evals == 1u;
-    uint32_t fl = s_flags;
-    if (fl & MDX_RF_STORE) {
-        if (tid < count)
-            for (uint32_t c = 0; c < 3u; ++c) a.y[at + c] = a.stage[at + c];
-        if (tid < a.G) a.row[(size_t)pose * a.G + tid] = s_row[tid];
-        if (tid < 6u) a.rigid[(size_t)pose * 6u + tid] = s_rigid[tid];
-    }
-    if (first && tid < count)
-        for (uint32_t c = 0; c < 3u; ++c) a.x0[at + c] = a.stage[at + c];
-    if (fl == MDX_RF_STORE) {
-        // the largest atom speed of the new direction (a maximum: exact in any order)
-        double m = 0.0;
-        if (tid < count) m = fx_speed(s_st.rf.v, s_st.rf.w, s_c, &s_x[0][0], tid, T, s_tor, s_u, s_wk, s_sh);
-#pragma unroll
-        for (int k = 32; k > 0; k >>= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
-        if ((tid & 63u) == 0u) s_m[tid >> 6] = m;
-        __syncthreads();
-        if (tid == 0u) {
-            double mm = s_m[0];
-            for (int k = 1; k < 4; ++k) mm = s_m[k] > mm ? s_m[k] : mm;
-            s_flags = fl = fl | rf_set_speed(s_st.rf, mm);
-        }
-        __syncthreads();
-        fl = s_flags;
-    }
-    if (!(fl & MDX_RF_FROZEN)) {
-        if (tid == 0u) {
-            fx_trial(s_st, T);
-            rf_rotation(s_st.rf.qt, s_R);
-        }
-        // B(theta_try) from the input pose: s_x is free now
-        if (tid < count)
-            for (uint32_t c = 0; c < 3u; ++c) s_x[tid][c] = (double)a.x0[at + c];
-        __syncthreads();
-        if (tid < T) { s_cs[tid] = cos(s_st.tht[tid]); s_sn[tid] = sin(s_st.tht[tid]); }
-        __syncthreads();
-        for (uint32_t k = 0; k < T; ++k) {
-            const double th = s_st.tht[k];
-            if (th == 0.0) continue;      // (uniform over the workgroup)
-            const mdx_fx_torsion& t = s_tor[k];
-            double u[3];
-            const bool turns = fx_axis(&s_x[0][0], t, u);      // (atoms a and b: not written in this round)
-            if (turns && tid < count && tid != t.b && fx_member(t.mask, tid)) {
-                const double b[3] = {s_x[t.b][0], s_x[t.b][1], s_x[t.b][2]};
-                fx_rotate(u, b, s_cs[k], s_sn[k], s_x[tid]);
-            }
-            __syncthreads();
-        }
-        if (tid < 3u) s_bc[tid] = rf_mean(&s_x[0][0], count, tid);
-    }
-    __syncthreads();
-    {
-        uint32_t* dst = (uint32_t*)(a.st + pose);
-        for (uint32_t i = tid; i < sizeof(mdx_fx_state) / 4u; i += 256u) dst[i] = ((const uint32_t*)&s_st)[i];
-    }
-    if (fl & MDX_RF_FROZEN) {
-        if (tid == 0u) a.frozen[pose] = 1u;
-        return;
-    }
-    if (tid < count) {
-        float y[3];
-        fx_coords(s_st.rf.c0, s_st.rf.tt, s_R, s_x[tid], s_bc, y);
-        for (uint32_t c = 0; c < 3u; ++c) a.stage[at + c] = y[c];
-    }
+// the options of a refinement: the refusals, then the stepper's options with the defaults filled in (the rigid entry point has neither
+// tors_tol nor flags: it passes 0 for both)
+static int refine_opts_check(const std::string& who, const mdx_flex_opts& opts, mdx_fx_opts& o) {
+    if (opts.max_evals == 0 || opts.max_evals > MDX_REFINE_MAX_EVALS_CAP) FAIL(MDX_EPARAM, who + ": max_evals must be in 1..MDX_REFINE_MAX_EVALS_CAP (4096)");
+    for (float v : {opts.f_tol, opts.tau_tol, opts.tors_tol, opts.h_start, opts.h_max})
+        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": a tolerance or step length is negative or not finite");
+    if (opts.flags & ~MDX_FLEX_DIHEDRALS) FAIL(MDX_EPARAM, who + ": unknown flag bits");
+    o = mdx_fx_opts{{(double)opts.f_tol, (double)opts.tau_tol, opts.h_start > 0.f ? (double)opts.h_start : 0.01,
+                     opts.h_max > 0.f ? (double)opts.h_max : 0.2}, (double)opts.tors_tol};
+    if (o.rf.h_start > o.rf.h_max) FAIL(MDX_EPARAM, who + ": h_start exceeds h_max");
+    return MDX_OK;
 }
 
-// The flexible block of a chunk of n poses: RefineLayout with the larger state record, and the terms' energies behind it
-struct FlexLayout {
-    size_t frozen, state, y, row, rigid, x0, eterm, end;
-    FlexLayout(uint32_t n, size_t per_pose, uint32_t G, uint32_t n_terms) {
-        frozen = 0;
-        state = ((sizeof(uint32_t) * n + 15u) / 16u) * 16u;
-        y = state + sizeof(mdx_fx_state) * n;
-        row = y + sizeof(float) * per_pose * n;
-        rigid = row + sizeof(float) * (size_t)G * n;
-        x0 = rigid + sizeof(float) * 6u * n;
-        eterm = ((x0 + sizeof(float) * per_pose * n + 15u) / 16u) * 16u;
-        end = eterm + sizeof(double) * FLEX_TERM_WORDS * (size_t)n_terms * n;
+// the step kernel's arguments for a chunk laid out by `lay`; flex: with the torsion table of flex_table (T torsions, n_terms terms)
+static StepArgs step_args(mdx_handle* h, const PoseArgs& a, uint32_t count, bool flex, uint32_t T, uint32_t n_terms, const StepLayout& lay,
+                          const mdx_fx_opts& o) {
+    DeviceState& d = h->d;
+    unsigned char* blk = (unsigned char*)d.ps_flex;
+    StepArgs r{};
+    r.count = count; r.G = h->n_grp; r.T = T; r.n_terms = n_terms; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
+    r.frozen = (uint32_t*)(blk + lay.frozen); r.st = blk + lay.state;
+    r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
+    if (flex) {
+        const FlexTable tab(count, n_terms);
+        const unsigned char* tb = (const unsigned char*)d.ps_flex_tab;
+        r.eterm = (double*)(blk + lay.eterm);
+        r.tor = (const mdx_fx_torsion*)(tb + tab.tor); r.dih = (const mdx_fx_dihedral*)(tb + tab.dih);
+        r.aoff = (const uint32_t*)(tb + tab.aoff); r.aent = (const uint32_t*)(tb + tab.aent);
     }
-};
+    for (int k = 0; k < 3; ++k) r.box[k] = (double)a.box[k];
+    r.o = o;
+    return r;
+}
+
+// one evaluation of a chunk: the REFINE force pass, then the step kernel
+template <bool FLEX>
+static void step_evaluate(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, const StepArgs& r) {
+    pose_launch(h, a, mode, geom, n, true, true);
+    if (FLEX) hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
+    else hipLaunchKernelGGL(pose_refine_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
+}
+
+// where a refinement's results go; the rigid entry point has no dih / tgrad, and its xform ends with t
+struct RefineOut { float* poses; float* rows; float* rigid; float* xform; float* dih; float* tgrad; uint32_t* status; uint32_t* evals; };
+
+// one pose's record as it came back: status, evaluations, (q, t) and - flexible - theta behind them, E_dih and g
+static void refine_unpack(const mdx_rf_state& s, uint32_t* status, uint32_t* evals, float* x) {
+    *status = s.frozen ? s.status : MDX_REFINE_MAX_EVALS;
+    *evals = s.evals;
+    for (int c = 0; c < 4; ++c) x[c] = (float)s.q[c];
+    for (int c = 0; c < 3; ++c) x[4 + c] = (float)s.t[c];
+}
+static void refine_unpack(const mdx_fx_state& s, uint32_t T, uint32_t* status, uint32_t* evals, float* x, float* dih, float* tgrad) {
+    refine_unpack(s.rf, status, evals, x);
+    for (uint32_t c = 0; c < T; ++c) { x[7u + c] = (float)s.th[c]; tgrad[c] = (float)s.g[c]; }
+    *dih = s.edih;
+}
+
+// The loop of both refinements over the chunks of a batch, State = mdx_rf_state (T = n_terms = 0) or mdx_fx_state: upload, zero the
+// frozen words and records, max_evals x (force pass, step kernel), one read-back, one wait; the outputs are written once all chunks
+// have run.  pose_setup (and, flexible, flex_table) have passed.
+template <class State>
+static int refine_chunks(mdx_handle* h, PoseArgs& a, int mode, bool geom, uint32_t count, uint32_t n_poses, const float* poses, uint32_t T,
+                         uint32_t n_terms, uint32_t max_evals, const mdx_fx_opts& o, const RefineOut& out) {
+    constexpr bool FLEX = std::is_same<State, mdx_fx_state>::value;
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t G = h->n_grp, X = 7u + T;
+    const size_t per_pose = 3 * (size_t)count;
+    MDX_TRY(pose_grow(&d.ps_flex, h->ps_cap_flex, StepLayout(POSE_CHUNK, per_pose, G, sizeof(State), n_terms).end));
+    std::vector<float> yres(per_pose * n_poses), rres((size_t)n_poses * G), gres(6u * (size_t)n_poses), xres((size_t)X * n_poses),
+        dres(FLEX ? n_poses : 0u), tres((size_t)T * n_poses);
+    std::vector<uint32_t> sres(n_poses), eres(n_poses);
+    std::vector<unsigned char> back;
+    for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
+        const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
+        const StepLayout lay(n, per_pose, G, sizeof(State), n_terms);
+        unsigned char* blk = (unsigned char*)d.ps_flex;
+        const StepArgs r = step_args(h, a, count, FLEX, T, n_terms, lay, o);
+        a.frozen = r.frozen;
+        HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(blk, 0, lay.y, st));
+        mdx_prof_begin(h, 0);
+        for (uint32_t k = 0; k < max_evals; ++k) step_evaluate<FLEX>(h, a, mode, geom, n, r);
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        back.resize(lay.x0 - lay.state);
+        HIP_TRY(hipMemcpyAsync(back.data(), blk + lay.state, back.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const unsigned char* b0 = back.data() - lay.state;
+        std::memcpy(yres.data() + per_pose * p0, b0 + lay.y, sizeof(float) * per_pose * n);
+        std::memcpy(rres.data() + (size_t)p0 * G, b0 + lay.row, sizeof(float) * (size_t)G * n);
+        std::memcpy(gres.data() + 6u * (size_t)p0, b0 + lay.rigid, sizeof(float) * 6u * n);
+        for (uint32_t k = 0; k < n; ++k) {
+            State s;
+            std::memcpy(&s, b0 + lay.state + sizeof(State) * k, sizeof(s));
+            const size_t p = p0 + k;
+            if constexpr (FLEX) refine_unpack(s, T, &sres[p], &eres[p], xres.data() + X * p, &dres[p], tres.data() + (size_t)T * p);
+            else refine_unpack(s, &sres[p], &eres[p], xres.data() + X * p);
+        }
+    }
+    std::memcpy(out.poses, yres.data(), sizeof(float) * yres.size());
+    if (out.rows) std::memcpy(out.rows, rres.data(), sizeof(float) * rres.size());
+    if (out.rigid) std::memcpy(out.rigid, gres.data(), sizeof(float) * gres.size());
+    if (out.xform) std::memcpy(out.xform, xres.data(), sizeof(float) * xres.size());
+    if (out.dih) std::memcpy(out.dih, dres.data(), sizeof(float) * dres.size());
+    if (out.tgrad && T) std::memcpy(out.tgrad, tres.data(), sizeof(float) * tres.size());
+    if (out.status) std::memcpy(out.status, sres.data(), sizeof(uint32_t) * sres.size());
+    if (out.evals) std::memcpy(out.evals, eres.data(), sizeof(uint32_t) * eres.size());
+    return MDX_OK;
+}
+
+extern "C" int mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses,
+                                const mdx_refine_opts* opts, float* poses_out, float* rows_out_or_null, uint32_t n_groups,
+                                float* rigid_out_or_null, float* xform_out_or_null, uint32_t* status_out_or_null,
+                                uint32_t* evals_out_or_null) {
+    const std::string who = "mdx_refine_poses";
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_poses == 0) return MDX_OK;
+    if (!poses || !poses_out || !opts) FAIL(MDX_EPARAM, "null argument");
+    mdx_fx_opts o{};
+    MDX_TRY(refine_opts_check(who, mdx_flex_opts{opts->max_evals, opts->f_tol, opts->tau_tol, 0.f, opts->h_start, opts->h_max, 0u}, o));
+    PoseArgs a{};
+    int mode = 0; bool geom = false;
+    MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, true, a, mode, geom));
+    return refine_chunks<mdx_rf_state>(h, a, mode, geom, count, n_poses, poses, 0u, 0u, opts->max_evals, o,
+                                       RefineOut{poses_out, rows_out_or_null, rigid_out_or_null, xform_out_or_null, nullptr, nullptr,
+                                                 status_out_or_null, evals_out_or_null});
+}
+
+// ---- the flexible refinement's own: the torsion list and its table -----------------------------------------------------------------------
 
 // What can be refused of a torsion list on the host's copy of the topology alone: the range's bonds, the moving sides.  tor: [n_torsions]
 static int flex_graph(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t root, uint32_t n_torsions,
@@ -1036,12 +1060,7 @@ static int flex_table(mdx_handle* h, const std::string& who, uint32_t first, uin
     if (n_terms) std::memcpy(img.data() + lay.dih, dih.data(), sizeof(mdx_fx_dihedral) * n_terms);
     std::memcpy(img.data() + lay.aoff, aoff.data(), sizeof(uint32_t) * aoff.size());
     if (n_terms) std::memcpy(img.data() + lay.aent, aent.data(), sizeof(uint32_t) * aent.size());
-    if (h->ps_cap_flex_tab < lay.end) {
-        if (d.ps_flex_tab) { (void)hipFree(d.ps_flex_tab); d.ps_flex_tab = nullptr; }
-        h->ps_cap_flex_tab = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_flex_tab, lay.end));
-        h->ps_cap_flex_tab = lay.end;
-    }
+    MDX_TRY(pose_grow(&d.ps_flex_tab, h->ps_cap_flex_tab, lay.end));
     HIP_TRY(hipMemcpyAsync(d.ps_flex_tab, img.data(), lay.end, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->fx_valid = true; h->fx_first = first; h->fx_count = count; h->fx_epoch = h->grp_epoch; h->fx_root = root; h->fx_flags = flags;
@@ -1050,65 +1069,20 @@ static int flex_table(mdx_handle* h, const std::string& who, uint32_t first, uin
 }
 
 // What mdx_refine_poses_flex and mdx_search_poses share ahead of their loops: the checks of the torsion list and the options, the
-// refusals and buffers of pose_setup, the table and the block of a chunk
+// refusals and buffers of pose_setup, the table
 static int flex_begin(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, uint32_t root,
                       uint32_t n_torsions, const uint32_t* torsion_bonds, const mdx_flex_opts* opts, uint32_t n_groups, PoseArgs& a, int& mode,
                       bool& geom, mdx_fx_opts& o) {
     if (n_torsions > MDX_POSE_MAX_TORSIONS) FAIL(MDX_EPARAM, who + ": n_torsions exceeds MDX_POSE_MAX_TORSIONS (32)");
     if (n_torsions && !torsion_bonds) FAIL(MDX_EPARAM, who + ": null torsion_bonds with n_torsions > 0");
-    if (opts->max_evals == 0 || opts->max_evals > MDX_REFINE_MAX_EVALS_CAP) FAIL(MDX_EPARAM, who + ": max_evals must be in 1..MDX_REFINE_MAX_EVALS_CAP (4096)");
-    for (float v : {opts->f_tol, opts->tau_tol, opts->tors_tol, opts->h_start, opts->h_max})
-        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": a tolerance or step length is negative or not finite");
-    if (opts->flags & ~MDX_FLEX_DIHEDRALS) FAIL(MDX_EPARAM, who + ": unknown flag bits");
-    o = mdx_fx_opts{{(double)opts->f_tol, (double)opts->tau_tol, opts->h_start > 0.f ? (double)opts->h_start : 0.01,
-                     opts->h_max > 0.f ? (double)opts->h_max : 0.2}, (double)opts->tors_tol};
-    if (o.rf.h_start > o.rf.h_max) FAIL(MDX_EPARAM, who + ": h_start exceeds h_max");
+    MDX_TRY(refine_opts_check(who, *opts, o));
     // the torsion list against the host's copy of the bonds - once the range itself has passed the checks pose_setup opens with
     if (count == 0 || count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, who + ": count must be in 1..MDX_POSE_MAX_ATOMS (256)");
     if ((uint64_t)first + count > h->N) FAIL(MDX_EPARAM, "atom range out of bounds");
     std::vector<mdx_fx_torsion> tor;
     MDX_TRY(flex_graph(h, who, first, count, root, n_torsions, torsion_bonds, tor));
     MDX_TRY(pose_setup(h, who, first, count, n_poses, poses, n_groups, true, a, mode, geom));
-    MDX_TRY(flex_table(h, who, first, count, root, n_torsions, torsion_bonds, opts->flags, tor));
-    DeviceState& d = h->d;
-    const size_t need = FlexLayout(POSE_CHUNK, 3 * (size_t)count, h->n_grp, h->fx_terms).end;
-    if (h->ps_cap_flex < need) {
-        if (d.ps_flex) { (void)hipFree(d.ps_flex); d.ps_flex = nullptr; }
-        h->ps_cap_flex = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_flex, need));
-        h->ps_cap_flex = need;
-    }
-    return MDX_OK;
-}
-
-// the step kernel's arguments for a chunk laid out by `lay`
-static FlexArgs flex_args(mdx_handle* h, const PoseArgs& a, uint32_t count, uint32_t T, const FlexLayout& lay, const mdx_fx_opts& o) {
-    DeviceState& d = h->d;
-    const uint32_t n_terms = h->fx_terms;
-    const FlexTable tab(count, n_terms);
-    unsigned char* blk = (unsigned char*)d.ps_flex;
-    const unsigned char* tb = (const unsigned char*)d.ps_flex_tab;
-    FlexArgs r{};
-    r.count = count; r.G = h->n_grp; r.T = T; r.n_terms = n_terms; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
-    r.frozen = (uint32_t*)(blk + lay.frozen); r.st = (mdx_fx_state*)(blk + lay.state);
-    r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
-    r.eterm = (double*)(blk + lay.eterm);
-    r.tor = (const mdx_fx_torsion*)(tb + tab.tor); r.dih = (const mdx_fx_dihedral*)(tb + tab.dih);
-    r.aoff = (const uint32_t*)(tb + tab.aoff); r.aent = (const uint32_t*)(tb + tab.aent);
-    for (int k = 0; k < 3; ++k) r.box[k] = (double)a.box[k];
-    r.o = o;
-    return r;
-}
-
-// one evaluation of a chunk: the REFINE force pass, then the flexible step kernel
-static void flex_evaluate(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, const FlexArgs& r) {
-    switch (mode) {
-    case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, true, true); break;
-    case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, true, true); break;
-    case CM_RF: launch_poses<CM_RF>(h, a, geom, n, true, true); break;
-    default: launch_poses<CM_EWALD>(h, a, geom, n, true, true); break;
-    }
-    hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
+    return flex_table(h, who, first, count, root, n_torsions, torsion_bonds, opts->flags, tor);
 }
 
 extern "C" int mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses, const float* poses, uint32_t root,
@@ -1124,54 +1098,9 @@ extern "C" int mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t cou
     int mode = 0; bool geom = false;
     mdx_fx_opts o{};
     MDX_TRY(flex_begin(h, who, first, count, n_poses, poses, root, n_torsions, torsion_bonds, opts, n_groups, a, mode, geom, o));
-    DeviceState& d = h->d;
-    hipStream_t st = h->stream;
-    const uint32_t G = h->n_grp, T = n_torsions, n_terms = h->fx_terms;
-    const size_t per_pose = 3 * (size_t)count;
-    const uint32_t X = 7u + T;
-    std::vector<float> yres(per_pose * n_poses), rres((size_t)n_poses * G), gres(6u * (size_t)n_poses), xres((size_t)X * n_poses),
-        dres(n_poses), tres((size_t)T * n_poses);
-    std::vector<uint32_t> sres(n_poses), eres(n_poses);
-    std::vector<unsigned char> back;
-    for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
-        const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
-        const FlexLayout lay(n, per_pose, G, n_terms);
-        unsigned char* blk = (unsigned char*)d.ps_flex;
-        const FlexArgs r = flex_args(h, a, count, T, lay, o);
-        a.frozen = r.frozen;
-        HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(blk, 0, lay.y, st));
-        mdx_prof_begin(h, 0);
-        for (uint32_t k = 0; k < opts->max_evals; ++k) flex_evaluate(h, a, mode, geom, n, r);
-        mdx_prof_end(h);
-        HIP_TRY(hipGetLastError());
-        back.resize(lay.x0 - lay.state);
-        HIP_TRY(hipMemcpyAsync(back.data(), blk + lay.state, back.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const unsigned char* b0 = back.data() - lay.state;
-        std::memcpy(yres.data() + per_pose * p0, b0 + lay.y, sizeof(float) * per_pose * n);
-        std::memcpy(rres.data() + (size_t)p0 * G, b0 + lay.row, sizeof(float) * (size_t)G * n);
-        std::memcpy(gres.data() + 6u * (size_t)p0, b0 + lay.rigid, sizeof(float) * 6u * n);
-        for (uint32_t k = 0; k < n; ++k) {
-            const mdx_fx_state* s = (const mdx_fx_state*)(b0 + lay.state + sizeof(mdx_fx_state) * k);
-            sres[p0 + k] = s->rf.frozen ? s->rf.status : MDX_REFINE_MAX_EVALS;
-            eres[p0 + k] = s->rf.evals;
-            float* x = xres.data() + (size_t)X * (p0 + k);
-            for (int c = 0; c < 4; ++c) x[c] = (float)s->rf.q[c];
-            for (int c = 0; c < 3; ++c) x[4 + c] = (float)s->rf.t[c];
-            for (uint32_t c = 0; c < T; ++c) { x[7u + c] = (float)s->th[c]; tres[(size_t)T * (p0 + k) + c] = (float)s->g[c]; }
-            dres[p0 + k] = s->edih;
-        }
-    }
-    std::memcpy(poses_out, yres.data(), sizeof(float) * yres.size());
-    if (rows_out_or_null) std::memcpy(rows_out_or_null, rres.data(), sizeof(float) * rres.size());
-    if (rigid_out_or_null) std::memcpy(rigid_out_or_null, gres.data(), sizeof(float) * gres.size());
-    if (xform_out_or_null) std::memcpy(xform_out_or_null, xres.data(), sizeof(float) * xres.size());
-    if (dih_out_or_null) std::memcpy(dih_out_or_null, dres.data(), sizeof(float) * dres.size());
-    if (tgrad_out_or_null && T) std::memcpy(tgrad_out_or_null, tres.data(), sizeof(float) * tres.size());
-    if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
-    if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
-    return MDX_OK;
+    return refine_chunks<mdx_fx_state>(h, a, mode, geom, count, n_poses, poses, n_torsions, h->fx_terms, opts->max_evals, o,
+                                       RefineOut{poses_out, rows_out_or_null, rigid_out_or_null, xform_out_or_null, dih_out_or_null,
+                                                 tgrad_out_or_null, status_out_or_null, evals_out_or_null});
 }
 
 // ---- mdx_search_poses: an iterated local search per walker around the loop above (mdx_search_step.h) ------------------------------------
@@ -1203,7 +1132,7 @@ struct SearchArgs {
 // Launched with round index r between two refinements, one workgroup per walker: it decides round r - 1 (r >= 1) from what the
 // refinement left - thread 0 takes the decision, the threads copy the accepted coordinates (and, for a new best, row and rigid) into the
 // walker's search record - and, for r < n_rounds, starts round r: thread 0 draws the move and forms (dq, dt), B(dtheta) is built in LDS
-// from the current pose with one barrier per non-zero torsion as pose_flex_step_kernel builds a trial, every thread writes its atom of
+// from the current pose by pose_build_torsions, the loop pose_flex_step_kernel builds a trial with, every thread writes its atom of
 // X0' into the staging buffer, and the walker's state record and frozen word are zeroed ("evaluation 0: the trial is the input").
 // Round 0 has no move: the staged pose is the caller's.  Plain stores only.
 __global__ __launch_bounds__(256) void pose_search_kernel(SearchArgs a, uint32_t r) {
@@ -1256,17 +1185,7 @@ __global__ __launch_bounds__(256) void pose_search_kernel(SearchArgs a, uint32_t
             if (mv.kind == MDX_SR_TORSION) { s_th[mv.torsion] = mv.dtheta; s_cs[mv.torsion] = cos(mv.dtheta); s_sn[mv.torsion] = sin(mv.dtheta); }
         }
         __syncthreads();
-        for (uint32_t k = 0; k < T; ++k) {
-            if (s_th[k] == 0.0) continue;      // (uniform over the workgroup)
-            const mdx_fx_torsion& t = a.tor[k];      // (read where it lies: at most one torsion is turned per round)
-            double u[3];
-            const bool turns = fx_axis(&s_x[0][0], t, u);      // (atoms a and b: not written in this round)
-            if (turns && tid < count && tid != t.b && fx_member(t.mask, tid)) {
-                const double b[3] = {s_x[t.b][0], s_x[t.b][1], s_x[t.b][2]};
-                fx_rotate(u, b, s_cs[k], s_sn[k], s_x[tid]);
-            }
-            __syncthreads();
-        }
+        pose_build_torsions(s_x, a.tor, s_th, s_cs, s_sn, T, count, tid);      // (the table where it lies: at most one torsion turns per round)
         if (tid < 3u) s_bc[tid] = rf_mean(&s_x[0][0], count, tid);
         __syncthreads();
         if (tid < count) {
@@ -1305,13 +1224,8 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
     hipStream_t st = h->stream;
     const uint32_t G = h->n_grp, T = n_torsions, n_terms = h->fx_terms;
     const size_t per_pose = 3 * (size_t)count;
-    const size_t need = SearchLayout(POSE_CHUNK, per_pose, G).end;
-    if (h->ps_cap_search < need) {
-        if (d.ps_search) { (void)hipFree(d.ps_search); d.ps_search = nullptr; }
-        h->ps_cap_search = 0;
-        HIP_TRY(hipMalloc((void**)&d.ps_search, need));
-        h->ps_cap_search = need;
-    }
+    MDX_TRY(pose_grow(&d.ps_flex, h->ps_cap_flex, StepLayout(POSE_CHUNK, per_pose, G, sizeof(mdx_fx_state), n_terms).end));
+    MDX_TRY(pose_grow(&d.ps_search, h->ps_cap_search, SearchLayout(POSE_CHUNK, per_pose, G).end));
     std::vector<float> yres(per_pose * n_walkers), rres((size_t)n_walkers * G), dres(n_walkers);
     std::vector<double> scres(n_walkers);
     std::vector<uint32_t> brres(n_walkers), stres(4u * (size_t)n_walkers);
@@ -1319,13 +1233,13 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
     std::vector<unsigned char> back;
     for (uint32_t p0 = 0; p0 < n_walkers; p0 += POSE_CHUNK) {
         const uint32_t n = std::min(POSE_CHUNK, n_walkers - p0);
-        const FlexLayout lay(n, per_pose, G, n_terms);
+        const StepLayout lay(n, per_pose, G, sizeof(mdx_fx_state), n_terms);
         const SearchLayout sl(n, per_pose, G);
         unsigned char* sb = (unsigned char*)d.ps_search;
-        const FlexArgs r = flex_args(h, a, count, T, lay, o);
+        const StepArgs r = step_args(h, a, count, true, T, n_terms, lay, o);
         a.frozen = r.frozen;
         SearchArgs s{};
-        s.count = count; s.G = G; s.T = T; s.stage = d.ps_stage; s.frozen = r.frozen; s.st = r.st; s.y = r.y; s.row = r.row; s.rigid = r.rigid;
+        s.count = count; s.G = G; s.T = T; s.stage = d.ps_stage; s.frozen = r.frozen; s.st = (mdx_fx_state*)r.st; s.y = r.y; s.row = r.row; s.rigid = r.rigid;
         s.tor = r.tor; s.streams = (const uint64_t*)(sb + sl.streams); s.rec = (mdx_sr_record*)(sb + sl.rec);
         s.cur_y = (float*)(sb + sl.cur_y); s.best_y = (float*)(sb + sl.best_y); s.best_row = (float*)(sb + sl.best_row);
         s.best_rigid = (float*)(sb + sl.best_rigid);
@@ -1336,7 +1250,7 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
         mdx_prof_begin(h, 0);
         for (uint32_t rd = 0; rd < opts->n_rounds; ++rd) {
             hipLaunchKernelGGL(pose_search_kernel, dim3(n), dim3(256), 0, st, s, rd);
-            for (uint32_t k = 0; k < opts->refine.max_evals; ++k) flex_evaluate(h, a, mode, geom, n, r);
+            for (uint32_t k = 0; k < opts->refine.max_evals; ++k) step_evaluate<true>(h, a, mode, geom, n, r);
         }
         hipLaunchKernelGGL(pose_search_kernel, dim3(n), dim3(256), 0, st, s, opts->n_rounds);
         mdx_prof_end(h);
