@@ -331,7 +331,9 @@ int mdx_pair_launch_info(const mdx_handle* h, uint32_t out[24]);
  * sigma (one LJ atom type: a water box, rigid OPC; Lorentz-Berthelot rule, no alchemical window) is eligible: its force-only pair launches
  * multiply by the one f32 value sigma_ij^2 can take instead of adding and squaring per pair - the same bits, two vector instructions
  * fewer per cluster pair.  out[0]: the handle is eligible (MDX_UNI_LJ=0 in the environment: never), out[1]: the last pair launch of the
- * step loop ran such a body, out[2]: the last pair launch of any kind did, out[3]: the bits of that f32 value (0 when not eligible).
+ * step loop ran such a body (non-zero; bit 1 set: with the chunk loop that keeps two sets of pipeline registers and waits for vector
+ * memory once per two chunks - the one-wave half-list kernels), out[2]: the same of the last pair launch of any kind, out[3]: the bits
+ * of that f32 value (0 when not eligible).
  * No call of the reference corresponds to it. */
 int mdx_pair_body_info(const mdx_handle* h, uint32_t out[4]);
 /* The Verlet skin in force, and whether the library is still tuning it (mdx_config.skin == 0). */

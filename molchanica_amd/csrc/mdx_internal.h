@@ -451,7 +451,7 @@ struct mdx_handle {
     // one LJ atom type (mdx_refresh_uni_lj: at create and wherever the LJ records or the alchemical state change): the pair launches that
     // have a constant-sigma^2 body (pair_eval<..., UNI>, launch_variant) send it out.  mdx_pair_body_info reads the three words.
     bool uni_lj = false; float uni_c = 0.f;
-    uint32_t pair_body_step = 0, pair_body_any = 0;      // the last pair launch of the step loop / of any kind ran a UNI body
+    uint32_t pair_body_step = 0, pair_body_any = 0;      // the last pair launch of the step loop / of any kind ran a UNI body (bit 0; bit 1: its two-set chunk loop)
     bool bonded_deferred = false; // step loop, large classes: the NEXT step's fused bonded + kick + drift pass evaluates the bonded terms of this force call
     uint64_t rng_state = 0;
     bool zero_com = false;

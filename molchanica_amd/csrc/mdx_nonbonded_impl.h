@@ -24,6 +24,13 @@ extern uint4* g_mdx_drain; extern size_t g_mdx_drain_cap; extern uint32_t g_mdx_
 #ifndef NB_HALF_FLUSH
 #define NB_HALF_FLUSH 0   // 1: j-forces leave once per chunk from LDS; 0: one 24-lane atomic per entry
 #endif
+#ifndef NB_SPLIT_MASKED
+#define NB_SPLIT_MASKED 1 // 1: the chunk loop exists twice, masked chunks and plain ones (nb_cluster_body)
+#endif
+#ifndef NB_LATCH2
+#define NB_LATCH2 1       // 1: the one-wave half-list UNI kernels keep two sets of the chunk pipeline's registers and wait for vector
+                          // memory once per two chunks (nb_cluster_body, LATCH2); 0: every kernel has the one-set loop
+#endif
 
 // The force-only pair evaluation of the default flavour (shifted-cutoff Coulomb, Lorentz-Berthelot, one cutoff, half list) as ONE
 // block of hand-written gfx950 instructions (round 3).  Same arithmetic, instruction for instruction, as hipcc's code for
@@ -93,6 +100,11 @@ __device__ __forceinline__ void pair_eval_asm(float xi, float yi, float zi, floa
         : "vcc");
 }
 
+// which instantiations of nb_cluster_body keep two sets of the chunk pipeline's registers (LATCH2 there; launch_variant reports it)
+constexpr bool nb_latch2(bool half, bool uni, int wpt, bool energy, bool alch, bool step) {
+    return NB_LATCH2 && NB_SPLIT_MASKED && half && !NB_HALF_FLUSH && uni && wpt == 1 && !energy && !alch && !step;
+}
+
 template <bool ENERGY, int COUL, bool GEOM, bool SAMECUT, bool MASKED>
 __device__ __forceinline__ void chunk_pairs(const float4* __restrict__ sx, const float2* __restrict__ sl,
                                             unsigned long long mask, float xi, float yi, float zi, float qi,
@@ -146,10 +158,9 @@ __global__ __launch_bounds__(NB_WAVES * 64) void nb_tile_kernel(NbArgs a) {
     }
     for (uint32_t c = 0; c < nchunks; ++c) {
         {   // image shift, then park in LDS
-            const int kx = (int)(ncode % 3u) - 1, ky = (int)((ncode / 3u) % 3u) - 1, kz = (int)(ncode / 9u) - 1;
-            nj.x += (float)kx * a.p.shift[0];
-            nj.y += (float)ky * a.p.shift[1];
-            nj.z += (float)kz * a.p.shift[2];
+            float rx, ry, rz;
+            image_shift_row(ncode, a.p.shift, rx, ry, rz);
+            nj.x += rx; nj.y += ry; nj.z += rz;
             sx[lane] = nj;
             sl[lane] = nl;
         }
@@ -407,22 +418,43 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     // s_waitcnt vmcnt(0) per chunk sits where the data is a whole chunk old and the entry loop has
     // no vector-memory instruction in it (a mask fetched at its point of use - or an atomic issued
     // per entry - drags a vmcnt(0) into the loop and serialises the wave on memory latency).
-    float4 nj = make_float4(0.f, 0.f, 0.f, 0.f), nf = nj;      // (STEP: nf = the force row beside the j-atom's Y)
-    float2 nl = make_float2(0.f, 0.f);
-    uint32_t ny = 13, njc = 0;
-    float nown = 0.f;
-    unsigned long long nmq = ~0ull;
-    uint2 ent_n = make_uint2(0u, 13u);
-    if ((uint32_t)part < nchunks) {
-        const uint2 ent = entries[e0 + part * 8 + (lane >> 3)];
-        if ((uint32_t)part < nmc) nmq = a.masks[(size_t)(mbase + part) * 64 + lane];
-        if ((uint32_t)part + wv < nchunks) ent_n = entries[e0 + (part + wv) * 8 + (lane >> 3)];
-        const uint32_t js = ent.x * MDX_CLUSTER + (lane & 7);
-        nj = a.posq[js]; ny = ent.y; njc = ent.x;
-        if (UNI) nl.y = lj_eps[2 * js]; else nl = a.lj[js];
-        if (STEP) nf = a.st_fprev[js];
-        if (ENERGY && HALF) nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
-    }
+    //
+    // LATCH2 (the one-wave half-list kernels with the constant-sigma^2 body: plain list, the dual-list twins, the merged launch): in the
+    // PLAIN chunks the pipeline exists twice.  In a half-list loop that one wait sits a handful of instructions behind the chunk's last
+    // j-force atomic.  The atomic leaves from inside the entry loop, whose every entry may skip it, so the compiler cannot count the
+    // operations behind the loads and waits for zero (and a count would not help: loads and no-return atomics share vmcnt and retire in no
+    // fixed order among each other): the wave pays close to an atomic's round trip at every chunk.  With two register sets, each a
+    // pipeline of its own over every second plain chunk of the wave's share (each fetches atoms one and entries two of ITS chunks ahead),
+    // and the chunk loop unrolled by two, the wait at the head of set 0's chunk retires set 1's loads as well - they are a whole chunk
+    // old by then - and set 1's chunk begins without one: one vmcnt(0) per two chunks, none written by hand (plain_pass2 below).  The
+    // strip is one.  Nine more registers in the plain loop.  The masked chunks at the head of the list (5 - 10 %) keep one set: with two
+    // there, exclusion words included, every one of these kernels went to 128 VGPRs and 100 - 250 B of scratch.  Taken where the register
+    // report leaves four waves per SIMD without scratch: the general bodies (122 - 128 VGPRs), the multi-wave classes, STEP and the energy
+    // flavours keep one set throughout, and the full lists have no atomic to wait for.
+    struct JSet {
+        float4 nj, nf;               // the chunk in flight: j-atom of this lane (STEP: nf = the force row beside the j-atom's Y),
+        float2 nl;                   // its Lennard-Jones record,
+        uint32_t ny, njc;            // its entry's word and j-cluster,
+        float nown;                  // (ENERGY, HALF) 1.0 <=> the j-atom is owned here,
+        unsigned long long nmq;      // its exclusion bits (masked chunks)
+        uint2 ent;                   // the entry of the set's chunk after that one
+    };
+    constexpr bool LATCH2 = nb_latch2(HALF, UNI, WPT, ENERGY, ALCH, STEP);
+    JSet S0 = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float2(0.f, 0.f), 13u, 0u, 0.f, ~0ull, make_uint2(0u, 13u)};
+    JSet S1 = S0;
+    auto prime = [&](JSet& X, const uint32_t c0) __attribute__((always_inline)) {
+        if (c0 < nchunks) {
+            const uint2 ent = entries[e0 + c0 * 8 + (lane >> 3)];
+            if (c0 < nmc) X.nmq = a.masks[(size_t)(mbase + c0) * 64 + lane];
+            if (c0 + wv < nchunks) X.ent = entries[e0 + (c0 + wv) * 8 + (lane >> 3)];
+            const uint32_t js = ent.x * MDX_CLUSTER + (lane & 7);
+            X.nj = a.posq[js]; X.ny = ent.y; X.njc = ent.x;
+            if (UNI) X.nl.y = lj_eps[2 * js]; else X.nl = a.lj[js];
+            if (STEP) X.nf = a.st_fprev[js];
+            if (ENERGY && HALF) X.nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
+        }
+    };
+    prime(S0, (uint32_t)part);
     float* const fbase = reinterpret_cast<float*>(a.force);
     // (HALF) loop invariants of the per-entry j-force tail: which component this lane carries through the last reduction level, and
     // the byte offset of its word in the j-cluster's eight force rows
@@ -452,40 +484,63 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     if (HALF && NB_HALF_FLUSH) __builtin_amdgcn_s_waitcnt(0x0F70);
     const float rc2_s = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.p.rc2_lj)));   // an SGPR operand of v_cmpx
     // The chunk loop exists twice (round 3): the masked chunks at the head of the wave's share, then the plain ones - see the
-    // entry loop.  The software pipeline's state (nj, nl, ny, njc, ent_n, nmq) carries over from the first loop into the second.
-    auto chunk_pass = [&](auto masked_tag, const uint32_t c_begin, const uint32_t c_end) __attribute__((always_inline)) {
-    constexpr bool MASKED_CHUNK = decltype(masked_tag)::value;
-    for (uint32_t c = c_begin; c < c_end; c += wv) {
-        const uint32_t cur_y = ny, cur_jc = njc;
+    // entry loop.  The software pipeline's state (JSet) carries over from the first loop into the second.
+    // One chunk: c = its position, X = the set that holds it, ps = the chunk stride of that set (two sets: 2 wv).
+    auto chunk = [&](auto masked_tag, auto two_tag, const uint32_t c, JSet& X) __attribute__((always_inline)) {
+        constexpr bool MASKED_CHUNK = decltype(masked_tag)::value, TWO = decltype(two_tag)::value;
+        const uint32_t ps = TWO ? 2u * wv : wv;
+        uint32_t cur_y = X.ny, cur_jc = X.njc;
+        // (two sets: the copies are made HERE, behind the wait that retired the set.  Left to the allocator, a set's registers rotate at
+        // the end of its chunk - entry -> word in flight -> current word - and a copy there waits for the loads just issued.)
+        if (TWO) asm volatile("" : "+v"(cur_y), "+v"(cur_jc));
         constexpr bool masked = MASKED_CHUNK;
-        if (masked) s_mask[wave][lane] = nmq;                   // read back a byte per entry: two VGPRs fewer
-        if (ENERGY && HALF) s_ownj[wave][lane] = nown;
+        if (masked) s_mask[wave][lane] = X.nmq;                 // read back a byte per entry: two VGPRs fewer
+        if (ENERGY && HALF) s_ownj[wave][lane] = X.nown;
         if (HALF && NB_HALF_FLUSH) {
             // the lane that staged j-atom `lane` also flushes its force: remember where it goes.
             // List padding (imask 0) has no force: it will add 0 to this lane's own i-slot.
-            const bool live = ((ny >> 8) & 0xFFu) != 0u;
-            sg[lane] = make_float4(0.f, 0.f, 0.f, __uint_as_float(live ? njc * MDX_CLUSTER + (uint32_t)ii : t * MDX_TILE + lane));
+            const bool live = ((X.ny >> 8) & 0xFFu) != 0u;
+            sg[lane] = make_float4(0.f, 0.f, 0.f, __uint_as_float(live ? X.njc * MDX_CLUSTER + (uint32_t)ii : t * MDX_TILE + lane));
         }
         {   // image shift, then park in LDS
-            const uint32_t code = ny & 31u;
-            const int kx = (int)(code % 3u) - 1, ky = (int)((code / 3u) % 3u) - 1, kz = (int)(code / 9u) - 1;
-            if (STEP) nj = step_pos(nj, nf);
-            nj.x += (float)kx * a.p.shift[0];
-            nj.y += (float)ky * a.p.shift[1];
-            nj.z += (float)kz * a.p.shift[2];
-            sx[lane] = nj;
+            const uint32_t code = X.ny & 31u;
+            // (in place, as the load below is: shifted atom, LDS store and the next load share one register tuple - through a copy
+            // the tuple splits and the compiler mends it with moves right behind the load, each a wait for the load just issued)
+            if (STEP) X.nj = step_pos(X.nj, X.nf);
+            float rx, ry, rz;
+            image_shift_row(code, a.p.shift, rx, ry, rz);
+            X.nj.x += rx; X.nj.y += ry; X.nj.z += rz;
+            sx[lane] = X.nj;
             // (once per chunk; the 16-B stride makes this store a 4-way bank conflict)
-            if (UNI) sl[lane].x = nl.y; else *reinterpret_cast<float2*>(&sl[lane]) = nl;
+            if (UNI) sl[lane].x = X.nl.y; else *reinterpret_cast<float2*>(&sl[lane]) = X.nl;
         }
         WAVE_LDS_SYNC();
-        if (c + wv < nmc) nmq = a.masks[(size_t)(mbase + c + wv) * 64 + lane];
-        if (c + wv < nchunks) {
-            const uint32_t js = ent_n.x * MDX_CLUSTER + (lane & 7);
-            nj = a.posq[js]; ny = ent_n.y; njc = ent_n.x;
-            if (UNI) nl.y = lj_eps[2 * js]; else nl = a.lj[js];
-            if (STEP) nf = a.st_fprev[js];
-            if (ENERGY && HALF) nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
-            if (c + 2 * wv < nchunks) ent_n = entries[e0 + (c + 2 * wv) * 8 + (lane >> 3)];
+        if constexpr (TWO) {
+            // Every load unconditional: behind a branch the loaded registers meet their old values in a phi, the compiler resolves it
+            // with copies right behind the load, and the copies wait for the load just issued.  A set with no chunk left reads the
+            // current chunk's records again (valid addresses, lines this wave has just had), and nothing uses them.
+            // (X.ent is a list entry at all times - the set's next one, the null entry of the prologue or such a re-read - so js is an atom.)
+            const uint32_t ce = c + 2u * ps < nchunks ? c + 2u * ps : c;
+            const uint32_t js = X.ent.x * MDX_CLUSTER + (lane & 7);
+            X.ny = X.ent.y; X.njc = X.ent.x;
+            asm volatile("" : "+v"(X.ny), "+v"(X.njc));
+            X.nj = a.posq[js];
+            X.nl.y = lj_eps[2 * js];
+            X.ent = entries[e0 + ce * 8 + (lane >> 3)];
+        } else {
+        if (c + ps < nmc) X.nmq = a.masks[(size_t)(mbase + c + ps) * 64 + lane];
+        if (c + ps < nchunks) {
+            const uint32_t js = X.ent.x * MDX_CLUSTER + (lane & 7);
+            X.ny = X.ent.y; X.njc = X.ent.x;
+            // (copied HERE: sunk below the entry's load, the copies keep the load out of the entry's registers.  Not in the STEP bodies,
+            // which sit at 128 VGPRs with scratch and took 4 - 16 B more of it with the pin)
+            if (!STEP) asm volatile("" : "+v"(X.ny), "+v"(X.njc));
+            X.nj = a.posq[js];
+            if (UNI) X.nl.y = lj_eps[2 * js]; else X.nl = a.lj[js];
+            if (STEP) X.nf = a.st_fprev[js];
+            if (ENERGY && HALF) X.nown = a.energy_all ? 1.0f : (float)((a.slot_flags[js] >> 1) & 1u);
+            if (c + 2 * ps < nchunks) X.ent = entries[e0 + (c + 2 * ps) * 8 + (lane >> 3)];
+        }
         }
         float celj = 0.f, cecoul = 0.f, cevir = 0.f, cecross = 0.f, cedudl = 0.f;   // (ENERGY) fp32 partial sums of this chunk
         uint32_t newy = cur_y & 0xFFu;                                // (pruning launch) this lane's entry word with the inner mask
@@ -606,7 +661,32 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
                 unsafeAtomicAdd(fbase + (size_t)slot * 4 + comp, sgf[atom * 4 + comp]);
             }
         }
-    }
+    };
+    auto chunk_pass = [&](auto masked_tag, const uint32_t c_begin, const uint32_t c_end) __attribute__((always_inline)) {
+        for (uint32_t c = c_begin; c < c_end; c += wv) chunk(masked_tag, std::false_type{}, c, S0);
+    };
+    // (LATCH2) the plain chunks, two per trip: set 0, then set 1.  At the hand-over set 0 holds the first plain chunk and the entry of the
+    // second, as the one-set loop in front left them; set 1 is loaded from that entry, and each set fetches the entry of ITS next chunk.
+    // These few loads are waited for once per tile.  (X.ent is a list entry at all times, chunk(): the addresses are atoms.)
+    auto plain_pass2 = [&](const uint32_t c_begin, const uint32_t c_end) __attribute__((always_inline)) {
+        if (c_begin >= c_end) return;
+        {
+            const uint32_t js = S0.ent.x * MDX_CLUSTER + (lane & 7);
+            S1.ny = S0.ent.y; S1.njc = S0.ent.x;
+            S1.nj = a.posq[js];
+            S1.nl.y = lj_eps[2 * js];
+            const uint32_t c2 = c_begin + 2u * wv < nchunks ? c_begin + 2u * wv : c_begin, c3 = c_begin + 3u * wv < nchunks ? c_begin + 3u * wv : c_begin;
+            // (set 0's entry LAST: the first chunk needs it at once, and the wait for the youngest load retires them all - with
+            // a younger one in flight the compiler's count for set 1's entry stays in the loop as a second wait per trip)
+            S1.ent = entries[e0 + c3 * 8 + (lane >> 3)];
+            S0.ent = entries[e0 + c2 * 8 + (lane >> 3)];
+        }
+        for (uint32_t c = c_begin; c < c_end; c += wv) {
+            chunk(std::false_type{}, std::true_type{}, c, S0);
+            c += wv;
+            if (c >= c_end) break;
+            chunk(std::false_type{}, std::true_type{}, c, S1);
+        }
     };
 #ifndef NB_SPLIT_MASKED
 #define NB_SPLIT_MASKED 1
@@ -614,7 +694,8 @@ __device__ __forceinline__ void nb_cluster_body(const NbArgs& a, const bool owne
     if (NB_SPLIT_MASKED) {
         const uint32_t c_mid = c_first < nchunks ? c_first : nchunks;      // this wave's first plain chunk
         chunk_pass(std::true_type{}, (uint32_t)part, c_mid);
-        chunk_pass(std::false_type{}, c_mid, nchunks);
+        if constexpr (LATCH2) plain_pass2(c_mid, nchunks);
+        else chunk_pass(std::false_type{}, c_mid, nchunks);
     } else chunk_pass(std::true_type{}, (uint32_t)part, nchunks);
     // sum the eight j-lanes of every i-atom (lanes ii, ii+8, ..., ii+56), then lane (ii, jj) keeps
     // i-cluster ci == jj: slot tile*64 + jj*8 + ii == tile*64 + lane, a coalesced store.
@@ -821,24 +902,24 @@ __global__ __launch_bounds__((SPLIT > 1 ? WPT / SPLIT : (WPT > NB_WAVES ? WPT : 
 // The launches that exist with a constant-sigma^2 body (UNI; handles with one LJ atom type, `uni`): force-only, Lorentz-Berthelot, not
 // the softened Coulomb - the one-wave half-list kernels (plain list, the dual-list twins, the merged launch) and the full-list
 // kernels of four and eight waves per tile.  Everything else, and every handle that is not eligible, gets the general body.
-// Returns whether the UNI body went out (mdx_pair_body_info).
+// Returns the body that went out (mdx_pair_body_info): bit 0 = the UNI body, bit 1 = its chunk loop with two register sets (LATCH2).
 template <bool ENERGY, int COUL, bool G, bool S, int WPT, bool HALF, int DUAL>
-static bool launch_cluster(bool uni, dim3 g, dim3 b, uint32_t lds, hipStream_t st, const NbArgs& a) {
+static uint32_t launch_cluster(bool uni, dim3 g, dim3 b, uint32_t lds, hipStream_t st, const NbArgs& a) {
     if constexpr (!ENERGY && !G && COUL != CM_SOFT) {
         if (uni) {
             hipLaunchKernelGGL((nb_cluster_kernel<false, COUL, false, S, WPT, HALF, false, DUAL, false, 1, true>), g, b, lds, st, a);
-            return true;
+            return 1u | (nb_latch2(HALF, true, WPT, false, false, false) ? 2u : 0u);
         }
     }
     hipLaunchKernelGGL((nb_cluster_kernel<ENERGY, COUL, G, S, WPT, HALF, false, DUAL>), g, b, lds, st, a);
-    return false;
+    return 0u;
 }
 
 template <bool ENERGY, int COUL>
 void launch_variant(mdx_handle* h, const NbArgs& a_in, bool geom, bool samecut) {
     NbArgs a = a_in;
     const bool uni = h->uni_lj && !h->alch_on && !geom && a.p.uni_c != 0.f;
-    bool uni_used = false;
+    uint32_t uni_used = 0u;      // (launch_cluster's word)
     const int var = mdx_nb_variant(h);
     // waves per tile: split a tile's list over the 4 waves of its workgroup when the launch has
     // fewer tiles than ~3 per SIMD (the chip holds 4 waves/SIMD of this kernel on 1024 SIMDs)
@@ -985,7 +1066,7 @@ void launch_variant(mdx_handle* h, const NbArgs& a_in, bool geom, bool samecut) 
 #undef NB_DUAL
 #undef NB_STEP
     // (mdx_pair_body_info: did the constant-sigma^2 body go out - by the step loop, by anything)
-    if (a.inner || (h->nb_step >= 0 && a.gate)) h->pair_body_step = uni_used ? 1u : 0u;
-    h->pair_body_any = uni_used ? 1u : 0u;
+    if (a.inner || (h->nb_step >= 0 && a.gate)) h->pair_body_step = uni_used;
+    h->pair_body_any = uni_used;
 }
 

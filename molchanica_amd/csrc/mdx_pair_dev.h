@@ -40,6 +40,18 @@ __device__ __forceinline__ float jforce_reduce8(const float g[3], const bool sel
     return v;
 }
 
+// The image shift an entry's 5-bit code stands for: code = (kx + 1) + 3 (ky + 1) + 9 (kz + 1), k in {-1, 0, 1}; 13 = no shift (list
+// padding carries it).  The one statement of the decode: the chunk loops add these products to the j-atom (the compiler contracts
+// product and add into an FMA).  (The same rows read from a 32-row table in the free halves of the Lennard-Jones strip - two LDS reads
+// and three adds for 14 VALU and 3 FMA per chunk - measured +0.1 % alone and +0.3 % on the two-set loop, under the bar both times:
+// profiles/walk_latch_ab.txt.)
+__device__ __forceinline__ void image_shift_row(const uint32_t code, const float (&shift)[3], float& rx, float& ry, float& rz) {
+    const int kx = (int)(code % 3u) - 1, ky = (int)((code / 3u) % 3u) - 1, kz = (int)(code / 9u) - 1;
+    rx = (float)kx * shift[0];
+    ry = (float)ky * shift[1];
+    rz = (float)kz * shift[2];
+}
+
 #ifndef NB_IFORCE_ROWS
 #define NB_IFORCE_ROWS 1      // 1: a half-list tile's i-forces leave as four contiguous 256-B atomics (iforce_add_rows); 0: three strided ones
 #endif

@@ -728,6 +728,8 @@ class MdState:
         out = (C.c_uint32 * 4)()
         _check(load_library().mdx_pair_body_info(self._h, out))
         return {"eligible": bool(out[0]), "step": bool(out[1]), "any": bool(out[2]), "c_bits": int(out[3]),
+                # the chunk loop of that body: two register sets, one vector-memory wait per two chunks (one-wave half-list kernels)
+                "step_two_sets": bool(out[1] & 2), "any_two_sets": bool(out[2] & 2),
                 "c": float(np.array([out[3]], np.uint32).view(np.float32)[0])}
 
     def skin(self):
