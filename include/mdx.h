@@ -704,8 +704,8 @@ int      mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t count, ui
  * rounds with round 0 among them, evaluations of all rounds).  With n_rounds == 1, best_out, best_rows_out and best_dih_out are
  * poses_out, rows_out and dih_out of mdx_refine_poses_flex bit for bit.  A walker gives the same bits alone or in a batch of any size,
  * at any place in it, given the same stream id; a search of R rounds and one of R' > R rounds agree on every round < R.
- * Not part of it: receptor or ring flexibility, other local optimisers, clustering of the results, exchange between walkers,
- * continuing a search across calls, decomposed handles, alchemical windows, ligands above 256 atoms or 32 torsions. */
+ * Not part of it: receptor or ring flexibility, other local optimisers, exchange between walkers (clustering the results is
+ * mdx_cluster_poses, below), continuing a search across calls, decomposed handles, alchemical windows, ligands above 256 atoms or 32 torsions. */
 #define MDX_SEARCH_MAX_ROUNDS 1024u
 typedef struct { uint32_t n_rounds; float trans_amp, rot_amp, tors_amp, kT; uint64_t seed; mdx_flex_opts refine; } mdx_search_opts;
 int      mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_walkers, const float* starts /* [n_walkers][count][3] */,
@@ -715,6 +715,54 @@ int      mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_
                           uint32_t n_groups, double* best_score_out_or_null /* [n_walkers]: S */, float* best_dih_out_or_null /* [n_walkers] */,
                           uint32_t* best_round_out_or_null /* [n_walkers] */,
                           uint32_t* stats_out_or_null /* [n_walkers][4]: rounds accepted, accepted uphill, non-finite rounds, evaluations in total */);
+
+/* ---- pose distances and clustering: symmetry-aware RMSD in the receptor's frame, greedy leader clustering by it --------------------------
+ * What follows a search: rank the poses by score, keep a pose only if it is further than an RMSD cutoff from every pose already kept,
+ * report the distinct modes with their populations (mdx_cluster_poses); and how far poses are from given ones, such as a crystal
+ * ligand (mdx_pose_rmsd).  The handle gives its device, stream, box and grow-on-demand scratch only: energy groups are not required,
+ * nothing of its state is read, it is not changed and continues bit for bit like one that made no such call.
+ *
+ * Inputs.  Poses are fp32 [n][count][3] in caller order, each one whole molecule.  mask: uint8 [count], non-zero = the atom counts;
+ * NULL = all atoms; M = the masked atoms in atom order, n_m = |M| >= 1.  perms: uint32 [n_perms][count], the ligand's graph
+ * automorphisms as atom -> atom maps, perms[0] the identity; n_perms == 0 means the identity only.
+ * Centroid.  c(p) = the fp64 mean over M, in atom order, of the coordinates converted to fp64 (the sum, then one division by n_m).
+ * Image shift.  On a periodic axis of the handle s_axis = L_axis rint((c(b)_axis - c(a)_axis) / L_axis), L_axis = (double) box_hi -
+ * (double) box_lo of the handle's current box; s_axis = 0 on an axis that is not periodic (s = 0 on a vacuum handle).  Two poses whose
+ * centroids are nearer than half a box get s = 0 exactly.
+ * Distance.  Under permutation pi: acc_pi(a, b) = sum over k in M, in atom order, then x, y, z, of acc = acc + d d with
+ * d = ((double) a_k - (double) b_pi(k)) + s, no contraction.  D(a, b) = min over pi, in caller order, of acc_pi.  rmsd(a, b) =
+ * sqrt(D / n_m), rounded to fp32.  a is always the row pose or the leader; b is the one whose atoms are permuted.  D is symmetric when
+ * the perms are a group (molchanica_amd.topology.ligand_automorphisms returns one).
+ * Within the cutoff.  T = ((double) cut (double) cut) n_m, computed once; a pair is within the cutoff when D <= T.  cut == 0 is legal:
+ * only coincident poses join.
+ * Clustering (greedy leader, the de-duplication rule of Vina-style programs).  Rank the poses by (score ascending, index ascending);
+ * scores are fp64, +inf is legal and ranks last.  Visit the poses in rank order: a pose joins the first leader, in leader order, that
+ * it is within the cutoff of, with the leader as a; otherwise it becomes the next leader.  *n_clusters_out = the number of leaders;
+ * leader_out[c] = the caller index of cluster c's leader, leaders in rank order (entries from n_clusters on are left untouched - size
+ * the arrays for n_poses); cluster_of_out[p] = the cluster of pose p; rmsd_to_leader_out[p] = rmsd(leader, p), 0 for a leader - the bits
+ * mdx_pose_rmsd returns for that pair; size_out[c] = the members of cluster c, its leader among them.
+ * A pose pair gives the same bits in a batch of any size, at any place in it.
+ *
+ * MDX_EPARAM (mdx_last_error says which; a refused call writes nothing to any output): count == 0 or > MDX_POSE_MAX_ATOMS; n_poses, n_a
+ * or n_b above MDX_CLUSTER_MAX_POSES; a required pointer NULL; a mask that is all zero; n_perms > MDX_CLUSTER_MAX_PERMS, or perms NULL with
+ * n_perms > 0; a perm that is not a bijection of 0..count-1 (the error names it); perms[0] not the identity; a perm that maps a masked
+ * atom to an unmasked one; rmsd_cut negative or not finite; a coordinate that is not finite; a score that is NaN; a decomposed handle.
+ * n_poses == 0 succeeds and does nothing, except that *n_clusters_out = 0; n_a == 0 or n_b == 0 succeeds and writes nothing.
+ * One wait per call.  Under mdx_profile(1) the device time of the pair tiles is added to nb_ms_sum, of the gather to bonded_ms_sum, of
+ * the leader scan to integ_ms_sum and of the assignment to fused_ms_sum of mdx_get_stats (tools/pose_cluster_rates.py reads them there).
+ * Not part of it: superposition (Kabsch) RMSD - docking RMSD is taken in the receptor's frame -, other linkages than the greedy leader,
+ * more than 16384 poses per call, weighted masks, clustering inside mdx_search_poses itself, decomposed handles. */
+#define MDX_CLUSTER_MAX_POSES 16384u
+#define MDX_CLUSTER_MAX_PERMS 64u
+int      mdx_pose_rmsd(mdx_handle* h, uint32_t count, uint32_t n_a, const float* poses_a /* [n_a][count][3] */, uint32_t n_b,
+                       const float* poses_b_or_null /* [n_b][count][3]; NULL: A against A (n_b is ignored) */,
+                       const uint8_t* mask_or_null /* [count] */, uint32_t n_perms, const uint32_t* perms_or_null /* [n_perms][count] */,
+                       float* out /* [n_a][n_b] */);
+int      mdx_cluster_poses(mdx_handle* h, uint32_t count, uint32_t n_poses, const float* poses /* [n_poses][count][3] */,
+                           const double* scores /* [n_poses] */, const uint8_t* mask_or_null /* [count] */, uint32_t n_perms,
+                           const uint32_t* perms_or_null /* [n_perms][count] */, float rmsd_cut, uint32_t* n_clusters_out,
+                           uint32_t* leader_out_or_null /* [n_poses] */, uint32_t* cluster_of_out_or_null /* [n_poses] */,
+                           float* rmsd_to_leader_out_or_null /* [n_poses] */, uint32_t* size_out_or_null /* [n_poses] */);
 
 /* ---- multi-GPU: one periodic box spatially decomposed over the GPUs of a node (the reference is
  * single-device, src/util.rs:1086 `CudaContext::new(0)`, so this is new capability, not parity) -------------------

@@ -244,6 +244,44 @@ public:
         return r;
     }
 
+    /// mdx_pose_rmsd: the symmetry-aware RMSD, in the receptor's frame, of every pose of a against every pose of b (b empty: of a) - the
+    /// minimum over the symmetry images `perms` ([n_perms][count], the identity first; empty: the identity only) of the root mean square
+    /// distance over the atoms of `mask` ([count]; empty: all), across the nearest periodic image of the centroids (mdx.h states the rule).
+    /// -> [n_a][n_b]
+    std::vector<float> pose_rmsd(uint32_t count, const std::vector<float>& a, const std::vector<float>& b = {}, const std::vector<uint8_t>& mask = {},
+                                 const std::vector<uint32_t>& perms = {}) {
+        if (count == 0 || a.size() % (3 * (size_t)count) != 0 || b.size() % (3 * (size_t)count) != 0)
+            throw std::invalid_argument("pose_rmsd: poses must hold [n][count][3] floats");
+        if ((!mask.empty() && mask.size() != count) || perms.size() % count != 0) throw std::invalid_argument("pose_rmsd: mask holds [count], perms [n_perms][count]");
+        const uint32_t na = (uint32_t)(a.size() / (3 * (size_t)count)), nb = b.empty() ? na : (uint32_t)(b.size() / (3 * (size_t)count));
+        std::vector<float> out((size_t)na * nb, 0.f);
+        check(mdx_pose_rmsd(h_, count, na, a.data(), nb, b.empty() ? nullptr : b.data(), mask.empty() ? nullptr : mask.data(),
+                            (uint32_t)(perms.size() / count), perms.empty() ? nullptr : perms.data(), out.data()));
+        return out;
+    }
+    /// mdx_cluster_poses: greedy leader clustering by that distance - the poses ranked by (score, index); a pose joins the first leader it
+    /// is within rmsd_cut of, or becomes the next leader.
+    struct PoseClusters {
+        std::vector<uint32_t> leaders, sizes;              ///< [n_clusters]: pose index of every cluster's leader, best first; members
+        std::vector<uint32_t> cluster_of;                  ///< [n]
+        std::vector<float> rmsd_to_leader;                 ///< [n], 0 for a leader
+    };
+    PoseClusters cluster_poses(uint32_t count, const std::vector<float>& poses, const std::vector<double>& scores, float rmsd_cut,
+                               const std::vector<uint8_t>& mask = {}, const std::vector<uint32_t>& perms = {}) {
+        if (count == 0 || poses.size() % (3 * (size_t)count) != 0) throw std::invalid_argument("cluster_poses: poses must hold [n][count][3] floats");
+        const uint32_t n = (uint32_t)(poses.size() / (3 * (size_t)count));
+        if (scores.size() != n) throw std::invalid_argument("cluster_poses: scores must hold one entry per pose");
+        if ((!mask.empty() && mask.size() != count) || perms.size() % count != 0) throw std::invalid_argument("cluster_poses: mask holds [count], perms [n_perms][count]");
+        PoseClusters r;
+        r.leaders.assign(n, 0u); r.sizes.assign(n, 0u); r.cluster_of.assign(n, 0u); r.rmsd_to_leader.assign(n, 0.f);
+        uint32_t k = 0;
+        check(mdx_cluster_poses(h_, count, n, poses.data(), scores.data(), mask.empty() ? nullptr : mask.data(), (uint32_t)(perms.size() / count),
+                                perms.empty() ? nullptr : perms.data(), rmsd_cut, &k, r.leaders.data(), r.cluster_of.data(), r.rmsd_to_leader.data(),
+                                r.sizes.data()));
+        r.leaders.resize(k); r.sizes.resize(k);
+        return r;
+    }
+
     /// `md.cell = SimBox::new(lo, hi)` + `md.rebuild_spatial_caches()` (sol_shrinking_box.rs:600-603, 632).
     void set_cell(const SimBox& b) { check(mdx_set_box(h_, b.bounds_low.data(), b.bounds_high.data())); }
     SimBox cell() const {

@@ -31,10 +31,20 @@ POSE_MAX_TORSIONS = 32           # MDX_POSE_MAX_TORSIONS: the most torsions mdx_
 FLEX_DIHEDRALS = 0x1             # MDX_FLEX_DIHEDRALS
 SEARCH_MAX_ROUNDS = 1024         # MDX_SEARCH_MAX_ROUNDS: the most rounds mdx_search_poses takes
 
+CLUSTER_MAX_POSES = 16384        # MDX_CLUSTER_MAX_POSES: the most poses mdx_pose_rmsd (per side) and mdx_cluster_poses take
+CLUSTER_MAX_PERMS = 64           # MDX_CLUSTER_MAX_PERMS: the most symmetry images of the ligand they take
+
 _fp = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
+
+# mdx_pose_rmsd(h, count, n_a, poses_a, n_b, poses_b_or_null, mask_or_null, n_perms, perms_or_null, out) and
+# mdx_cluster_poses(h, count, n_poses, poses, scores, mask_or_null, n_perms, perms_or_null, rmsd_cut, n_clusters_out, leader_out_or_null,
+#                   cluster_of_out_or_null, rmsd_to_leader_out_or_null, size_out_or_null)
+POSE_RMSD_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_uint32, _fp, C.c_uint32, _fp, _u8p, C.c_uint32, _u32p, _fp]
+CLUSTER_POSES_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_double), _u8p, C.c_uint32, _u32p, C.c_float, _u32p, _u32p,
+                          _u32p, _fp, _u32p]
 
 
 class CSystem(C.Structure):

@@ -294,6 +294,8 @@ struct DeviceState {
     void* ps_flex = nullptr; void* ps_flex_tab = nullptr;
     // mdx_search_poses: the search records, current and best coordinates, best rows / rigid and stream ids of one chunk (SearchLayout)
     void* ps_search = nullptr;
+    // mdx_pose_rmsd / mdx_cluster_poses (mdx_pose_cluster.hip): the block of one call (ClLayout) and the pair matrix - fp32 rmsd or bits
+    void* ps_cl = nullptr; void* ps_cl_mat = nullptr;
 };
 
 struct MdxDecomp;   // mdx_comm.h: the handle is one rank of a spatially decomposed box
@@ -363,7 +365,7 @@ struct mdx_handle {
     size_t ps_cap_stage = 0, ps_cap_slab = 0, ps_cap_fslab = 0;      // bytes of ps_stage, ps_slab (ps_rows with it), ps_fslab (ps_fout, ps_rigid)
     // mdx_refine_poses_flex: what ps_flex_tab was built for (with ps_first / ps_count / ps_epoch) and how many dihedral terms it holds
     bool fx_valid = false; uint32_t fx_first = 0, fx_count = 0, fx_root = 0, fx_flags = 0, fx_terms = 0; uint64_t fx_epoch = 0;
-    std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0, ps_cap_search = 0;
+    std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0, ps_cap_search = 0, ps_cap_cl = 0, ps_cap_cl_mat = 0;
     bool alch_on = false; double alch_lambda = 0.0; uint32_t alch_lo = 0, alch_hi = 0;
     float sc_alpha = 0.5f, sc_sigma_min = 3.0f;   // soft core of the alchemical window (mdx_set_alchemical_softcore)
     std::vector<double> foreign_lams;             // mdx_set_foreign_lambdas (survives window changes; empty: none)

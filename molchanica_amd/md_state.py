@@ -17,7 +17,8 @@ import os
 
 import numpy as np
 
-from ._abi import (CCommDiag, CFlexOpts, CHBond, CConfig, CEnergies, CRefineOpts, CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE,
+from ._abi import (CCommDiag, CFlexOpts, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
+                   CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, POSE_RMSD_ARGTYPES,
                    MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, VEL, MdConfig, MdSystem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -176,6 +177,8 @@ def load_library():
                                           _fp, C.c_uint32, _fp, _fp, _fp, _fp, _u32p, _u32p]
     lib.mdx_search_poses.argtypes = [H, C.c_uint32, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, _u32p,
                                      C.POINTER(CSearchOpts), _fp, _fp, C.c_uint32, C.POINTER(C.c_double), _fp, _u32p, _u32p]
+    lib.mdx_pose_rmsd.argtypes = POSE_RMSD_ARGTYPES
+    lib.mdx_cluster_poses.argtypes = CLUSTER_POSES_ARGTYPES
     _lib = lib
     return lib
 
@@ -445,6 +448,72 @@ class MdState:
                                     C.byref(opts), y.ctypes.data_as(_fp), r.ctypes.data_as(_fp), n, sc.ctypes.data_as(C.POINTER(C.c_double)),
                                     e.ctypes.data_as(_fp), br.ctypes.data_as(_u32p), stt.ctypes.data_as(_u32p)))
         return y, (r[:, :n] if n else r[:, :0]), sc, e, br, stt
+
+    @staticmethod
+    def _cluster_args(who: str, poses, mask, perms):
+        """The shape and dtype checks pose_rmsd() and cluster_poses() share -> (poses, mask or None, perms or None), contiguous"""
+        if not isinstance(poses, np.ndarray) or poses.dtype != np.float32:
+            raise ParamError(f"{who}: poses must be a float32 ndarray [N, count, 3]")
+        if poses.ndim != 3 or poses.shape[2] != 3 or not 1 <= poses.shape[1] <= POSE_MAX_ATOMS or poses.shape[0] > CLUSTER_MAX_POSES:
+            raise ParamError(f"{who}: poses must have shape [N, count, 3] with N <= {CLUSTER_MAX_POSES} and 1 <= count <= {POSE_MAX_ATOMS}, "
+                             f"got {poses.shape}")
+        count = poses.shape[1]
+        m = None
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.dtype.kind not in "biu" or m.shape != (count,):
+                raise ParamError(f"{who}: mask must be booleans or integers [count]")
+            m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+        pm = None
+        if perms is not None:
+            pm = np.asarray(perms)
+            if pm.dtype.kind not in "iu" or pm.ndim != 2 or pm.shape[1] != count or pm.shape[0] > CLUSTER_MAX_PERMS:
+                raise ParamError(f"{who}: perms must be integers [P, count] with P <= {CLUSTER_MAX_PERMS}")
+            if (pm < 0).any() or (pm >= count).any():
+                raise ParamError(f"{who}: perms hold atom indices (< count)")
+            pm = np.ascontiguousarray(pm, dtype=np.uint32)
+            if pm.shape[0] == 0:
+                pm = None
+        return np.ascontiguousarray(poses), m, pm
+
+    def pose_rmsd(self, poses_a, poses_b=None, mask=None, perms=None):
+        """`mdx_pose_rmsd`: the symmetry-aware RMSD, in the receptor's frame, of every pose of poses_a against every pose of poses_b
+        (None: of poses_a) - the minimum over the ligand's symmetry images `perms` (uint [P, count], the identity first, e.g. from
+        topology.ligand_automorphisms; None: the identity only) of the root mean square distance over the atoms of `mask` ([count],
+        None: all), across the periodic image that brings the centroids together; include/mdx.h states the rule.  poses: float32
+        [A, count, 3] and [B, count, 3].  -> float32 [A, B].  The handle is left as it is."""
+        a, m, pm = self._cluster_args("pose_rmsd", poses_a, mask, perms)
+        b = None
+        if poses_b is not None:
+            b, _, _ = self._cluster_args("pose_rmsd", poses_b, None, None)
+            if b.shape[1] != a.shape[1]:
+                raise ParamError("pose_rmsd: poses_a and poses_b must hold the same number of atoms")
+        A, B = a.shape[0], (a.shape[0] if b is None else b.shape[0])
+        out = np.zeros((A, B), dtype=np.float32)
+        _check(load_library().mdx_pose_rmsd(self._h, a.shape[1], A, a.ctypes.data_as(_fp), B, None if b is None else b.ctypes.data_as(_fp),
+                                            None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8)), 0 if pm is None else pm.shape[0],
+                                            None if pm is None else pm.ctypes.data_as(_u32p), out.ctypes.data_as(_fp)))
+        return out
+
+    def cluster_poses(self, poses, scores, rmsd_cut: float, mask=None, perms=None):
+        """`mdx_cluster_poses`: greedy leader clustering of a pose batch by the distance of pose_rmsd() - the poses are ranked by
+        (score ascending, index ascending); in that order a pose joins the first leader it is within rmsd_cut A of, or becomes the next
+        leader.  poses: float32 [N, count, 3]; scores: float64 [N] (+inf allowed, NaN refused), e.g. best and score of search_poses().
+        -> (leaders [K] u32: pose index of every cluster's leader, best first; cluster_of [N] u32; rmsd_to_leader [N] f32, 0 for a
+        leader; sizes [K] u32).  The handle is left as it is."""
+        a, m, pm = self._cluster_args("cluster_poses", poses, mask, perms)
+        if not isinstance(scores, np.ndarray) or scores.dtype != np.float64 or scores.shape != (a.shape[0],):
+            raise ParamError("cluster_poses: scores must be a float64 ndarray [N]")
+        sc = np.ascontiguousarray(scores)
+        N = a.shape[0]
+        k = C.c_uint32(0)
+        lead, cl, sz = (np.zeros(N, dtype=np.uint32) for _ in range(3))
+        rm = np.zeros(N, dtype=np.float32)
+        _check(load_library().mdx_cluster_poses(self._h, a.shape[1], N, a.ctypes.data_as(_fp), sc.ctypes.data_as(C.POINTER(C.c_double)),
+                                                None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8)), 0 if pm is None else pm.shape[0],
+                                                None if pm is None else pm.ctypes.data_as(_u32p), float(rmsd_cut), C.byref(k),
+                                                lead.ctypes.data_as(_u32p), cl.ctypes.data_as(_u32p), rm.ctypes.data_as(_fp), sz.ctypes.data_as(_u32p)))
+        return lead[:k.value].copy(), cl, rm, sz[:k.value].copy()
 
     # -- position restraints (include/mdx.h: E = k max(0, |x - r0| - b)^2) ------------------------------------------------
     def set_position_restraints(self, idx, ref=None, k=1.0, flat_bottom=None):

@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._abi import CLUSTER_MAX_PERMS
+
 
 def adjacency(n_atoms: int, bonds: np.ndarray) -> list[list[int]]:
     adj: list[list[int]] = [[] for _ in range(n_atoms)]
@@ -82,3 +84,76 @@ def csr_from_pairs(n_atoms: int, pairs: np.ndarray):
     offsets = np.zeros(n_atoms + 1, dtype=np.uint32)
     offsets[1:] = np.cumsum(counts)
     return offsets, both[:, 1].astype(np.uint32)
+
+
+def ligand_automorphisms(n: int, bonds, keys, mask=None, cap: int = CLUSTER_MAX_PERMS) -> np.ndarray:
+    """The symmetry images `MdState.pose_rmsd` / `cluster_poses` take: the automorphisms of the bond graph on n atoms that preserve the
+    per-atom `keys` (e.g. the LJ type index), the identity first, de-duplicated by their action on the atoms of `mask` ([n] booleans,
+    None: all) - with a heavy-atom mask the permutations of methyl hydrogens collapse; of the perms that act alike the first found
+    stands for all (its unmasked atoms map in one consistent way).  -> uint32 [P, n].  Raises ParamError when more than `cap` distinct
+    ones exist: a truncated set is not a group, and the distance would stop being symmetric.  Plain backtracking in atom order over
+    key- and degree-compatible candidates."""
+    from .md_state import ParamError
+    n = int(n)
+    keys = np.asarray(keys).reshape(-1)
+    if keys.shape[0] != n:
+        raise ParamError("ligand_automorphisms: keys must hold one entry per atom")
+    b = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
+    if b.size and (b.min() < 0 or b.max() >= n):
+        raise ParamError("ligand_automorphisms: a bond names an atom outside 0..n-1")
+    m = np.ones(n, bool) if mask is None else np.asarray(mask).reshape(-1) != 0
+    if m.shape[0] != n or not m.any():
+        raise ParamError("ligand_automorphisms: mask must select at least one of the n atoms")
+    adj = [set(x) for x in adjacency(n, b)]
+    sig = [(keys[i].item(), len(adj[i])) for i in range(n)]
+    # visit the atoms so that each one after the first of its component has an earlier neighbour: candidates come from that
+    # neighbour's image, not from all atoms
+    order, parent, seen = [], {}, [False] * n
+    for root in range(n):
+        if seen[root]:
+            continue
+        seen[root] = True
+        queue = [root]
+        parent[root] = -1
+        while queue:
+            i = queue.pop(0)
+            order.append(i)
+            for j in sorted(adj[i]):
+                if not seen[j]:
+                    seen[j] = True
+                    parent[j] = i
+                    queue.append(j)
+    masked = np.flatnonzero(m)
+    found, actions = [], set()
+    image, used = [-1] * n, [False] * n
+
+    def place(pos):
+        if pos == n:
+            act = tuple(image[i] for i in masked)
+            if act not in actions:
+                if len(found) >= cap:
+                    raise ParamError(f"ligand_automorphisms: more than cap = {cap} distinct symmetry images on the masked atoms")
+                actions.add(act)
+                found.append(list(image))
+            return
+        i = order[pos]
+        cands = range(n) if parent[i] < 0 else sorted(adj[image[parent[i]]])
+        for c in cands:
+            if used[c] or sig[c] != sig[i]:
+                continue
+            # every bond of i to an atom placed before it must be a bond of the images (equal degrees make the converse hold at the end)
+            if any(image[j] >= 0 and image[j] not in adj[c] for j in adj[i]):
+                continue
+            image[i], used[c] = c, True
+            place(pos + 1)
+            image[i], used[c] = -1, False
+
+    import sys
+    limit = sys.getrecursionlimit()
+    sys.setrecursionlimit(max(limit, n + 200))
+    try:
+        place(0)
+    finally:
+        sys.setrecursionlimit(limit)
+    found.sort(key=lambda p: (p != list(range(n)),))      # (stable: the identity first, the others in the order found)
+    return np.asarray(found, dtype=np.uint32).reshape(-1, n)
