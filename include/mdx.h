@@ -336,6 +336,14 @@ int mdx_pair_launch_info(const mdx_handle* h, uint32_t out[24]);
  * of that f32 value (0 when not eligible).
  * No call of the reference corresponds to it. */
 int mdx_pair_body_info(const mdx_handle* h, uint32_t out[4]);
+/* Diagnostics: the triad flavour of the fused bonded + kick + drift pass.  A handle in which every atom's bonded work is either nothing
+ * or one angle plus one or two bonds to the angle's other two atoms (a box of flexible three-site water; no dihedral, 1-4 pair, Ewald
+ * exclusion or position restraint anywhere) is eligible: the pass reads 8 bytes per atom - two partner slots and a code into a small
+ * table of shapes - instead of an offset and two or three 16-byte records, and computes the same bits.  out[0]: the handle is eligible
+ * (position restraints make it ineligible, clearing them eligible again), out[1]: distinct shapes (3 for such a water box), out[2]: the
+ * last fused launch took the triad flavour (MDX_FUSED_TRIAD=0 in the environment, read per launch: never), out[3]: 0.
+ * No call of the reference corresponds to it. */
+int mdx_fused_triad_info(const mdx_handle* h, uint32_t out[4]);
 /* The Verlet skin in force, and whether the library is still tuning it (mdx_config.skin == 0). */
 int mdx_get_skin(const mdx_handle* h, float* skin, int* tuning);
 

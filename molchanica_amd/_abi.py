@@ -45,6 +45,8 @@ _u8p = C.POINTER(C.c_uint8)
 POSE_RMSD_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_uint32, _fp, C.c_uint32, _fp, _u8p, C.c_uint32, _u32p, _fp]
 CLUSTER_POSES_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_double), _u8p, C.c_uint32, _u32p, C.c_float, _u32p, _u32p,
                           _u32p, _fp, _u32p]
+# mdx_fused_triad_info(h, out[4]): eligible, distinct shapes, the last fused launch took the triad flavour, 0
+FUSED_TRIAD_INFO_ARGTYPES = [C.c_void_p, _u32p]
 
 
 class CSystem(C.Structure):

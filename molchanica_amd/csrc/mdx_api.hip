@@ -44,6 +44,30 @@ static int alloc_n(T** dptr, size_t n) {
     return MDX_OK;
 }
 
+// Triads (mdx_triad_build): decided wherever the caller-order role tables are uploaded - mdx_create, posre_install.  An eligible handle
+// gets the caller-order records and the shape table on the device; any other keeps neither, and role_fill_body writes no tri_s.
+static int mdx_refresh_triads(mdx_handle* h, const std::vector<uint32_t>& off, const std::vector<RoleRec>& recs) {
+    DeviceState& d = h->d;
+    static_assert(sizeof(RoleRec) == 4 * sizeof(uint32_t), "RoleRec is four words");
+    std::vector<uint2> tri(h->N);
+    std::vector<uint32_t> shapes(4 * (size_t)MDX_TRIAD_SHAPE_CAP);
+    uint32_t ns = 0;
+    const bool ok = !recs.empty() && off.size() == (size_t)h->N + 1 &&
+                    mdx_triad_build(off.data(), reinterpret_cast<const uint32_t*>(recs.data()), h->N, reinterpret_cast<uint32_t*>(tri.data()),
+                                    shapes.data(), MDX_TRIAD_SHAPE_CAP, &ns) && ns > 0;
+    h->tri_ok = ok; h->tri_shapes = ok ? ns : 0u; h->tri_last = 0;
+    if (!ok) {
+        if (d.tri_o) { (void)hipFree(d.tri_o); d.tri_o = nullptr; }
+        if (d.tri_shape) { (void)hipFree(d.tri_shape); d.tri_shape = nullptr; }
+        return MDX_OK;
+    }
+    std::vector<uint4> sh(ns + 1);
+    for (uint32_t k = 0; k <= ns; ++k) sh[k] = make_uint4(shapes[4 * k], shapes[4 * k + 1], shapes[4 * k + 2], shapes[4 * k + 3]);
+    MDX_TRY(upload_vec(&d.tri_o, tri, h->stream)); MDX_TRY(upload_vec(&d.tri_shape, sh, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MDX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 extern "C" int mdx_device_count(void) {
     int n = 0;
@@ -145,7 +169,7 @@ static void free_device(mdx_handle* h) {
                     d.cell_count, d.cell_start, d.cell_cursor, d.sorted_orig, d.sorted_tmp, d.col_tiles, d.tile_start,
                     d.tile_col, d.scan_tmp, d.cl_lo, d.cl_hi, d.cl_kind, d.list_counts, d.entry_cnt, d.entry_off,
                     d.mchunk_cnt, d.mchunk_off, d.entries, d.entries_in, d.inner_nch, d.list_cursors, d.masks, d.role_off_o, d.role_rec_o, d.role_cnt_s,
-                    d.role_off_s, d.role_rec_s, d.role_prm, d.ctl, d.energy,
+                    d.role_off_s, d.role_rec_s, d.role_prm, d.tri_o, d.tri_s, d.tri_shape, d.ctl, d.energy,
                     d.flags_dev, d.bonded_part, d.bbox_red, d.pair_count, d.inner_count, d.pme_force, d.wstep_s, d.path, d.dprune, d.force_b, d.force_c, d.cons_o, d.cons_s, d.cons_tmp, d.cons_mask, d.cons_cnt, d.cons_off, d.cons_vir, d.vsite_o, d.vsite_s, d.gsite_o, d.gsite_s, d.gsite_tmp, d.pme_q, d.pme_f,
                     d.pme_theta, d.pme_q2, d.pme_f2, d.scratch4, d.tile_bnd, d.tile_scan, d.tile_order, d.tile_lpt, d.rb_ctl, d.scan_chain, d.grp, d.grp_mat, d.fl_hot, d.fl_slab, d.star_o, d.star_s, d.ewald_tab,
                     d.ps_cls, d.ps_p14, d.ps_stage, d.ps_slab, d.ps_rows, d.ps_fslab, d.ps_fout, d.ps_rigid, d.ps_flex, d.ps_flex_tab, d.ps_search, d.ps_cl, d.ps_cl_mat};
@@ -355,6 +379,7 @@ static int create_impl(const mdx_system* s, const mdx_config* c, int device, mdx
         MDX_TRY(upload_vec(&d.role_off_o, cnt, st)); MDX_TRY(upload_vec(&d.role_rec_o, recs, st));
         MDX_TRY(alloc_n(&d.role_rec_s, R));
         HIP_TRY(hipStreamSynchronize(st));
+        MDX_TRY(mdx_refresh_triads(h, cnt, recs));
     }
 
     // bonded / constrained pairs, kept for the hydrogen-bond donor table (mdx_set_hbond_detection)
@@ -1504,6 +1529,12 @@ extern "C" int mdx_pair_body_info(const mdx_handle* h, uint32_t out[4]) {
     return MDX_OK;
 }
 
+extern "C" int mdx_fused_triad_info(const mdx_handle* h, uint32_t out[4]) {
+    if (!h || !out) FAIL(MDX_EPARAM, "null argument");
+    out[0] = h->tri_ok ? 1u : 0u; out[1] = h->tri_shapes; out[2] = h->tri_last; out[3] = 0u;
+    return MDX_OK;
+}
+
 extern "C" int mdx_get_stats(mdx_handle* h, mdx_stats* out) {
     if (!h || !out) FAIL(MDX_EPARAM, "null argument");
     HIP_TRY(hipSetDevice(h->device));
@@ -1772,6 +1803,7 @@ static int posre_install(mdx_handle* h) {
     MDX_TRY(upload_vec(&d.role_off_o, off, st)); MDX_TRY(upload_vec(&d.role_rec_o, rec, st));
     MDX_TRY(alloc_n(&d.role_rec_s, R));
     HIP_TRY(hipStreamSynchronize(st));
+    MDX_TRY(mdx_refresh_triads(h, off, rec));      // (a restraint record makes the handle ineligible; clearing them all brings the triads back)
     h->forces_valid = false; h->e_cache_valid = false; h->e_pending = false;
     return mdx_refill_roles(h);
 }

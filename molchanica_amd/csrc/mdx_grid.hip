@@ -553,11 +553,26 @@ __device__ __forceinline__ void role_fill_body(uint32_t s, uint32_t S, const uin
                                                const uint8_t* __restrict__ lflag, const uint32_t* __restrict__ slot_of,
                                                const uint32_t* __restrict__ role_off_o, const RoleRec* __restrict__ rec_o,
                                                const uint32_t* __restrict__ role_off_s, RoleRec* __restrict__ rec_s,
-                                               uint32_t* __restrict__ err) {
+                                               uint32_t* __restrict__ err,
+                                               const uint2* __restrict__ tri_o, uint2* __restrict__ tri_s) {
     if (s >= S) return;
     const uint32_t o = orig_of[s];
-    if (o == MDX_INVALID || (lflag[o] & 1u)) return;
+    if (o == MDX_INVALID || (lflag[o] & 1u)) {
+        if (tri_o) tri_s[s] = make_uint2(0u, 0u);      // padding and ghost slots: "no roles"
+        return;
+    }
     const uint32_t g = gid[o];
+    if (tri_o) {
+        // triads (mdx_triad_build): the atom's 8 bytes, its two partners translated as the records' are below; the code rides in the top bytes
+        uint2 t = tri_o[g];
+        if ((t.x | t.y) >> 24) {
+            uint32_t sa = slot_of[t.x & 0xFFFFFFu], sb = slot_of[t.y & 0xFFFFFFu];
+            if (sa == MDX_INVALID) { atomicOr(err, 4u); sa = s; }
+            if (sb == MDX_INVALID) { atomicOr(err, 4u); sb = s; }
+            t.x = (sa & 0xFFFFFFu) | (t.x & 0xFF000000u); t.y = (sb & 0xFFFFFFu) | (t.y & 0xFF000000u);
+        }
+        tri_s[s] = t;
+    }
     const uint32_t b = role_off_o[g], n = role_off_o[g + 1] - b, w = role_off_s[s];
     for (uint32_t k = 0; k < n; ++k) {
         RoleRec r = rec_o[b + k];
@@ -575,8 +590,8 @@ __global__ void role_fill_kernel(uint32_t S, const uint32_t* __restrict__ orig_o
                                  const uint8_t* __restrict__ lflag, const uint32_t* __restrict__ slot_of,
                                  const uint32_t* __restrict__ role_off_o, const RoleRec* __restrict__ rec_o,
                                  const uint32_t* __restrict__ role_off_s, RoleRec* __restrict__ rec_s,
-                                 uint32_t* __restrict__ err) {
-    role_fill_body(blockIdx.x * blockDim.x + threadIdx.x, S, orig_of, gid, lflag, slot_of, role_off_o, rec_o, role_off_s, rec_s, err);
+                                 uint32_t* __restrict__ err, const uint2* __restrict__ tri_o, uint2* __restrict__ tri_s) {
+    role_fill_body(blockIdx.x * blockDim.x + threadIdx.x, S, orig_of, gid, lflag, slot_of, role_off_o, rec_o, role_off_s, rec_s, err, tri_o, tri_s);
 }
 
 // ================================================================================================
@@ -674,6 +689,7 @@ struct ListArgs {
     const uint32_t* T_dev;
     const uint32_t* rf_role_off_o; const RoleRec* rf_rec_o; const uint32_t* rf_role_off_s; RoleRec* rf_rec_s;
     const uint8_t* rf_lflag;
+    const uint2* rf_tri_o; uint2* rf_tri_s;      // triads (null: the handle is not eligible)
 };
 
 // MODE 0: count pass (sizes per tile, then a scan); MODE 1: fill pass; MODE 2: SINGLE pass - the tile's entries are
@@ -702,7 +718,7 @@ __global__ __launch_bounds__(LB_WAVES * 64) void build_list_kernel(ListArgs a) {
     }
     if (SINGLE && blockIdx.x >= a.list_grid) {     // the role lists ride along: independent of the pair list, and this launch leaves CUs idle
         role_fill_body((blockIdx.x - a.list_grid) * (LB_WAVES * 64) + threadIdx.x, a.rf_S, a.orig_of, a.gid, a.rf_lflag, a.slot_of,
-                       a.rf_role_off_o, a.rf_rec_o, a.rf_role_off_s, a.rf_rec_s, a.err);
+                       a.rf_role_off_o, a.rf_rec_o, a.rf_role_off_s, a.rf_rec_s, a.err, a.rf_tri_o, a.rf_tri_s);
         return;
     }
     const uint32_t per_xcd = (SINGLE ? a.list_grid : gridDim.x) >> 3;   // (a multiple of 8 workgroups) a contiguous eighth of the tiles per XCD
@@ -1478,7 +1494,7 @@ static int setup_grid(mdx_handle* h) {
         ALLOC(d.posq, S); ALLOC(d.lj, S); ALLOC(d.vel, S); ALLOC(d.force, S); ALLOC(d.ref, S); ALLOC(d.posq_alt, S); ALLOC(d.path, S); ALLOC(d.dprune, S);
         ALLOC(d.force_b, S); ALLOC(d.force_c, S);
         ALLOC(d.orig_of, S); ALLOC(d.slot_flags, S); ALLOC(d.pme_force, S);
-        ALLOC(d.role_cnt_s, S + 1); ALLOC(d.role_off_s, S + 1);
+        ALLOC(d.role_cnt_s, S + 1); ALLOC(d.role_off_s, S + 1); ALLOC(d.tri_s, S);
         ALLOC(d.tile_col, need_tiles);
         ALLOC(d.cl_lo, NC); ALLOC(d.cl_hi, NC); ALLOC(d.cl_kind, NC);
         ALLOC(d.list_counts, need_tiles);
@@ -1951,7 +1967,7 @@ static int rebuild_fast(mdx_handle* h, RebuildResult* res, bool* fell_back) {
     uint32_t rf_blocks = 0;
     if (h->n_roles) {
         a.rf_S = S_bound; a.rf_role_off_o = d.role_off_o; a.rf_rec_o = d.role_rec_o; a.rf_role_off_s = d.role_off_s;
-        a.rf_rec_s = d.role_rec_s; a.rf_lflag = d.lflag;
+        a.rf_rec_s = d.role_rec_s; a.rf_lflag = d.lflag; a.rf_tri_o = d.tri_o; a.rf_tri_s = d.tri_s;
         rf_blocks = div_up(S_bound, LB_WAVES * 64);
     }
     if (g.npop > 1) hipLaunchKernelGGL((build_list_kernel<LB_SINGLE, LB_PLAIN_DD>), dim3(a.list_grid + rf_blocks), dim3(LB_WAVES * 64), 0, st, a);
@@ -2160,7 +2176,7 @@ int mdx_rebuild(mdx_handle* h) {
                                d.lflag, d.role_off_o, d.role_cnt_s);
             MDX_TRY(mdx_exclusive_scan_u32(h, d.role_cnt_s, d.role_off_s, S + 1));
             a.rf_S = S; a.rf_role_off_o = d.role_off_o; a.rf_rec_o = d.role_rec_o; a.rf_role_off_s = d.role_off_s;
-            a.rf_rec_s = d.role_rec_s; a.rf_lflag = d.lflag;
+            a.rf_rec_s = d.role_rec_s; a.rf_lflag = d.lflag; a.rf_tri_o = d.tri_o; a.rf_tri_s = d.tri_s;
             rf_blocks = div_up(S, LB_WAVES * 64);
             roles_done = true;
         }
@@ -2225,7 +2241,7 @@ int mdx_rebuild(mdx_handle* h) {
                            d.lflag, d.role_off_o, d.role_cnt_s);
         MDX_TRY(mdx_exclusive_scan_u32(h, d.role_cnt_s, d.role_off_s, S + 1));
         hipLaunchKernelGGL(role_fill_kernel, dim3(div_up(S, 256)), dim3(256), 0, st, S, d.orig_of, d.gid, d.lflag,
-                           d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev);
+                           d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev, d.tri_o, d.tri_s);
     }
     MDX_TRY(mdx_remap_constraints(h));
     HIP_TRY(hipGetLastError());
@@ -2481,7 +2497,7 @@ int mdx_refill_roles(mdx_handle* h) {
                        d.lflag, d.role_off_o, d.role_cnt_s);
     MDX_TRY(mdx_exclusive_scan_u32(h, d.role_cnt_s, d.role_off_s, S + 1));
     hipLaunchKernelGGL(role_fill_kernel, dim3(div_up(S, 256)), dim3(256), 0, st, S, d.orig_of, d.gid, d.lflag,
-                       d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev);
+                       d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev, d.tri_o, d.tri_s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     return MDX_OK;

@@ -4,6 +4,8 @@
 #include <cstdint>
 #include <cstddef>
 #include <cstring>
+#include <array>
+#include <map>
 #if defined(__x86_64__) || defined(__i386__)
 #define MDX_HOST_X86 1
 #include <immintrin.h>
@@ -84,6 +86,60 @@ bool mdx_uniform_lj(const float* lj, size_t n, bool geometric, bool alch_on, flo
     const float s = sig;
     volatile float c = s * s;
     if (c_out) *c_out = c;
+    return true;
+}
+
+// Triads: is every atom's role list either empty or (one angle record with partners a, b; then one or two bond records, each to a or
+// to b)?  A box of flexible three-site water is.  Then an atom's bonded work is named by 8 bytes instead of an offset and two or three
+// 16-byte records, and the fused bonded + kick + drift pass (mdx_integrate.hip, the TRIAD flavour) reads those:
+//   tri[2 i]     = a | (code & 0xFF) << 24
+//   tri[2 i + 1] = b | (code >> 8)   << 24          code 0: no roles (a = b = 0)
+//   shapes[4 code ..] = { meta of the angle record, meta of the first bond record, meta of the second (0 without one),
+//                         number of bonds | (first bond's partner is b) << 8 | (second bond's partner is b) << 9 }
+// shapes[0 .. 3] = 0 is the shape of code 0.  The record list of atom i is then, field for field,
+//   {a, b, 0, shapes[4c]}, {sel0 ? b : a, 0, 0, shapes[4c + 1]}, and with two bonds {sel1 ? b : a, 0, 0, shapes[4c + 2]}.
+// off = the caller-order role offsets [n + 1], rec = the records as four words each (p[0], p[1], p[2], meta: RoleRec, mdx_internal.h),
+// shapes = room for 4 * shape_cap words (shape_cap <= 65536: the code has 16 bits), tri = room for 2 n words.  All or nothing: false
+// (and *n_shapes = 0) when one atom's list is anything else - another kind, a second angle, a bond to a third atom, a lone bond, three
+// bonds, a bond before the angle, a partner index of 2^24 or more, a non-zero unused field - or when the distinct shapes outnumber
+// shape_cap - 1.  *n_shapes: distinct shapes, the empty one not counted.
+bool mdx_triad_build(const uint32_t* off, const uint32_t* rec, size_t n, uint32_t* tri, uint32_t* shapes, uint32_t shape_cap, uint32_t* n_shapes) {
+    if (n_shapes) *n_shapes = 0;
+    if (!off || !tri || !shapes || shape_cap < 1u || (off[n] && !rec)) return false;
+    if (shape_cap > 65536u) shape_cap = 65536u;
+    const uint32_t KIND_BOND = 0u, KIND_ANGLE = 1u;      // (ROLE_BOND, ROLE_ANGLE)
+    std::map<std::array<uint32_t, 4>, uint32_t> code_of;
+    uint32_t count = 0;
+    shapes[0] = shapes[1] = shapes[2] = shapes[3] = 0u;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t b0 = off[i], len = off[i + 1] - b0;
+        if (off[i + 1] < b0) return false;
+        if (len == 0) { tri[2 * i] = tri[2 * i + 1] = 0u; continue; }
+        if (len < 2 || len > 3) return false;
+        const uint32_t* an = rec + 4 * (size_t)b0;
+        if ((an[3] & 0xFu) != KIND_ANGLE || ((an[3] >> 4) & 0xFu) > 2u || an[2] != 0u) return false;
+        const uint32_t a = an[0], b = an[1];
+        if (a >= (1u << 24) || b >= (1u << 24)) return false;
+        std::array<uint32_t, 4> sh = {an[3], 0u, 0u, len - 1u};
+        for (uint32_t k = 1; k < len; ++k) {
+            const uint32_t* bd = an + 4 * (size_t)k;
+            if ((bd[3] & 0xFu) != KIND_BOND || bd[1] != 0u || bd[2] != 0u) return false;
+            if (bd[0] != a && bd[0] != b) return false;
+            sh[k] = bd[3];
+            if (bd[0] != a) sh[3] |= 1u << (7 + k);
+        }
+        auto it = code_of.find(sh);
+        uint32_t code;
+        if (it == code_of.end()) {
+            if (count + 1u >= shape_cap) return false;
+            code = ++count;
+            code_of.emplace(sh, code);
+            for (int w = 0; w < 4; ++w) shapes[4 * (size_t)code + w] = sh[w];
+        } else code = it->second;
+        tri[2 * i] = a | ((code & 0xFFu) << 24);
+        tri[2 * i + 1] = b | ((code >> 8) << 24);
+    }
+    if (n_shapes) *n_shapes = count;
     return true;
 }
 

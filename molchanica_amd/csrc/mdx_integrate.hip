@@ -124,7 +124,10 @@ __device__ __forceinline__ void pipe_publish(const FusedArgs& a, uint32_t word) 
     for (int k = 0; k < 9; ++k) a.pc->m1_shard[k] = 0u;
 }
 // POSRE: a restrained handle (ROLE_POSRE records; they count as neither bond nor angle roles, so NODIH is off there)
-template <bool DUAL, bool PIPE, bool NODIH = false, bool POSRE = false>
+// TRIAD (with NODIH, without PIPE and POSRE): a handle whose every role list is empty or one angle plus one or two bonds to the angle's
+// partners (mdx_triad_build, mdx_hostutil.cpp - a box of flexible water).  The lane's 8-byte record names the two partners and a shape;
+// the records of its list are put together in registers and go through role_compute in the list's order: the record flavour's bits.
+template <bool DUAL, bool PIPE, bool NODIH = false, bool POSRE = false, bool TRIAD = false>
 __global__ __launch_bounds__(256) void bonded_integrate_kernel(FusedArgs a) {
     uint32_t gate = a.gate_in ? *a.gate_in : 0u;
     if (PIPE && (a.pipe_flags & 1u))       // what the ranks below this one found during the last drift came back with their ghost forces
@@ -140,6 +143,7 @@ __global__ __launch_bounds__(256) void bonded_integrate_kernel(FusedArgs a) {
         }
         return;
     }
+    static_assert(!TRIAD || (NODIH && !PIPE && !POSRE), "the triad flavour: bond and angle roles only, single-device handles");
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     float d2 = 0.f, path = 0.f;
     if (s < a.S) {
@@ -147,29 +151,50 @@ __global__ __launch_bounds__(256) void bonded_integrate_kernel(FusedArgs a) {
         // the offsets go first, the lane's own rows travel beside them, and the first FUSED_PRE records with their
         // partners are fetched as one batch each (a loop with a data-dependent trip count would take them one round trip
         // at a time) - a water atom has two or three roles
-        const uint32_t rb = a.role_off[s], re = a.role_off[s + 1];
+        // (TRIAD: two - record -> partners / shape -> parameter sets)
+        uint32_t rb = 0u, re = 0u;
+        uint2 tr = make_uint2(0u, 0u);
+        if (TRIAD) tr = a.tri[s];
+        else { rb = a.role_off[s]; re = a.role_off[s + 1]; }
         float4 p = a.posq_in[s];
         float4 v = a.vel[s];
         if (v.w != 0.f) {   // w = 418.4/m; 0 marks static, ghost and dummy slots
             float4 f = a.force[s];
-            constexpr int FUSED_PRE = 3;
-            RoleRec rr[FUSED_PRE]; float4 q0[FUSED_PRE], q1[FUSED_PRE], prm[FUSED_PRE];
+            if (TRIAD) {
+                const float4 qa = a.posq_in[tr.x & 0xFFFFFFu], qb = a.posq_in[tr.y & 0xFFFFFFu];
+                const uint4 sh = a.tri_shape[(tr.x >> 24) | ((tr.y >> 24) << 8)];      // (code 0, no roles: four zero words)
+                const float4 prm0 = a.prm[sh.x >> 8], prm1 = a.prm[sh.y >> 8], prm2 = a.prm[sh.z >> 8];
+                const uint32_t nb = sh.w & 3u;      // bonds behind the angle: 0 (no roles at all), 1 or 2
+                RoleEnergies en;
+                if (nb > 0u) {
+                    role_compute<false, NODIH, POSRE>(RoleRec{{tr.x & 0xFFFFFFu, tr.y & 0xFFFFFFu, 0u}, sh.x}, prm0, p, qa, qb, a.posq_in, a.p, f.x, f.y, f.z, en);
+                    const bool s0 = (sh.w >> 8) & 1u;
+                    role_compute<false, NODIH, POSRE>(RoleRec{{(s0 ? tr.y : tr.x) & 0xFFFFFFu, 0u, 0u}, sh.y}, prm1, p, s0 ? qb : qa, qa, a.posq_in, a.p, f.x, f.y, f.z, en);
+                }
+                if (nb > 1u) {
+                    const bool s1 = (sh.w >> 9) & 1u;
+                    role_compute<false, NODIH, POSRE>(RoleRec{{(s1 ? tr.y : tr.x) & 0xFFFFFFu, 0u, 0u}, sh.z}, prm2, p, s1 ? qb : qa, qa, a.posq_in, a.p, f.x, f.y, f.z, en);
+                }
+            } else {
+                constexpr int FUSED_PRE = 3;
+                RoleRec rr[FUSED_PRE]; float4 q0[FUSED_PRE], q1[FUSED_PRE], prm[FUSED_PRE];
 #pragma unroll
-            for (int i = 0; i < FUSED_PRE; ++i)      // (past the atom's own list: a null record - slot 0, parameter set 0 - fetched, never evaluated)
-                rr[i] = (rb + (uint32_t)i < re) ? a.roles[rb + (uint32_t)i] : RoleRec{{0u, 0u, 0u}, 0u};
+                for (int i = 0; i < FUSED_PRE; ++i)      // (past the atom's own list: a null record - slot 0, parameter set 0 - fetched, never evaluated)
+                    rr[i] = (rb + (uint32_t)i < re) ? a.roles[rb + (uint32_t)i] : RoleRec{{0u, 0u, 0u}, 0u};
 #pragma unroll
-            for (int i = 0; i < FUSED_PRE; ++i) { q0[i] = a.posq_in[rr[i].p[0]]; q1[i] = a.posq_in[rr[i].p[1]]; prm[i] = a.prm[rr[i].meta >> 8]; }
-            RoleEnergies en;
-            if (PIPE && (a.pipe_flags & 1u)) {
-                const uint32_t nr = a.send_cnt[s];
-                for (uint32_t k = 0; k < nr; ++k) { const float4 g = a.frc_in[a.send_rows[(size_t)s * 7 + k]]; f.x += g.x; f.y += g.y; f.z += g.z; }
-            }
+                for (int i = 0; i < FUSED_PRE; ++i) { q0[i] = a.posq_in[rr[i].p[0]]; q1[i] = a.posq_in[rr[i].p[1]]; prm[i] = a.prm[rr[i].meta >> 8]; }
+                RoleEnergies en;
+                if (PIPE && (a.pipe_flags & 1u)) {
+                    const uint32_t nr = a.send_cnt[s];
+                    for (uint32_t k = 0; k < nr; ++k) { const float4 g = a.frc_in[a.send_rows[(size_t)s * 7 + k]]; f.x += g.x; f.y += g.y; f.z += g.z; }
+                }
 #pragma unroll
-            for (int i = 0; i < FUSED_PRE; ++i)
-                if (rb + (uint32_t)i < re) role_compute<false, NODIH, POSRE>(rr[i], prm[i], p, q0[i], q1[i], a.posq_in, a.p, f.x, f.y, f.z, en);
-            for (uint32_t k = rb + FUSED_PRE; k < re; ++k) {
-                const RoleRec r = a.roles[k];
-                role_eval<false, NODIH, POSRE>(r, a.prm, p, a.posq_in, a.p, f.x, f.y, f.z, en);
+                for (int i = 0; i < FUSED_PRE; ++i)
+                    if (rb + (uint32_t)i < re) role_compute<false, NODIH, POSRE>(rr[i], prm[i], p, q0[i], q1[i], a.posq_in, a.p, f.x, f.y, f.z, en);
+                for (uint32_t k = rb + FUSED_PRE; k < re; ++k) {
+                    const RoleRec r = a.roles[k];
+                    role_eval<false, NODIH, POSRE>(r, a.prm, p, a.posq_in, a.p, f.x, f.y, f.z, en);
+                }
             }
             const float kdt = a.dt * v.w;
             v.x += kdt * f.x; v.y += kdt * f.y; v.z += kdt * f.z;
@@ -428,7 +453,17 @@ int mdx_launch_bonded_integrate(mdx_handle* h, float dt, const uint32_t* d_gate_
     // SIMD instead of five for a pass that lives on loads in flight.  MDX_FUSED_NODIH=0: A/B (read per launch)
     const char* nd_env = std::getenv("MDX_FUSED_NODIH");
     const bool nodih = h->n_roles_dih == 0 && !(nd_env && nd_env[0] == '0');
-    if (h->n_posre) {      // restrained handle: the generic flavour with the ROLE_POSRE branch
+    // triads (mdx_refresh_triads): every role list of the handle is empty or angle + bonds to its partners - the flavour that reads 8 bytes
+    // per slot instead of the offsets and the records (1 M water atoms: 30.0 -> 23.0 us per launch, profiles/fused_triad_ab.txt).  Slots fit 24 bits.
+    // MDX_FUSED_TRIAD=0: the record flavours, launch for launch (A/B, read per launch)
+    const char* tr_env = std::getenv("MDX_FUSED_TRIAD");
+    const bool triad = h->tri_ok && nodih && !pipe && !h->n_posre && d.tri_s && d.tri_shape && h->S < (1u << 24) && !(tr_env && tr_env[0] == '0');
+    a.tri = d.tri_s; a.tri_shape = d.tri_shape;
+    h->tri_last = triad ? 1u : 0u;
+    if (triad) {
+        if (dual) hipLaunchKernelGGL((bonded_integrate_kernel<true, false, true, false, true>), g, b, 0, h->stream, a);
+        else hipLaunchKernelGGL((bonded_integrate_kernel<false, false, true, false, true>), g, b, 0, h->stream, a);
+    } else if (h->n_posre) {      // restrained handle: the generic flavour with the ROLE_POSRE branch
         if (pipe) {
             if (dual) hipLaunchKernelGGL((bonded_integrate_kernel<true, true, false, true>), g, b, 0, h->stream, a);
             else hipLaunchKernelGGL((bonded_integrate_kernel<false, true, false, true>), g, b, 0, h->stream, a);

@@ -244,6 +244,10 @@ struct DeviceState {
     uint32_t* role_cnt_s = nullptr; uint32_t* role_off_s = nullptr;  // [S+1]
     RoleRec*  role_rec_s = nullptr;                                  // [R]
     float4*   role_prm = nullptr;                                    // distinct parameter sets of the bonded terms
+    // triads (mdx_triad_build, mdx_hostutil.cpp; handles whose every role list is empty or angle + 1-2 bonds to the angle's partners):
+    // 8 bytes per atom - caller order (null: the handle is not eligible), slot order (written by role_fill_body at every rebuild) - and
+    // the shapes the codes index
+    uint2* tri_o = nullptr; uint2* tri_s = nullptr; uint4* tri_shape = nullptr;   // [N], [S], [shapes + 1]
     // SPME (mdx_pme.hip)
     float* pme_q = nullptr; float2* pme_f = nullptr; float* pme_theta = nullptr;
     float* pme_q2 = nullptr; float2* pme_f2 = nullptr;   // alchemical window: the coupled molecule's own mesh
@@ -454,6 +458,9 @@ struct mdx_handle {
     // have a constant-sigma^2 body (pair_eval<..., UNI>, launch_variant) send it out.  mdx_pair_body_info reads the three words.
     bool uni_lj = false; float uni_c = 0.f;
     uint32_t pair_body_step = 0, pair_body_any = 0;      // the last pair launch of the step loop / of any kind ran a UNI body (bit 0; bit 1: its two-set chunk loop)
+    // triads (mdx_refresh_triads: wherever the caller-order role tables are uploaded).  mdx_fused_triad_info reads the three words.
+    bool tri_ok = false; uint32_t tri_shapes = 0;
+    uint32_t tri_last = 0;        // the last fused bonded + kick + drift launch took the triad flavour
     bool bonded_deferred = false; // step loop, large classes: the NEXT step's fused bonded + kick + drift pass evaluates the bonded terms of this force call
     uint64_t rng_state = 0;
     bool zero_com = false;
@@ -485,6 +492,7 @@ struct FusedArgs {
     const float4* posq_in; float4* posq_out; float4* vel; float4* force; float4* ref;
     float* path; const float* dprune;      // path split (DeviceState): null -> the accumulator rides in ref[].w
     const uint32_t* role_off; const RoleRec* roles; const float4* prm; BondedParams p; uint32_t R;
+    const uint2* tri; const uint4* tri_shape;      // the TRIAD flavour reads these instead of role_off / roles
     const uint32_t* gate_in; uint32_t* disp_out; uint32_t thr_bits; uint32_t* prune_out; float path_thr;
     // Decomposed handle, pipelined step (PIPE; mdx_decomp.hip).  The pass takes over what two kernels and two launch boundaries did:
     //   pipe_flags & 1  the ghost forces the peers returned for the previous force call are ADDED here (frc_in has the layout of the
@@ -637,6 +645,9 @@ static inline void mdx_tail_plan(const mdx_handle* h, uint32_t T, uint32_t* w_ou
 
 // One LJ atom type (mdx_hostutil.cpp): does every atom with a well carry the same sigma / 2, and if so, sigma_ij^2 as the device rounds it.
 bool mdx_uniform_lj(const float* lj, size_t n, bool geometric, bool alch_on, float* c_out);
+// Triads (mdx_hostutil.cpp): 8-byte records and a shape table for a handle whose role lists are all empty or angle + bonds to its partners.
+bool mdx_triad_build(const uint32_t* off, const uint32_t* rec, size_t n, uint32_t* tri, uint32_t* shapes, uint32_t shape_cap, uint32_t* n_shapes);
+constexpr uint32_t MDX_TRIAD_SHAPE_CAP = 65536u;      // codes have 16 bits; 0 is "no roles"
 // ... decided for a handle from h_lj, the combining rule and the alchemical state.  MDX_UNI_LJ=0: never (the parent's launches,
 // instantiation for instantiation; read once per process).
 static inline void mdx_refresh_uni_lj(mdx_handle* h) {

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from ._abi import (CCommDiag, CFlexOpts, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
-                   CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, POSE_RMSD_ARGTYPES,
+                   CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, FUSED_TRIAD_INFO_ARGTYPES, POSE_RMSD_ARGTYPES,
                    MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, VEL, MdConfig, MdSystem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -87,6 +87,7 @@ def load_library():
     lib.mdx_get_skin.argtypes = [H, _fp, C.POINTER(C.c_int)]
     lib.mdx_pair_launch_info.argtypes = [H, _u32p]
     lib.mdx_pair_body_info.argtypes = [H, _u32p]
+    lib.mdx_fused_triad_info.argtypes = FUSED_TRIAD_INFO_ARGTYPES
     lib.mdx_minimize_energy.argtypes = [H, C.c_uint32, _fp, C.c_float, C.POINTER(CEnergies), _u32p]
     lib.mdx_initialize_velocities.argtypes = [H, C.c_float, C.c_int, C.c_uint64]
     lib.mdx_set_thermostat.argtypes = [H, C.c_int, C.c_float, C.c_float, C.c_uint32, C.c_uint64]
@@ -800,6 +801,13 @@ class MdState:
                 # the chunk loop of that body: two register sets, one vector-memory wait per two chunks (one-wave half-list kernels)
                 "step_two_sets": bool(out[1] & 2), "any_two_sets": bool(out[2] & 2),
                 "c": float(np.array([out[3]], np.uint32).view(np.float32)[0])}
+
+    def fused_triad_info(self) -> dict:
+        """The triad flavour of the fused bonded + kick + drift pass (handles whose every role list is empty or one angle plus one or
+        two bonds to its partners; include/mdx.h: mdx_fused_triad_info)."""
+        out = (C.c_uint32 * 4)()
+        _check(load_library().mdx_fused_triad_info(self._h, out))
+        return {"eligible": bool(out[0]), "shapes": int(out[1]), "last_launch": bool(out[2])}
 
     def skin(self):
         """-> (Verlet skin in force, still tuning?)  (MdConfig.skin == 0 lets the library choose it)."""
