@@ -6,14 +6,15 @@
 // Everything here is integer / bounding-box work, HBM- or latency-bound; it runs once per ~25 steps at 300 K.
 //
 // Pipeline (all on the handle's stream):
-//   bin      atom -> (column, z-bin) cell id, wrap into the box, histogram       (1 thread/atom)
+//   bin      atom -> (column, z-bin) cell id, wrap into the box, histogram; the histogram's atomic returns the atom's
+//            arrival rank in its cell                                          (rb_prep_kernel, 1 thread/atom)
 //   scan     exclusive prefix over cells; per-column tile counts and prefix
-//   scatter  counting-sort scatter (arbitrary order inside a cell) ...
-//   cellsort ... made deterministic: each cell's handful of atoms sorted by (z, atom id)
+//   scatter  counting-sort scatter by arrival rank (arbitrary order inside a cell) ...      (rb_scatter_kernel)
+//   cellsort ... made deterministic: each cell's handful of atoms sorted by (z, atom id)    (cell_rank_kernel)
 //   assign   one wavefront per tile: 64 z-consecutive atoms of a column, bitonic sub-sort by
-//            y | x | z so that each run of 8 lanes (a cluster) is a compact brick
-//   gather   slot-space arrays (posq, lj, vel, ref) from caller-order data; dummies parked far away
-//   bbox     per-cluster bounding boxes
+//            y | x | z so that each run of 8 lanes (a cluster) is a compact brick; the slot-space arrays (posq, lj, vel,
+//            ref) from caller-order data, dummies parked far away; per-cluster bounding boxes and interaction kinds;
+//            the slots' bonded-role counts                                      (rb_assign_kernel)
 //   list     per tile: all (j-cluster, image) within r_list of the tile (bounding boxes; candidates looked up through
 //            the column's z-bins), with the per-i-cluster mask, exclusion-bearing entries first + their 64-bit
 //            per-lane interaction masks; half list: every cluster pair in ONE tile's list (parity of I + J)
@@ -42,7 +43,9 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 
-__device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_t* s_wave, uint32_t* total) {
+// exclusive scan of one value per thread over a workgroup of THREADS threads; *total: the sum, the same in every thread
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* s_wave /* [THREADS / 64] */, uint32_t* total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t inc = v;
 #pragma unroll
@@ -54,7 +57,7 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_
     __syncthreads();
     uint32_t base = 0, tot = 0;
 #pragma unroll
-    for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+    for (int w = 0; w < THREADS / 64; ++w) {
         uint32_t x = s_wave[w];
         if (w < wave) base += x;
         tot += x;
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_tile_kernel(const uint32_t*
         sum += v[k];
     }
     uint32_t total;
-    uint32_t ex = block_exclusive_scan_256(sum, s_wave, &total);
+    uint32_t ex = block_exclusive_scan<SCAN_THREADS>(sum, s_wave, &total);
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         if (base + k < n) out[base + k] = ex;
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_sums_kernel(uint32_t* __res
     for (uint32_t b0 = 0; b0 < nb; b0 += SCAN_THREADS) {
         uint32_t i = b0 + threadIdx.x;
         uint32_t v = (i < nb) ? sums[i] : 0u, total;
-        uint32_t ex = block_exclusive_scan_256(v, s_wave, &total);
+        uint32_t ex = block_exclusive_scan<SCAN_THREADS>(v, s_wave, &total);
         if (i < nb) sums[i] = carry + ex;
         carry += total;
     }
@@ -264,34 +267,11 @@ __device__ __forceinline__ float wrap1(float x, float lo, float L) {
 }
 
 __global__ void rebuild_clear_kernel(uint32_t* __restrict__ slot_of, uint32_t n_slot_of, uint32_t* __restrict__ cell_count,
-                                     uint32_t* __restrict__ cell_cursor, uint32_t n_cells1, uint32_t* __restrict__ flags) {
+                                     uint32_t n_cells1, uint32_t* __restrict__ flags) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_slot_of) slot_of[i] = MDX_INVALID;
-    if (i < n_cells1) { cell_count[i] = 0u; cell_cursor[i] = 0u; }
+    if (i < n_cells1) cell_count[i] = 0u;
     if (i < 4u) flags[i] = 0u;
-}
-
-__global__ void bin_atoms_kernel(float4* __restrict__ pos_orig, uint32_t N, GridParams g, const uint8_t* __restrict__ lflag,
-                                 uint32_t* __restrict__ cell_of, uint32_t* __restrict__ cell_count,
-                                 uint32_t* __restrict__ nonfinite) {
-    uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= N) return;
-    float4 p = pos_orig[o];
-    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) {
-        atomicOr(nonfinite, 1u);
-        p.x = g.lo[0]; p.y = g.lo[1]; p.z = g.lo[2];
-    }
-    if (g.per[0]) p.x = wrap1(p.x, g.lo[0], g.len[0]);
-    if (g.per[1]) p.y = wrap1(p.y, g.lo[1], g.len[1]);
-    if (g.per[2]) p.z = wrap1(p.z, g.lo[2], g.len[2]);
-    pos_orig[o] = p;
-    int cx = min(g.ncx - 1, max(0, mdx_col_of(g, 0, p.x)));
-    int cy = min(g.ncy - 1, max(0, mdx_col_of(g, 1, p.y)));
-    int zb = min(g.nzb - 1, max(0, (int)((p.z - g.lo[2]) * g.inv_zbin)));
-    const int pop = (g.npop > 1 && (lflag[o] & 1u)) ? 1 : 0;      // ghosts get column sets of their own
-    uint32_t cell = (uint32_t)(((pop * g.ncx + cx) * g.ncy + cy) * g.nzb + zb);
-    cell_of[o] = cell;
-    atomicAdd(&cell_count[cell], 1u);
 }
 
 __global__ void column_tiles_kernel(const uint32_t* __restrict__ cell_start, uint32_t ncol, int nzb,
@@ -308,15 +288,6 @@ __global__ void tile_col_kernel(const uint32_t* __restrict__ tile_start, uint32_
     uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ncol) return;
     for (uint32_t t = tile_start[c]; t < tile_start[c + 1]; ++t) tile_col[t] = c;
-}
-
-__global__ void scatter_kernel(const uint32_t* __restrict__ cell_of, const uint32_t* __restrict__ cell_start,
-                               uint32_t* __restrict__ cell_cursor, uint32_t* __restrict__ sorted_orig, uint32_t N) {
-    uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= N) return;
-    uint32_t c = cell_of[o];
-    uint32_t k = atomicAdd(&cell_cursor[c], 1u);
-    sorted_orig[cell_start[c] + k] = o;
 }
 
 // Order of every cell's members by (z, atom id): removes the arbitrary order the atomic scatter left, so the whole
@@ -414,105 +385,6 @@ __device__ __forceinline__ void kind_tile_order(float& x, float& y, float& z, ui
     seg = a; bitonic64_seg<1>(seg, x, y, z, o, lane); cut();
     seg = a; bitonic64_seg<0>(seg, x, y, z, o, lane); cut();
     seg = a; bitonic64_seg<2>(seg, x, y, z, o, lane);
-}
-
-__global__ __launch_bounds__(256) void assign_tiles_kernel(
-    uint32_t T, int nzb, const uint32_t* __restrict__ tile_col, const uint32_t* __restrict__ tile_start,
-    const uint32_t* __restrict__ cell_start, const uint32_t* __restrict__ sorted_orig,
-    const float4* __restrict__ pos_orig, const uint32_t* __restrict__ gid, uint32_t* __restrict__ orig_of,
-    uint32_t* __restrict__ slot_of, int kind_split, const uint8_t* __restrict__ lflag, const float* __restrict__ o_qs,
-    const float2* __restrict__ o_lj) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (t > T) return;
-    if (t == T) {  // the null tile: all dummies
-        orig_of[(size_t)t * MDX_TILE + lane] = MDX_INVALID;
-        return;
-    }
-    const uint32_t c = tile_col[t];
-    const uint32_t a0 = cell_start[(size_t)c * nzb] + (t - tile_start[c]) * MDX_TILE;
-    const uint32_t aend = cell_start[(size_t)(c + 1) * nzb];
-    const uint32_t p = a0 + lane;
-    const bool valid = p < aend;
-    uint32_t o = valid ? sorted_orig[p] : MDX_INVALID;
-    float x = FLT_MAX, y = FLT_MAX, z = FLT_MAX;
-    if (valid) { float4 q = pos_orig[o]; x = q.x; y = q.y; z = q.z; }
-    if (kind_split) {      // the same order rb_assign_kernel gives: slot assignment is a function of the positions, not of the chain that ran
-        int group = 2;
-        if (valid) {
-            const uint32_t g = gid[o];
-            group = (!(lflag[o] & 2u) && o_lj[g].y != 0.f && o_qs[g] == 0.f) ? 0 : 1;
-        }
-        kind_tile_order(x, y, z, o, group, lane);
-    } else {
-    // halves by y, quarters by x, eighths (clusters) by z
-    bitonic_group<64>(y, x, z, o, lane);
-    bitonic_group<32>(x, y, z, o, lane);
-    bitonic_group<16>(z, x, y, o, lane);
-    }
-    const uint32_t slot = t * MDX_TILE + lane;
-    orig_of[slot] = o;
-    if (o != MDX_INVALID) slot_of[gid[o]] = slot;
-}
-
-__global__ void gather_slots_kernel(uint32_t S, const uint32_t* __restrict__ orig_of,
-                                    const uint32_t* __restrict__ gid, const uint8_t* __restrict__ lflag,
-                                    const float4* __restrict__ pos_orig, const float4* __restrict__ vel_orig,
-                                    const float* __restrict__ o_qs, const float2* __restrict__ o_lj,
-                                    const float* __restrict__ o_invm, float4* __restrict__ posq,
-                                    float2* __restrict__ lj, float4* __restrict__ vel, float4* __restrict__ ref,
-                                    float4* __restrict__ force, uint8_t* __restrict__ slot_flags, float* __restrict__ path,
-                                    float* __restrict__ dprune) {
-    uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    uint32_t o = orig_of[s];
-    float4 p, v; float2 l;
-    uint8_t fl = 0;
-    if (o != MDX_INVALID) {
-        const uint32_t g = gid[o];
-        const bool ghost = (lflag[o] & 1u) != 0;
-        float4 q = pos_orig[o], w = vel_orig[o];
-        // (lflag bit 1: a ghost kept only as the bonded partner of an owned atom - its pairs belong to other ranks)
-        const bool silent = (lflag[o] & 2u) != 0;
-        p = make_float4(q.x, q.y, q.z, silent ? 0.f : o_qs[g]);
-        v = ghost ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(w.x, w.y, w.z, o_invm[g]);
-        l = silent ? make_float2(o_lj[g].x, 0.f) : o_lj[g];
-        fl = ghost ? 1 : 3;
-    } else {
-        // dummy: far away, every dummy at its own coordinate so no two coincide
-        float d = MDX_DUMMY_BASE + MDX_DUMMY_STEP * (float)(s & 0xFFFFF);
-        p = make_float4(d, d + 17.0f * (float)(s >> 20), d, 0.f);
-        v = make_float4(0.f, 0.f, 0.f, 0.f);
-        l = make_float2(0.f, 0.f);
-    }
-    posq[s] = p; vel[s] = v; lj[s] = l; ref[s] = make_float4(p.x, p.y, p.z, 0.f);   // .w: path length (dual list)
-    path[s] = 0.f; dprune[s] = 0.f;                                                  // (... or, path split, its own array)
-    force[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-    slot_flags[s] = fl;
-}
-
-__global__ void cluster_bbox_kernel(uint32_t NC, const uint32_t* __restrict__ orig_of,
-                                    const float4* __restrict__ posq, const uint8_t* __restrict__ slot_flags,
-                                    float4* __restrict__ cl_lo, float4* __restrict__ cl_hi,
-                                    const float2* __restrict__ lj, uint8_t* __restrict__ cl_kind) {
-    uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= NC) return;
-    float3 lo = make_float3(3.0e38f, 3.0e38f, 3.0e38f), hi = make_float3(-3.0e38f, -3.0e38f, -3.0e38f);
-    int n = 0, n_owned = 0;
-    uint32_t kind = 0;
-    for (int k = 0; k < MDX_CLUSTER; ++k) {
-        uint32_t s = c * MDX_CLUSTER + k;
-        if (orig_of[s] == MDX_INVALID) continue;
-        n_owned += (slot_flags[s] >> 1) & 1;
-        float4 p = posq[s];
-        kind |= (lj[s].y != 0.f ? 1u : 0u) | (p.w != 0.f ? 2u : 0u);
-        lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
-        hi.x = fmaxf(hi.x, p.x); hi.y = fmaxf(hi.y, p.y); hi.z = fmaxf(hi.z, p.z);
-        ++n;
-    }
-    cl_lo[c] = make_float4(lo.x, lo.y, lo.z, (float)n);
-    cl_hi[c] = make_float4(hi.x, hi.y, hi.z, (float)n_owned);   // .w: atoms this rank owns (half list)
-    cl_kind[c] = (uint8_t)kind;
 }
 
 __global__ void unsort_kernel(uint32_t N, const uint32_t* __restrict__ gid, const uint32_t* __restrict__ slot_of,
@@ -1471,7 +1343,6 @@ static int setup_grid(mdx_handle* h) {
         ALLOC(d.cell_count, (size_t)new_ncells + 1);
         h->cell_count_clean = false;
         ALLOC(d.cell_start, (size_t)new_ncells + 1);
-        ALLOC(d.cell_cursor, (size_t)new_ncells + 1);
     }
     if (new_ncol > h->ncol || !d.col_tiles) {
         ALLOC(d.col_tiles, (size_t)new_ncol + 1);
@@ -1533,12 +1404,14 @@ __global__ void readback_kernel(RbSrc s, volatile uint32_t* out, uint32_t seq) {
     __threadfence_system();
     out[31] = seq;      // the host spins on this word (a stream synchronisation costs ~5 us more: tools/ubench/sync_latency.hip)
 }
-static int readback(mdx_handle* h, const RbSrc& s) {
+static int alloc_readback(mdx_handle* h) {
     if (!h->h_rb) { HIP_TRY(hipHostMalloc((void**)&h->h_rb, sizeof(uint32_t) * 32, hipHostMallocDefault)); h->h_rb[31] = 0u; }
+    return MDX_OK;
+}
+// the host's wait for word 31 of the read-back block to show `seq` (MDX_CHUNK_SPIN=0: an ordinary stream synchronisation)
+static int spin_on_readback(mdx_handle* h, uint32_t seq) {
     static const bool spin_ok = [] { const char* e = std::getenv("MDX_CHUNK_SPIN"); return !(e && e[0] == '0'); }();
-    const uint32_t seq = ++h->rb_seq;
-    hipLaunchKernelGGL(readback_kernel, dim3(1), dim3(1), 0, h->stream, s, (volatile uint32_t*)h->h_rb, seq);
-    if (!spin_ok || h->profile) { HIP_TRY(hipStreamSynchronize(h->stream)); return MDX_OK; }
+    if (!spin_ok) { HIP_TRY(hipStreamSynchronize(h->stream)); return MDX_OK; }
     volatile uint32_t* seq_word = (volatile uint32_t*)h->h_rb + 31;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 0; *seq_word != seq; ++spins) {
@@ -1549,6 +1422,13 @@ static int readback(mdx_handle* h, const RbSrc& s) {
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     return MDX_OK;
+}
+static int readback(mdx_handle* h, const RbSrc& s) {
+    MDX_TRY(alloc_readback(h));
+    const uint32_t seq = ++h->rb_seq;
+    hipLaunchKernelGGL(readback_kernel, dim3(1), dim3(1), 0, h->stream, s, (volatile uint32_t*)h->h_rb, seq);
+    if (h->profile) { HIP_TRY(hipStreamSynchronize(h->stream)); return MDX_OK; }
+    return spin_on_readback(h, seq);
 }
 
 // totals of the single-pass build's region cursors (statistics): entries, masked chunks
@@ -1570,26 +1450,33 @@ __global__ void pair_sum_kernel(unsigned long long* __restrict__ pc) {      // o
 static float c_inner_skin(const mdx_config& c) { return c.inner_skin == 0.f ? 0.5f : c.inner_skin; }
 
 // ================================================================================================
-// Fused list rebuild (round 4).  The chain above is ~28 launches with three host synchronisation points (the tile count,
-// the list totals, the interior-tile count of a decomposed handle); at 1 M atoms its small kernels are a third of the
-// rebuild, and for one rank of an 8-GPU run - 200 k atoms - launch latency and host round trips are most of it (0.49 ms of
-// which the two list kernels are 0.1).  Here the tile count never leaves the device until the end:
-//   prep      (atom)   slot space -> caller order (positions, velocities), wrap, cell id, histogram - the atomicAdd's return
-//                      value is the atom's arrival rank in its cell, so the scatter below needs no cursor
+// The two chains of a rebuild.  Every stage exists once; the chains differ in how they are strung together.
+// The UNFUSED chain (rebuild_unfused) launches each stage by itself and lets the host read the tile count in front of the tile
+// assignment and the list totals behind the list: ~22 launches, two or three host waits (a third for the interior-tile count of
+// a decomposed handle).  It sizes every array itself.  At 1 M atoms its small kernels are a third of the rebuild, and for one rank
+// of an 8-GPU run - 200 k atoms - launch latency and host round trips are most of it (0.49 ms of which the two list kernels are
+// 0.1).  In the FUSED chain (rebuild_fast, round 4) the tile count never leaves the device until the end:
+//   prep      (atom)   [fused: slot space -> caller order (positions, velocities);] wrap, cell id, histogram - the atomicAdd's
+//                      return value is the atom's arrival rank in its cell, so the scatter below needs no cursor.  Both chains;
+//                      the word that reports a non-finite position is the caller's (rb_ctl[RB_NONFINITE] / flags_dev[1])
 //   gridscan  (1 workgroup) exclusive scan of the cell histogram (which it leaves zeroed for the next rebuild), tiles per
 //                      column, their scan, tile -> column, T; clears the list cursors, the statistics and the error bits
-//   scatter, rank (atom)   cell members in arrival order, then in (z, atom id) order: deterministic
-//   assign    (wave = tile, launched for an upper bound of tiles) the 64 atoms of a tile, bitonic sub-sort, slot-space arrays,
-//                      cluster bounding boxes and the slots' bonded-role counts - assign + gather + bbox + role count in one
-//   role scan (1 or 3 launches, length read on the device)
-//   list      build_list_kernel<LB_SINGLE> as before, role fill in its extra workgroups; T read on the device
-//   prune     as before; on a half-shell decomposed handle it also says which tiles are interior
-//   finish    (1 workgroup) tiles by list length (inside the pair kernel's XCD ranges, or interior first), totals, and the
-//                      one read-back into pinned host memory the host spins on
-// = 9-11 launches, one host wait.  Anything unusual (first build, vacuum systems, overflow of the list arrays, more than a
-// million cells, MDX_REBUILD_FUSED=0) takes the chain above.
+//                      [unfused: rebuild_clear_kernel in front, then scan, column_tiles_kernel, scan, tile_col_kernel]
+//   scatter, rank (atom)   cell members in arrival order, then in (z, atom id) order: deterministic.  Both chains
+//   assign    (wave = tile) the 64 atoms of a tile, bitonic sub-sort, slot-space arrays, cluster bounding boxes and kinds, the
+//                      slots' bonded-role counts.  Both chains: the fused one launches it for an upper bound of tiles and the
+//                      kernel reads T on the device (AssignArgs::T_dev), the unfused one passes T
+//   role scan (1 or 3 launches; fused: length read on the device)          roles_to_slots
+//   list      build_list_kernel<LB_SINGLE>, role fill in its extra workgroups [unfused: or count + scan + fill, role_fill_kernel]
+//   prune     launch_exact_prune; in the fused chain, on a half-shell decomposed handle, it also says which tiles are interior
+//   finish    (1 workgroup) tiles by list length (inside the pair kernel's XCD ranges, or interior first: lpt_counting_sort),
+//                      totals, and the one read-back into pinned host memory the host spins on
+//                      [unfused: cursor_sum / pair_sum + readback; the tile orders by mdx_rebuild's tail, lpt_order_kernel]
+// = 9-11 launches, one host wait.  Anything unusual (first build, vacuum systems, overflow of the list arrays, more than 2^21
+// cells, MDX_REBUILD_FUSED=0, MDX_LIST_TWO_PASS=1) takes the unfused chain.  Slot order and list are a function of the positions,
+// not of the chain that ran (tests/test_gpu_rebuild_chains.py).
 // ================================================================================================
-constexpr uint32_t LPT_BUCKETS = 129;      // tiles by list length: a counting sort over the chunk count (lpt_order_kernel below)
+constexpr uint32_t LPT_BUCKETS = 129;      // tiles by list length: a counting sort over the chunk count (lpt_counting_sort below)
 enum { RB_T = 0, RB_T_OWN = 1, RB_NONFINITE = 2, RB_N_INT = 3, RB_SCAN_N = 4, RB_WORDS = 8 };
 
 template <bool UNSORT>
@@ -1598,14 +1485,14 @@ __global__ __launch_bounds__(256) void rb_prep_kernel(uint32_t N, GridParams g, 
                                                       float4* __restrict__ pos_orig, float4* __restrict__ vel_orig,
                                                       const uint8_t* __restrict__ lflag, uint32_t* __restrict__ cell_of,
                                                       uint32_t* __restrict__ cell_k, uint32_t* __restrict__ cell_count,
-                                                      uint32_t* __restrict__ rb_ctl) {
+                                                      uint32_t* __restrict__ nonfinite) {
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= N) return;
     float4 p;
     if (UNSORT) { const uint32_t sl = slot_of[gid[o]]; p = posq[sl]; vel_orig[o] = vel[sl]; }
     else p = pos_orig[o];
-    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) {
-        rb_ctl[RB_NONFINITE] = 1u;
+    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) {      // parked in cell 0; the host returns the error behind the chain
+        *nonfinite = 1u;
         p.x = g.lo[0]; p.y = g.lo[1]; p.z = g.lo[2];
     }
     if (g.per[0]) p.x = wrap1(p.x, g.lo[0], g.len[0]);
@@ -1627,20 +1514,6 @@ struct GridScanArgs {
     uint32_t* rb_ctl; uint32_t* flags; unsigned long long* pair_count; uint32_t* list_cursors;
     ScanChain chain;
 };
-__device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(inc, d); if (lane >= d) inc += t; }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN1_THREADS / 64; ++w) { const uint32_t x = s_wave[w]; if (w < wave) base += x; tot += x; }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
 __global__ __launch_bounds__(SCAN1_THREADS) void rb_gridscan_kernel(GridScanArgs a) {
     __shared__ uint32_t s_wave[SCAN1_THREADS / 64];
     __shared__ uint32_t s_bcast;
@@ -1671,7 +1544,7 @@ __global__ __launch_bounds__(SCAN1_THREADS) void rb_gridscan_kernel(GridScanArgs
         uint32_t nt = 0, tot;
         if (c < a.ncol)
             nt = (a.cell_start[(size_t)(c + 1) * a.nzb] - a.cell_start[(size_t)c * a.nzb] + MDX_TILE - 1) / MDX_TILE;
-        const uint32_t ex = block_exclusive_scan_1024(nt, s_wave, &tot);
+        const uint32_t ex = block_exclusive_scan<SCAN1_THREADS>(nt, s_wave, &tot);
         if (c < a.ncol) {
             a.tile_start[c] = run + ex;
             for (uint32_t t = 0; t < nt; ++t) a.tile_col[run + ex + t] = c;
@@ -1698,7 +1571,8 @@ __global__ __launch_bounds__(256) void rb_scatter_kernel(uint32_t N, const uint3
 }
 
 struct AssignArgs {
-    const uint32_t* rb_ctl; int nzb;
+    uint32_t T; const uint32_t* T_dev;      // as ListArgs: the tile count, or (fused chain) an upper bound and the word that holds the count
+    int nzb;
     const uint32_t* tile_col; const uint32_t* tile_start; const uint32_t* cell_start; const uint32_t* sorted_orig;
     const float4* pos_orig; const float4* vel_orig; const uint32_t* gid; const uint8_t* lflag;
     const float* o_qs; const float2* o_lj; const float* o_invm;
@@ -1711,7 +1585,7 @@ struct AssignArgs {
 };
 __global__ __launch_bounds__(256) void rb_assign_kernel(AssignArgs a) {
     const int lane = threadIdx.x & 63;
-    const uint32_t T = __builtin_amdgcn_readfirstlane(a.rb_ctl[RB_T]);
+    const uint32_t T = a.T_dev ? __builtin_amdgcn_readfirstlane(*a.T_dev) : a.T;
     const uint32_t t = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (t > T) return;
     uint32_t o = MDX_INVALID;
@@ -1786,6 +1660,51 @@ __global__ __launch_bounds__(256) void rb_assign_kernel(AssignArgs a) {
     }
 }
 
+// ---- tiles by decreasing list length ------------------------------------------------------------------------------------
+// A launch of a few thousand tiles is 2-3 rounds of waves per SIMD; in spatial order the long lists (owned bricks, box
+// interior) and the short ones (halo shells, faces of a non-periodic system) come in runs, and the launch ends when the
+// last long list does.  Longest first is the classic list-scheduling order: the short lists fill the tail.  A counting
+// sort over the chunk count (129 buckets) inside up to eight major groups, by one workgroup of 1024 threads with its histogram and
+// cursors in LDS (atomics on a hundred global words would queue: a returning atomic on one address is served every ~35 ns,
+// tools/ubench/grid_barrier.hip - 70 us for the fullest bucket of a 9 k-tile launch).  The major group of a tile:
+//   group_tiles > 0 (large single-device systems): which of the eight contiguous tile ranges the pair kernel hands to the eight XCDs
+//                   (group_tiles tiles each) - a range stays on its XCD's L2 and still runs longest list first;
+//   is_int          (the interior / boundary split of a decomposed handle): interior tiles first, each part by length;
+//   neither         one group.
+// Returns the number of tiles in major group 0 (with is_int: the interior tiles), the same in every thread.
+struct LptSortLds { uint32_t hist[8 * LPT_BUCKETS], cur[8 * LPT_BUCKETS], scan[SCAN1_THREADS / 64]; };
+// the pair kernel's XCD ranges: ceil(workgroups / 8) workgroups of TPB tiles each (mdx_nonbonded.hip)
+__host__ __device__ inline uint32_t mdx_lpt_group_tiles(uint32_t T, uint32_t wpt) {
+    const uint32_t tpb = (wpt > (uint32_t)MDX_NB_WAVES ? wpt : (uint32_t)MDX_NB_WAVES) / wpt;
+    return (((T + tpb - 1u) / tpb + 7u) >> 3) * tpb;
+}
+__device__ __forceinline__ uint32_t lpt_counting_sort(uint32_t T, const ListCounts* __restrict__ counts, uint32_t group_tiles,
+                                                      const uint32_t* __restrict__ is_int, uint32_t* __restrict__ order, LptSortLds& s) {
+    constexpr uint32_t NB = 8 * LPT_BUCKETS;
+    for (uint32_t b = threadIdx.x; b < NB; b += SCAN1_THREADS) s.hist[b] = 0;
+    __syncthreads();
+    auto bucket = [&](uint32_t t) {
+        const uint32_t nch = (counts[t].n_masked + counts[t].n_plain) >> 3;
+        const uint32_t major = group_tiles ? min(t / group_tiles, 7u) : ((is_int && !is_int[t]) ? 1u : 0u);
+        return major * LPT_BUCKETS + LPT_BUCKETS - 1u - min(nch, LPT_BUCKETS - 1u);   // bucket 0 = the longest lists
+    };
+    for (uint32_t t = threadIdx.x; t < T; t += SCAN1_THREADS) atomicAdd(&s.hist[bucket(t)], 1u);
+    __syncthreads();
+    {   // exclusive prefix over the NB = 1032 buckets, two per thread (one thread walking them took ~20 us of LDS round trips)
+        const uint32_t b0 = 2u * threadIdx.x, h0 = b0 < NB ? s.hist[b0] : 0u, h1 = b0 + 1u < NB ? s.hist[b0 + 1u] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_exclusive_scan<SCAN1_THREADS>(h0 + h1, s.scan, &tot);
+        if (b0 < NB) s.cur[b0] = ex;
+        if (b0 + 1u < NB) s.cur[b0 + 1u] = ex + h0;
+    }
+    __syncthreads();
+    const uint32_t n_major0 = s.cur[LPT_BUCKETS];      // everything in front of major 1
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < T; t += SCAN1_THREADS) order[atomicAdd(&s.cur[bucket(t)], 1u)] = t;
+    __syncthreads();
+    return n_major0;
+}
+
 struct FinishArgs {
     uint32_t* rb_ctl; const ListCounts* counts;
     uint32_t* tile_lpt; uint32_t lpt_grouped; WptRule rule;      // tile_lpt: tiles by list length (grouped: inside each XCD range of the pair kernel)
@@ -1793,41 +1712,18 @@ struct FinishArgs {
     const unsigned long long* cursors; unsigned long long* pair_count; const uint32_t* flags;
     volatile uint32_t* host; uint32_t seq;
 };
-__global__ __launch_bounds__(1024) void rb_finish_kernel(FinishArgs a) {
-    constexpr uint32_t NB = 8 * LPT_BUCKETS;
-    __shared__ uint32_t s_hist[NB], s_cur[NB], s_scan[16];
+__global__ __launch_bounds__(SCAN1_THREADS) void rb_finish_kernel(FinishArgs a) {
+    __shared__ LptSortLds s_sort;
     __shared__ uint32_t s_nint;
     const uint32_t T = a.rb_ctl[RB_T];
     if (threadIdx.x == 0) s_nint = 0u;
-    for (int pass = 0; pass < 2; ++pass) {
-        uint32_t* const order = pass == 0 ? a.tile_lpt : a.tile_order;
-        if (!order) continue;           // (uniform)
-        uint32_t group_tiles = 0;
-        if (pass == 0 && a.lpt_grouped) {      // the pair kernel's XCD ranges: ceil(workgroups / 8) workgroups of TPB tiles each (mdx_nonbonded.hip)
-            const uint32_t wpt = (uint32_t)mdx_wpt_rule(a.rule, T), tpb = max(wpt, (uint32_t)MDX_NB_WAVES) / wpt;
-            group_tiles = (((T + tpb - 1u) / tpb + 7u) >> 3) * tpb;
-        }
-        for (uint32_t b = threadIdx.x; b < NB; b += blockDim.x) s_hist[b] = 0;
-        __syncthreads();
-        auto bucket = [&](uint32_t t) {
-            const uint32_t nch = (a.counts[t].n_masked + a.counts[t].n_plain) >> 3;
-            const uint32_t major = pass == 0 ? (group_tiles ? min(t / group_tiles, 7u) : 0u) : (a.tile_int[t] ? 0u : 1u);
-            return major * LPT_BUCKETS + LPT_BUCKETS - 1u - min(nch, LPT_BUCKETS - 1u);   // bucket 0 = the longest lists
-        };
-        for (uint32_t t = threadIdx.x; t < T; t += blockDim.x) atomicAdd(&s_hist[bucket(t)], 1u);
-        __syncthreads();
-        {   // exclusive prefix over the NB = 1032 buckets, two per thread (one thread walking them took ~20 us of LDS round trips)
-            const uint32_t b0 = 2u * threadIdx.x, h0 = b0 < NB ? s_hist[b0] : 0u, h1 = b0 + 1u < NB ? s_hist[b0 + 1u] : 0u;
-            uint32_t tot;
-            const uint32_t ex = block_exclusive_scan_1024(h0 + h1, s_scan, &tot);
-            if (b0 < NB) s_cur[b0] = ex;
-            if (b0 + 1u < NB) s_cur[b0 + 1u] = ex + h0;
-            __syncthreads();
-            if (pass == 1 && threadIdx.x == 0) s_nint = s_cur[LPT_BUCKETS];      // interior tiles = everything in front of major 1
-        }
-        __syncthreads();
-        for (uint32_t t = threadIdx.x; t < T; t += blockDim.x) order[atomicAdd(&s_cur[bucket(t)], 1u)] = t;
-        __syncthreads();
+    if (a.tile_lpt) {      // (uniform)
+        const uint32_t group_tiles = a.lpt_grouped ? mdx_lpt_group_tiles(T, (uint32_t)mdx_wpt_rule(a.rule, T)) : 0u;
+        (void)lpt_counting_sort(T, a.counts, group_tiles, nullptr, a.tile_lpt, s_sort);
+    }
+    if (a.tile_order) {
+        const uint32_t n_int = lpt_counting_sort(T, a.counts, 0u, a.tile_int, a.tile_order, s_sort);
+        if (threadIdx.x == 0) s_nint = n_int;
     }
     if (threadIdx.x < 64) {      // one wave: totals of the region cursors and of the spread statistics, then the read-back
         const unsigned long long c = a.cursors[(size_t)threadIdx.x * 16];
@@ -1850,22 +1746,41 @@ __global__ __launch_bounds__(1024) void rb_finish_kernel(FinishArgs a) {
 }
 
 
-static int spin_on_readback(mdx_handle* h, uint32_t seq) {
-    static const bool spin_ok = [] { const char* e = std::getenv("MDX_CHUNK_SPIN"); return !(e && e[0] == '0'); }();
-    if (!spin_ok) { HIP_TRY(hipStreamSynchronize(h->stream)); return MDX_OK; }
-    volatile uint32_t* seq_word = (volatile uint32_t*)h->h_rb + 31;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 0; *seq_word != seq; ++spins) {
-        if ((spins & 0xFFFu) == 0xFFFu && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) {
-            HIP_TRY(hipStreamSynchronize(h->stream));       // (an error on the stream, or a very long queue: wait the ordinary way)
-            break;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return MDX_OK;
+// ================================================================================================
+// host side of the rebuild: what both chains share, the two chains, mdx_rebuild
+// ================================================================================================
+// The rebuild's environment knobs (A/B and debugging), each read once per process.
+struct RebuildKnobs {
+    bool fused;            // MDX_REBUILD_FUSED=0: every rebuild takes the unfused chain
+    bool two_pass;         // MDX_LIST_TWO_PASS=1: count + scan + fill instead of the single-pass list build (which only the unfused chain can do)
+    bool exact_prune;      // MDX_EXACT_PRUNE=0: the list keeps every bounding-box pair
+    int inner_mode;        // MDX_REBUILD_INNER: the inner list out of the fused chain's pruning pass - 0 never, 1 flexible systems, 2 always
+    uint32_t mw_below;     // MDX_PRUNE_MW_BELOW: the fused chain prunes with eight waves per tile below this many tiles
+    bool list_debug;       // MDX_LIST_DEBUG: say on stderr why a single-pass build fell back
+};
+// One wave per tile is a launch as long as its longest list: one rank of 8 of the 1 M-atom box - 3.3 k tiles, the owned ones with
+// ~150 chunks - took 233 us where the whole box, five times the work, takes 256.  Eight waves per tile below these tile counts: the
+// fused chain's was measured on decomposed handles, the unfused chain keeps the value it was first given (a few hundred tiles: one
+// wave per tile is a 1/3-empty chip waiting for its longest list).
+constexpr uint32_t PRUNE_MW_BELOW_FUSED = 12000u, PRUNE_MW_BELOW_UNFUSED = 2048u;
+static const RebuildKnobs& rebuild_knobs() {
+    static const RebuildKnobs k = [] {
+        auto env = [](const char* name) { const char* e = std::getenv(name); return e ? e : ""; };
+        RebuildKnobs r;
+        r.fused = env("MDX_REBUILD_FUSED")[0] != '0';
+        r.two_pass = env("MDX_LIST_TWO_PASS")[0] == '1';
+        r.exact_prune = env("MDX_EXACT_PRUNE")[0] != '0';
+        const char in = env("MDX_REBUILD_INNER")[0];
+        r.inner_mode = in == '0' ? 0 : (in == '2' ? 2 : 1);
+        const char* const mw = std::getenv("MDX_PRUNE_MW_BELOW");
+        r.mw_below = mw ? (uint32_t)std::atoi(mw) : PRUNE_MW_BELOW_FUSED;
+        r.list_debug = std::getenv("MDX_LIST_DEBUG") != nullptr;
+        return r;
+    }();
+    return k;
 }
 
-struct RebuildResult { uint32_t T = 0, E = 0, MC = 0, n_interior = 0; unsigned long long npairs = 0; bool ordered = false, classified = false, inner_built = false; };
+struct RebuildResult { uint32_t E = 0, MC = 0; unsigned long long npairs = 0; bool ordered = false, classified = false, inner_built = false; };
 
 // which tile orders the rebuild produces (shared by both chains)
 struct TileOrderPlan { bool lpt, grouped, split; };
@@ -1884,6 +1799,125 @@ static TileOrderPlan tile_order_plan(const mdx_handle* h, uint32_t T) {
     return p;
 }
 
+static bool list_is_pruned(const mdx_handle* h) { return !std::isinf(h->r_list) && mdx_nb_variant(h) >= 2; }   // (the whole-tile kernel ignores imask)
+
+// Dual pair list: the step loop of a half-list run walks a rolling-pruned inner list.  What moves an atom inside the step loop feeds
+// its path accumulator: the drift pass, SHAKE, and - for the ghosts of a decomposed handle - the halo unpack; a virtual site inside
+// the triangle of its parents never moves further than they do (anything else keeps the plain list).
+static float next_inner_skin(const mdx_handle* h) { return h->inner_skin_auto > 0.f ? h->inner_skin_auto : c_inner_skin(h->cfg); }
+static bool dual_list_wanted(const mdx_handle* h, float inner_skin) {
+    return !h->dual_auto_off && mdx_nb_half(h) && list_is_pruned(h) && inner_skin > 0.f && inner_skin < h->cfg.skin &&
+           (h->n_vsites == 0 || h->vsites_convex);
+}
+
+// List-build error bits (flags_dev[0]) as error returns.  16 and 32 - a tile beyond the single pass's LDS buffers, a list beyond its
+// arrays - are no errors: the caller builds again by count + fill, with bit 1 alone checked in front of that and the rest behind it.
+static int list_flags_error(uint32_t f) {
+    if (f & 1u) { mdx_set_error("exclusion table overflow while building the pair list"); return MDX_EPARAM; }
+    if (f & 8u) { mdx_set_error("a constrained / virtual-site atom is missing from the local atom set"); return MDX_EPARAM; }
+    if (f & 2u) { mdx_set_error("exclusion table overflow while building the pair list"); return MDX_EPARAM; }
+    if (f & 4u) { mdx_set_error("a bonded partner of an owned atom is missing from the local atom set (halo too thin)"); return MDX_EPARAM; }
+    return MDX_OK;
+}
+
+// Tiles, slot-space arrays, cluster boxes and kinds, role counts: rb_assign_kernel for tiles [0, T] (tile T: the null tile).  T_dev
+// (fused chain): T is an upper bound of the tile count, which is still on the device.
+static void launch_assign(mdx_handle* h, uint32_t T, const uint32_t* T_dev) {
+    DeviceState& d = h->d;
+    AssignArgs aa{};
+    aa.T = T; aa.T_dev = T_dev; aa.nzb = h->grid.nzb; aa.tile_col = d.tile_col; aa.tile_start = d.tile_start; aa.cell_start = d.cell_start;
+    aa.sorted_orig = d.sorted_orig; aa.pos_orig = d.pos_orig; aa.vel_orig = d.vel_orig; aa.gid = d.gid; aa.lflag = d.lflag;
+    aa.o_qs = d.o_qs; aa.o_lj = d.o_lj; aa.o_invm = d.o_invm; aa.orig_of = d.orig_of; aa.slot_of = d.slot_of;
+    aa.cl_kind = d.cl_kind; aa.kind_split = h->kind_split ? 1 : 0;
+    aa.posq = d.posq; aa.lj = d.lj; aa.vel = d.vel; aa.ref = d.ref; aa.force = d.force; aa.slot_flags = d.slot_flags; aa.path = d.path; aa.dprune = d.dprune;
+    aa.cl_lo = d.cl_lo; aa.cl_hi = d.cl_hi;
+    aa.role_off_o = h->n_roles ? d.role_off_o : nullptr; aa.role_cnt_s = h->n_roles ? d.role_cnt_s : nullptr;
+    hipLaunchKernelGGL(rb_assign_kernel, dim3(div_up(T + 1, 4)), dim3(256), 0, h->stream, aa);
+    h->in_slot_space = true;
+}
+
+// Bonded role lists into slot space: count per slot, scan, fill with the partners re-indexed.  count = false: rb_assign_kernel has
+// written the counts; fill = false: the single-pass list build does it in workgroups of its own (launch_single_pass).  n_dev
+// (fused chain): S is an upper bound, the scan's length S + 1 is on the device.
+static int roles_to_slots(mdx_handle* h, uint32_t S, bool count, bool fill, const uint32_t* n_dev) {
+    DeviceState& d = h->d;
+    if (count) hipLaunchKernelGGL(role_count_kernel, dim3(div_up(S + 1, 256)), dim3(256), 0, h->stream, S, d.orig_of, d.gid,
+                                  d.lflag, d.role_off_o, d.role_cnt_s);
+    MDX_TRY(scan_u32_dev_n(h, d.role_cnt_s, d.role_off_s, S + 1, d.scan_tmp, n_dev));
+    if (fill) hipLaunchKernelGGL(role_fill_kernel, dim3(div_up(S, 256)), dim3(256), 0, h->stream, S, d.orig_of, d.gid, d.lflag,
+                                 d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev, d.tri_o, d.tri_s);
+    return MDX_OK;
+}
+
+// What every list build reads and writes.  T_dev (fused chain): T is an upper bound, the count is read on the device.
+static ListArgs list_args(const mdx_handle* h, uint32_t T, const uint32_t* T_dev) {
+    const DeviceState& d = h->d;
+    ListArgs a{};
+    a.T = T; a.T_dev = T_dev; a.g = h->grid;
+    a.r_build = std::isinf(h->r_list) ? h->r_list : h->r_list * (1.0f + 1e-5f) + 1e-4f;
+    a.tile_col = d.tile_col; a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
+    a.orig_of = d.orig_of; a.slot_of = d.slot_of; a.gid = d.gid; a.slot_flags = d.slot_flags;
+    a.excl_off = d.excl_off; a.excl_idx = d.excl_idx;
+    a.counts = d.list_counts; a.entry_cnt = d.entry_cnt; a.mchunk_cnt = d.mchunk_cnt;
+    a.entry_off = d.entry_off; a.mchunk_off = d.mchunk_off; a.entries = d.entries; a.masks = d.masks;
+    a.err = d.flags_dev; a.null_cluster = T * MDX_CL_PER_TILE;
+    a.mask_layout = mdx_nb_variant(h) >= 2 ? 2 : 1;
+    a.half = mdx_nb_half(h) ? 1 : 0;
+    a.cell_start = d.cell_start; a.posq = d.posq; a.pair_count = d.pair_count;
+    return a;
+}
+
+// the single pass cuts the entry and mask arrays into regions of at least 64 tiles each (ListArgs)
+static void size_list_regions(const mdx_handle* h, ListArgs* a) {
+    a->cursors = reinterpret_cast<unsigned long long*>(h->d.list_cursors);
+    a->n_regions = 1;
+    while (a->n_regions < (uint32_t)LB_REGIONS && a->n_regions * 128u <= a->T) a->n_regions <<= 1;
+    a->region_cap_e = (uint32_t)(std::min<uint64_t>(h->cap_entries, 0xFFFFFFFFull) / a->n_regions) & ~7u;
+    a->region_cap_m = h->cap_mchunks / a->n_regions;
+}
+
+// The single-pass list build over the arrays of the previous build (cursors and statistics cleared by the caller's chain), with -
+// where the handle has bonded roles - the workgroups that fill the slot-order role lists (role_off_s scanned: roles_to_slots).
+static void launch_single_pass(mdx_handle* h, ListArgs* a) {
+    DeviceState& d = h->d;
+    size_list_regions(h, a);
+    a->list_grid = (div_up(a->T, LB_WAVES) + 7u) & ~7u;
+    uint32_t rf_blocks = 0;
+    if (h->n_roles) {
+        a->rf_S = (a->T + 1) * MDX_TILE; a->rf_role_off_o = d.role_off_o; a->rf_rec_o = d.role_rec_o; a->rf_role_off_s = d.role_off_s;
+        a->rf_rec_s = d.role_rec_s; a->rf_lflag = d.lflag; a->rf_tri_o = d.tri_o; a->rf_tri_s = d.tri_s;
+        rf_blocks = div_up(a->rf_S, LB_WAVES * 64);
+    }
+    if (h->grid.npop > 1) hipLaunchKernelGGL((build_list_kernel<LB_SINGLE, LB_PLAIN_DD>), dim3(a->list_grid + rf_blocks), dim3(LB_WAVES * 64), 0, h->stream, *a);
+    else hipLaunchKernelGGL(build_list_kernel<LB_SINGLE>, dim3(a->list_grid + rf_blocks), dim3(LB_WAVES * 64), 0, h->stream, *a);
+}
+
+// The exact pruning pass over the list `a` built: cluster pairs without an atom pair inside the list radius lose their mask bit, and -
+// clusters by kind - those without a common interaction kind leave the list.  Eight waves per tile below mw_below tiles, else one.
+// rb_ctl, tint (fused chain; may be null): the tile count on the device, and the interior-tile flags the pass also writes.
+// inner (fused chain; may be null): the one-wave pass also writes the inner list of the dual pair list.  -> whether it did.
+static bool launch_exact_prune(mdx_handle* h, const ListArgs& a, uint32_t mw_below, const uint32_t* rb_ctl, uint32_t* tint, const PruneInner* inner) {
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    if (!a.T) return false;
+    const float r2 = a.r_build * a.r_build;
+    const float shx = h->per[0] ? h->box_hi[0] - h->box_lo[0] : 0.f, shy = h->per[1] ? h->box_hi[1] - h->box_lo[1] : 0.f,
+                shz = h->per[2] ? h->box_hi[2] - h->box_lo[2] : 0.f;
+    const uint8_t* const kinds = h->kind_split ? d.cl_kind : nullptr;
+    const dim3 one_wave_grid((div_up(a.T, 4) + 7u) & ~7u);
+    if (a.T < mw_below)
+        hipLaunchKernelGGL(prune_list_mw_kernel<8>, dim3(a.T), dim3(512), 0, st, a.T, r2, shx, shy, shz, d.posq, d.list_counts,
+                           d.entry_off, d.entries, a.null_cluster, d.pair_count, rb_ctl, tint, kinds);
+    else if (inner)
+        hipLaunchKernelGGL(prune_list_kernel<true>, one_wave_grid, dim3(256), 0, st, a.T, r2, shx, shy, shz,
+                           d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, rb_ctl, tint, kinds, *inner);
+    else
+        hipLaunchKernelGGL(prune_list_kernel<false>, one_wave_grid, dim3(256), 0, st, a.T, r2, shx, shy, shz,
+                           d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, rb_ctl, tint, kinds, PruneInner{});
+    return inner && a.T >= mw_below;
+}
+
+// The fused chain (comment above rb_prep_kernel).
 // *fell_back = true: nothing was decided here (the list outgrew its arrays, or a tile its LDS buffers): the caller runs the
 // unfused chain, which sizes the arrays afresh.  The slot-space state is complete either way.
 static int rebuild_fast(mdx_handle* h, RebuildResult* res, bool* fell_back) {
@@ -1891,20 +1925,20 @@ static int rebuild_fast(mdx_handle* h, RebuildResult* res, bool* fell_back) {
     hipStream_t st = h->stream;
     const uint32_t N = h->n_local;
     const GridParams g = h->grid;
+    const RebuildKnobs& knobs = rebuild_knobs();
     *fell_back = false;
     if (!d.rb_ctl) { ALLOC(d.rb_ctl, RB_WORDS); HIP_TRY(hipMemsetAsync(d.rb_ctl, 0, sizeof(uint32_t) * RB_WORDS, st)); }
     if (!d.pair_count) ALLOC(d.pair_count, PC_TOTAL + 2);
     if (!d.list_cursors) ALLOC(d.list_cursors, LB_REGIONS * 32 + 2);
-    if (!h->h_rb) { HIP_TRY(hipHostMalloc((void**)&h->h_rb, sizeof(uint32_t) * 32, hipHostMallocDefault)); h->h_rb[31] = 0u; }
+    MDX_TRY(alloc_readback(h));
     if (!h->cell_count_clean) { HIP_TRY(hipMemsetAsync(d.cell_count, 0, sizeof(uint32_t) * ((size_t)h->ncells + 1), st)); h->cell_count_clean = true; }
     if (!h->slot_of_clean) { HIP_TRY(hipMemsetAsync(d.slot_of, 0xFF, sizeof(uint32_t) * (size_t)h->N, st)); h->slot_of_clean = true; }
     const uint32_t T_bound = N / MDX_TILE + h->ncol + 1;        // sum over columns of ceil(n / 64) <= N / 64 + ncol
     if (T_bound + 1 > h->cap_tiles) { *fell_back = true; return MDX_OK; }      // (cannot happen behind setup_grid; if it does, the unfused chain sizes its arrays itself)
     const TileOrderPlan plan = tile_order_plan(h, T_bound);
-    const bool prune = !std::isinf(h->r_list) && mdx_nb_variant(h) >= 2;
-    static const bool exact_prune = [] { const char* e = std::getenv("MDX_EXACT_PRUNE"); return !(e && e[0] == '0'); }();
+    const bool prune = list_is_pruned(h) && knobs.exact_prune;
     // interior / boundary tiles come out of the pruning pass when owned and ghost atoms sit in separate column populations
-    const bool classify_here = plan.split && plan.lpt && g.npop > 1 && prune && exact_prune;
+    const bool classify_here = plan.split && plan.lpt && g.npop > 1 && prune;
     if (plan.lpt && (!d.tile_lpt || d.cap_tile_lpt < T_bound)) { d.cap_tile_lpt = h->cap_tiles + 1; ALLOC(d.tile_lpt, d.cap_tile_lpt); }
     if (classify_here && (!d.tile_bnd || h->cap_tile_split < T_bound + 1)) {
         h->cap_tile_split = h->cap_tiles + 1;
@@ -1914,10 +1948,10 @@ static int rebuild_fast(mdx_handle* h, RebuildResult* res, bool* fell_back) {
     // ---- prep: caller-order positions (wrapped) and velocities, cells ----
     if (h->in_slot_space)
         hipLaunchKernelGGL(rb_prep_kernel<true>, dim3(div_up(N, 256)), dim3(256), 0, st, N, g, d.gid, d.slot_of, d.posq, d.vel, d.pos_orig,
-                           d.vel_orig, d.lflag, d.cell_of, d.sorted_orig, d.cell_count, d.rb_ctl);
+                           d.vel_orig, d.lflag, d.cell_of, d.sorted_orig, d.cell_count, d.rb_ctl + RB_NONFINITE);
     else
         hipLaunchKernelGGL(rb_prep_kernel<false>, dim3(div_up(N, 256)), dim3(256), 0, st, N, g, d.gid, d.slot_of, d.posq, d.vel, d.pos_orig,
-                           d.vel_orig, d.lflag, d.cell_of, d.sorted_orig, d.cell_count, d.rb_ctl);
+                           d.vel_orig, d.lflag, d.cell_of, d.sorted_orig, d.cell_count, d.rb_ctl + RB_NONFINITE);
     h->in_slot_space = false;
     {
         GridScanArgs ga{};
@@ -1930,91 +1964,32 @@ static int rebuild_fast(mdx_handle* h, RebuildResult* res, bool* fell_back) {
     }
     hipLaunchKernelGGL(rb_scatter_kernel, dim3(div_up(N, 256)), dim3(256), 0, st, N, d.cell_of, d.sorted_orig, d.cell_start, d.sorted_tmp);
     hipLaunchKernelGGL(cell_rank_kernel, dim3(div_up(N, 256)), dim3(256), 0, st, N, d.cell_of, d.cell_start, d.pos_orig, d.sorted_tmp, d.sorted_orig);
-    {
-        AssignArgs aa{};
-        aa.rb_ctl = d.rb_ctl; aa.nzb = g.nzb; aa.tile_col = d.tile_col; aa.tile_start = d.tile_start; aa.cell_start = d.cell_start;
-        aa.sorted_orig = d.sorted_orig; aa.pos_orig = d.pos_orig; aa.vel_orig = d.vel_orig; aa.gid = d.gid; aa.lflag = d.lflag;
-        aa.o_qs = d.o_qs; aa.o_lj = d.o_lj; aa.o_invm = d.o_invm; aa.orig_of = d.orig_of; aa.slot_of = d.slot_of;
-        aa.cl_kind = d.cl_kind; aa.kind_split = h->kind_split ? 1 : 0;
-        aa.posq = d.posq; aa.lj = d.lj; aa.vel = d.vel; aa.ref = d.ref; aa.force = d.force; aa.slot_flags = d.slot_flags; aa.path = d.path; aa.dprune = d.dprune;
-        aa.cl_lo = d.cl_lo; aa.cl_hi = d.cl_hi;
-        aa.role_off_o = h->n_roles ? d.role_off_o : nullptr; aa.role_cnt_s = h->n_roles ? d.role_cnt_s : nullptr;
-        hipLaunchKernelGGL(rb_assign_kernel, dim3(div_up(T_bound + 1, 4)), dim3(256), 0, st, aa);
-    }
-    h->in_slot_space = true;
-    const uint32_t S_bound = (T_bound + 1) * MDX_TILE;
-    if (h->n_roles) MDX_TRY(scan_u32_dev_n(h, d.role_cnt_s, d.role_off_s, S_bound + 1, d.scan_tmp, d.rb_ctl + RB_SCAN_N));
+    launch_assign(h, T_bound, d.rb_ctl + RB_T);
+    if (h->n_roles) MDX_TRY(roles_to_slots(h, (T_bound + 1) * MDX_TILE, false, false, d.rb_ctl + RB_SCAN_N));
 
     // ---- pair list: single pass, then the exact pruning ----
-    ListArgs a{};
-    a.T = T_bound; a.T_dev = d.rb_ctl + RB_T; a.g = g;
-    a.r_build = std::isinf(h->r_list) ? h->r_list : h->r_list * (1.0f + 1e-5f) + 1e-4f;
-    a.tile_col = d.tile_col; a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
-    a.orig_of = d.orig_of; a.slot_of = d.slot_of; a.gid = d.gid; a.slot_flags = d.slot_flags;
-    a.excl_off = d.excl_off; a.excl_idx = d.excl_idx;
-    a.counts = d.list_counts; a.entry_cnt = d.entry_cnt; a.mchunk_cnt = d.mchunk_cnt;
-    a.entry_off = d.entry_off; a.mchunk_off = d.mchunk_off; a.entries = d.entries; a.masks = d.masks;
-    a.err = d.flags_dev; a.null_cluster = T_bound * MDX_CL_PER_TILE;
-    a.mask_layout = mdx_nb_variant(h) >= 2 ? 2 : 1;
-    a.half = mdx_nb_half(h) ? 1 : 0;
-    a.cell_start = d.cell_start; a.posq = d.posq; a.pair_count = d.pair_count;
-    a.cursors = reinterpret_cast<unsigned long long*>(d.list_cursors);
-    a.n_regions = 1;
-    while (a.n_regions < (uint32_t)LB_REGIONS && a.n_regions * 128u <= T_bound) a.n_regions <<= 1;      // >= 64 tiles per region
-    a.region_cap_e = (uint32_t)(std::min<uint64_t>(h->cap_entries, 0xFFFFFFFFull) / a.n_regions) & ~7u;
-    a.region_cap_m = h->cap_mchunks / a.n_regions;
-    a.list_grid = (div_up(T_bound, LB_WAVES) + 7u) & ~7u;
-    uint32_t rf_blocks = 0;
-    if (h->n_roles) {
-        a.rf_S = S_bound; a.rf_role_off_o = d.role_off_o; a.rf_rec_o = d.role_rec_o; a.rf_role_off_s = d.role_off_s;
-        a.rf_rec_s = d.role_rec_s; a.rf_lflag = d.lflag; a.rf_tri_o = d.tri_o; a.rf_tri_s = d.tri_s;
-        rf_blocks = div_up(S_bound, LB_WAVES * 64);
-    }
-    if (g.npop > 1) hipLaunchKernelGGL((build_list_kernel<LB_SINGLE, LB_PLAIN_DD>), dim3(a.list_grid + rf_blocks), dim3(LB_WAVES * 64), 0, st, a);
-    else hipLaunchKernelGGL(build_list_kernel<LB_SINGLE>, dim3(a.list_grid + rf_blocks), dim3(LB_WAVES * 64), 0, st, a);
+    ListArgs a = list_args(h, T_bound, d.rb_ctl + RB_T);
+    launch_single_pass(h, &a);
     // Dual list: the inner list of the one-wave-per-tile class comes out of the exact pruning pass (prune_list_kernel<true>), so
     // that the force call behind this rebuild walks it instead of being a pruning pass itself.  Single-device handles, the
-    // conditions under which mdx_rebuild switches the dual list on (below), MDX_REBUILD_INNER=0: A/B knob.
+    // conditions under which mdx_rebuild switches the dual list on, MDX_REBUILD_INNER=0: A/B knob.
     // Measured (round 6, profiles/r06_rebuild_inner_ab.txt): the pass costs +96 us per rebuild at 1 M atoms (quick accept off, a second
     // ballot per surviving cluster pair) and saves the 151 us a pruning pass costs over an inner-list walk: 1936.6 -> 1946.6 steps/s on
     // the flexible headline box.  At the reference's default operating point (rigid OPC, dt 2 fs: a rebuild every 8 steps, the
     // pruning pass only 20 % dearer than the walk, kind filter in the pass) it LOSES: 864 -> 853 steps/s.  So: flexible systems
     // only; MDX_REBUILD_INNER=0 never, =2 always (A/B).
-    static const int inner_mode = [] { const char* e = std::getenv("MDX_REBUILD_INNER"); return e ? (e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1)) : 1; }();
-    const bool inner_env = inner_mode == 2 || (inner_mode == 1 && !mdx_has_constraints(h) && h->n_vsites == 0);
-    const float inner_skin_next = h->inner_skin_auto > 0.f ? h->inner_skin_auto : c_inner_skin(h->cfg);
-    const bool dual_next = !h->dual_auto_off && mdx_nb_half(h) && prune && inner_skin_next > 0.f && inner_skin_next < h->cfg.skin &&
-                           (h->n_vsites == 0 || h->vsites_convex);
-    const bool inner_here = inner_env && dual_next && exact_prune && !h->dd && h->n_local == h->N && g.npop == 1 && !h->alch_on &&
+    const bool inner_env = knobs.inner_mode == 2 || (knobs.inner_mode == 1 && !mdx_has_constraints(h) && h->n_vsites == 0);
+    const float inner_skin_next = next_inner_skin(h);
+    const bool inner_here = inner_env && prune && dual_list_wanted(h, inner_skin_next) && !h->dd && h->n_local == h->N && g.npop == 1 && !h->alch_on &&
                             d.entries_in && d.inner_nch;
-    bool inner_launched = false;
-    if (prune && exact_prune) {
-        const float rb = a.r_build;
-        const float shx = h->per[0] ? h->box_hi[0] - h->box_lo[0] : 0.f, shy = h->per[1] ? h->box_hi[1] - h->box_lo[1] : 0.f,
-                    shz = h->per[2] ? h->box_hi[2] - h->box_lo[2] : 0.f;
-        uint32_t* const tint = classify_here ? d.tile_bnd : nullptr;
-        const uint8_t* const kinds = h->kind_split ? d.cl_kind : nullptr;     // cluster pairs without a common interaction kind leave the list
-        // One wave per tile is a launch as long as its longest list: one rank of 8 of the 1 M-atom box - 3.3 k tiles, the owned ones
-        // with ~150 chunks - took 233 us where the whole box, five times the work, takes 256.  Eight waves per tile up to
-        // MDX_PRUNE_MW_BELOW tiles (the unfused chain keeps its 2048)
-        static const uint32_t mw_below = [] { const char* e = std::getenv("MDX_PRUNE_MW_BELOW"); return e ? (uint32_t)std::atoi(e) : 12000u; }();
-        if (T_bound < mw_below)
-            hipLaunchKernelGGL(prune_list_mw_kernel<8>, dim3(T_bound), dim3(512), 0, st, T_bound, rb * rb, shx, shy, shz, d.posq, d.list_counts,
-                               d.entry_off, d.entries, a.null_cluster, d.pair_count, (const uint32_t*)d.rb_ctl, tint, kinds);
-        else if (inner_here) {
-            PruneInner pin{};
-            pin.entries_in = d.entries_in; pin.inner_nch = d.inner_nch; pin.rule = mdx_wpt_rule_of(h);
-            const float rin = std::max(std::isfinite(h->cfg.lj_cutoff) && h->cfg.lj_cutoff > 0.f ? h->cfg.lj_cutoff : 0.f,
-                                       std::isfinite(h->cfg.coulomb_cutoff) && h->cfg.coulomb_cutoff > 0.f ? h->cfg.coulomb_cutoff : 0.f) + inner_skin_next;
-            pin.rin2 = rin * rin;      // (= NbArgs::rin2 of the pair kernel's pruning pass, mdx_nonbonded.hip)
-            hipLaunchKernelGGL(prune_list_kernel<true>, dim3((div_up(T_bound, 4) + 7u) & ~7u), dim3(256), 0, st, T_bound, rb * rb, shx, shy, shz,
-                               d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, (const uint32_t*)d.rb_ctl, tint, kinds, pin);
-            inner_launched = true;
-        } else
-            hipLaunchKernelGGL(prune_list_kernel<false>, dim3((div_up(T_bound, 4) + 7u) & ~7u), dim3(256), 0, st, T_bound, rb * rb, shx, shy, shz,
-                               d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, (const uint32_t*)d.rb_ctl, tint, kinds,
-                               PruneInner{});
+    PruneInner pin{};
+    if (inner_here) {
+        pin.entries_in = d.entries_in; pin.inner_nch = d.inner_nch; pin.rule = mdx_wpt_rule_of(h);
+        const float rin = std::max(std::isfinite(h->cfg.lj_cutoff) && h->cfg.lj_cutoff > 0.f ? h->cfg.lj_cutoff : 0.f,
+                                   std::isfinite(h->cfg.coulomb_cutoff) && h->cfg.coulomb_cutoff > 0.f ? h->cfg.coulomb_cutoff : 0.f) + inner_skin_next;
+        pin.rin2 = rin * rin;      // (= NbArgs::rin2 of the pair kernel's pruning pass, mdx_nonbonded.hip)
     }
+    const bool inner_launched = prune && launch_exact_prune(h, a, knobs.mw_below, d.rb_ctl, classify_here ? d.tile_bnd : nullptr, inner_here ? &pin : nullptr);
     MDX_TRY(mdx_remap_constraints(h));
     // ---- finish: tile orders, totals, the one read-back ----
     const uint32_t seq = ++h->rb_seq;
@@ -2025,31 +2000,26 @@ static int rebuild_fast(mdx_handle* h, RebuildResult* res, bool* fell_back) {
         fa.tile_int = classify_here ? d.tile_bnd : nullptr; fa.tile_order = classify_here ? d.tile_order : nullptr;
         fa.cursors = reinterpret_cast<const unsigned long long*>(d.list_cursors); fa.pair_count = d.pair_count; fa.flags = d.flags_dev;
         fa.host = (volatile uint32_t*)h->h_rb; fa.seq = seq;
-        hipLaunchKernelGGL(rb_finish_kernel, dim3(1), dim3(1024), 0, st, fa);
+        hipLaunchKernelGGL(rb_finish_kernel, dim3(1), dim3(SCAN1_THREADS), 0, st, fa);
     }
     HIP_TRY(hipGetLastError());
     MDX_TRY(spin_on_readback(h, seq));
-    const uint32_t T = h->h_rb[0];
-    uint32_t flags[4];
-    for (int k = 0; k < 4; ++k) flags[k] = h->h_rb[4 + k];
+    const uint32_t T = h->h_rb[0], flags0 = h->h_rb[4];
     if (h->h_rb[2]) { h->cell_count_clean = false; mdx_set_error("non-finite position at neighbour rebuild"); return MDX_ENAN; }
     if (T > T_bound) { mdx_set_error("internal: tile count beyond its bound"); return MDX_EDEVICE; }
     h->T = T; h->S = (T + 1) * MDX_TILE;
-    if (flags[0] & 1u) { mdx_set_error("exclusion table overflow while building the pair list"); return MDX_EPARAM; }
-    if (flags[0] & (16u | 32u)) {      // a tile beyond the LDS buffers, or a list that outgrew the arrays: the unfused chain sizes them afresh
-        if (std::getenv("MDX_LIST_DEBUG")) fprintf(stderr, "[mdx] fused list rebuild fell back: flags %u, T %u, cap_e %llu cap_m %u regions %u\n",
-                                                   flags[0], T, (unsigned long long)h->cap_entries, h->cap_mchunks, a.n_regions);
+    MDX_TRY(list_flags_error(flags0 & 1u));
+    if (flags0 & (16u | 32u)) {
+        if (knobs.list_debug) fprintf(stderr, "[mdx] fused list rebuild fell back: flags %u, T %u, cap_e %llu cap_m %u regions %u\n",
+                                      flags0, T, (unsigned long long)h->cap_entries, h->cap_mchunks, a.n_regions);
         *fell_back = true;
         return MDX_OK;
     }
-    if (flags[0] & 8u) { mdx_set_error("a constrained / virtual-site atom is missing from the local atom set"); return MDX_EPARAM; }
-    if (flags[0] & 2u) { mdx_set_error("exclusion table overflow while building the pair list"); return MDX_EPARAM; }
-    if (flags[0] & 4u) { mdx_set_error("a bonded partner of an owned atom is missing from the local atom set (halo too thin)"); return MDX_EPARAM; }
-    res->T = T; res->E = h->h_rb[8]; res->MC = h->h_rb[9];
+    MDX_TRY(list_flags_error(flags0));
+    res->E = h->h_rb[8]; res->MC = h->h_rb[9];
     const unsigned long long built = (unsigned long long)h->h_rb[10] | ((unsigned long long)h->h_rb[11] << 32);
     const unsigned long long kept = (unsigned long long)h->h_rb[12] | ((unsigned long long)h->h_rb[13] << 32);
-    res->npairs = (prune && exact_prune) ? kept : built;
-    h->E = res->E; h->MC = res->MC;
+    res->npairs = prune ? kept : built;
     res->ordered = true;
     res->inner_built = inner_launched && mdx_wpt_rule(mdx_wpt_rule_of(h), T) == 1;      // (the kernel applied the same rule to the same T)
     h->force_zeroed = true;      // rb_assign_kernel cleared every slot's force: the pair launch behind this rebuild needs no fill of its own
@@ -2059,6 +2029,136 @@ static int rebuild_fast(mdx_handle* h, RebuildResult* res, bool* fell_back) {
     return MDX_OK;
 }
 
+// Count + scan + fill: the list build that sizes the entry and mask arrays itself (a handle's first build, MDX_LIST_TWO_PASS=1, and
+// behind a single pass that overflowed).
+// A region of the single-pass build fills at cap / n_regions, which an imbalance between the regions reaches before the
+// totals reach cap: while a list grows (equilibration, a shrinking box, an inhomogeneous solute) every rebuild would then
+// run the single pass AND count + fill with the arrays unchanged.  After such an overflow (grow_for_regions) the arrays are sized
+// with half as much room again as the list needs, so the overflow is paid once (round-2 advisor finding).
+static int build_list_two_pass(mdx_handle* h, ListArgs* a, bool grow_for_regions, RebuildResult* res) {
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t T = a->T;
+    const dim3 grid((div_up(T, LB_WAVES) + 7u) & ~7u), block(LB_WAVES * 64);
+    HIP_TRY(hipMemsetAsync(d.pair_count, 0, sizeof(unsigned long long) * (PC_TOTAL + 2), st));
+    HIP_TRY(hipMemsetAsync(d.entry_cnt + T, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(d.mchunk_cnt + T, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(build_list_kernel<LB_COUNT>, grid, block, 0, st, *a);
+    MDX_TRY(mdx_exclusive_scan_u32(h, d.entry_cnt, d.entry_off, T + 1));
+    MDX_TRY(mdx_exclusive_scan_u32(h, d.mchunk_cnt, d.mchunk_off, T + 1));
+    hipLaunchKernelGGL(pair_sum_kernel, dim3(1), dim3(64), 0, st, d.pair_count);
+    MDX_TRY(readback(h, RbSrc{{d.flags_dev, d.entry_off + T, d.mchunk_off + T, reinterpret_cast<const uint32_t*>(d.pair_count + PC_TOTAL)}, {4, 1, 1, 2}}));
+    const uint32_t E = h->h_rb[4], MC = h->h_rb[5];
+    res->E = E; res->MC = MC;
+    res->npairs = (unsigned long long)h->h_rb[6] | ((unsigned long long)h->h_rb[7] << 32);
+    MDX_TRY(list_flags_error(h->h_rb[0] & 3u));
+    if (E > h->cap_entries || !d.entries || (grow_for_regions && (double)h->cap_entries < 1.5 * (double)E)) {
+        h->cap_entries = (uint64_t)(E * (grow_for_regions ? 1.5 : 1.25)) + 1024;
+        ALLOC(d.entries, h->cap_entries);
+        ALLOC(d.entries_in, h->cap_entries);   // dual list: the pruning pass of the pair kernel fills it
+        a->entries = d.entries;
+    }
+    if (MC > h->cap_mchunks || !d.masks || (grow_for_regions && (double)h->cap_mchunks < 1.5 * (double)MC)) {
+        h->cap_mchunks = (uint32_t)(MC * (grow_for_regions ? 1.5 : 1.25)) + 64;
+        ALLOC(d.masks, (size_t)h->cap_mchunks * 64);
+        a->masks = d.masks;
+    }
+    hipLaunchKernelGGL(build_list_kernel<LB_FILL>, grid, block, 0, st, *a);
+    return MDX_OK;
+}
+
+// The unfused chain's one synchronisation behind the list: error bits, the single pass's totals (count + fill has read its own),
+// the pair counts as built and as pruned.
+static int read_list_totals(mdx_handle* h, bool single, uint32_t* flags0, RebuildResult* res, unsigned long long* npairs_pruned) {
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    if (single) hipLaunchKernelGGL(cursor_sum_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned long long*>(d.list_cursors),
+                                   d.list_cursors + LB_REGIONS * 32);
+    hipLaunchKernelGGL(pair_sum_kernel, dim3(1), dim3(64), 0, st, d.pair_count);
+    MDX_TRY(readback(h, RbSrc{{d.flags_dev, d.list_cursors ? d.list_cursors + LB_REGIONS * 32 : nullptr,
+                               reinterpret_cast<const uint32_t*>(d.pair_count + PC_TOTAL), nullptr}, {4, 2, 4, 0}}));
+    *flags0 = h->h_rb[0];
+    if (single) {
+        res->E = h->h_rb[4]; res->MC = h->h_rb[5];
+        res->npairs = (unsigned long long)h->h_rb[6] | ((unsigned long long)h->h_rb[7] << 32);
+    }
+    *npairs_pruned = (unsigned long long)h->h_rb[8] | ((unsigned long long)h->h_rb[9] << 32);
+    return MDX_OK;
+}
+
+// The unfused chain: the stages of the fused chain as launches of their own, the tile count read by the host in front of the tile
+// assignment (the first of its three waits), and either list build.  It sizes every array itself, so it is where a handle starts,
+// where vacuum systems and very large grids stay, and where the fused chain falls back to.  The caller has moved the dynamic state
+// to the caller-order staging (mdx_unsort_state).
+static int rebuild_unfused(mdx_handle* h, RebuildResult* res) {
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t N = h->n_local;
+    const GridParams g = h->grid;
+    const RebuildKnobs& knobs = rebuild_knobs();
+    h->cell_count_clean = false;     // (this chain leaves the histogram behind)
+    {   // slot_of = invalid, cell counters = 0, error bits = 0: one launch instead of three fills
+        const uint32_t n_max = std::max<uint32_t>(h->N, h->ncells + 1);
+        hipLaunchKernelGGL(rebuild_clear_kernel, dim3(div_up(n_max, 256)), dim3(256), 0, st, d.slot_of, h->N, d.cell_count, h->ncells + 1, d.flags_dev);
+    }
+    hipLaunchKernelGGL(rb_prep_kernel<false>, dim3(div_up(N, 256)), dim3(256), 0, st, N, g, d.gid, d.slot_of, d.posq, d.vel, d.pos_orig,
+                       d.vel_orig, d.lflag, d.cell_of, d.sorted_orig, d.cell_count, d.flags_dev + 1);
+    MDX_TRY(mdx_exclusive_scan_u32(h, d.cell_count, d.cell_start, h->ncells + 1));
+    hipLaunchKernelGGL(column_tiles_kernel, dim3(div_up(h->ncol + 1, 256)), dim3(256), 0, st, d.cell_start, h->ncol, g.nzb, d.col_tiles);
+    MDX_TRY(mdx_exclusive_scan_u32(h, d.col_tiles, d.tile_start, h->ncol + 1));
+    hipLaunchKernelGGL(rb_scatter_kernel, dim3(div_up(N, 256)), dim3(256), 0, st, N, d.cell_of, d.sorted_orig, d.cell_start, d.sorted_tmp);
+    hipLaunchKernelGGL(cell_rank_kernel, dim3(div_up(N, 256)), dim3(256), 0, st, N, d.cell_of, d.cell_start, d.pos_orig, d.sorted_tmp, d.sorted_orig);
+    h->slot_of_clean = true;
+    MDX_TRY(readback(h, RbSrc{{d.tile_start + h->ncol, d.flags_dev, nullptr, nullptr}, {1, 4, 0, 0}}));
+    const uint32_t T = h->h_rb[0];
+    if (h->h_rb[2]) { mdx_set_error("non-finite position at neighbour rebuild"); return MDX_ENAN; }
+    if (T + 1 > h->cap_tiles) { mdx_set_error("internal: tile capacity exceeded"); return MDX_EDEVICE; }
+    h->T = T; h->S = (T + 1) * MDX_TILE;
+    hipLaunchKernelGGL(tile_col_kernel, dim3(div_up(h->ncol, 256)), dim3(256), 0, st, d.tile_start, h->ncol, d.tile_col);
+    launch_assign(h, T, nullptr);
+
+    // ---- pair list ----
+    // Single pass when the arrays of the previous build are there to be reused (every rebuild but the first): one search of every
+    // tile's neighbourhood instead of count + scan + fill.  It is launched and NOT waited for: the exact pruning, the bonded role
+    // lists and the constraint remap queue up behind it, and its cursors and overflow bits are read at the one synchronisation at
+    // the end.  A tile that did not fit has an empty list (counts 0) by then, so what ran behind it was safe; count + fill then
+    // builds afresh.
+    if (!d.pair_count) ALLOC(d.pair_count, PC_TOTAL + 2);
+    const bool single = d.entries && d.masks && h->cap_entries && h->cap_mchunks && T && !knobs.two_pass;
+    const bool prune = list_is_pruned(h) && knobs.exact_prune;
+    if (h->n_roles) MDX_TRY(roles_to_slots(h, h->S, false, !single, nullptr));
+    ListArgs a = list_args(h, T, nullptr);
+    if (single) {
+        if (!d.list_cursors) ALLOC(d.list_cursors, LB_REGIONS * 32 + 2);     // 64 regions x one 128-B line, + the two totals
+        HIP_TRY(hipMemsetAsync(d.pair_count, 0, sizeof(unsigned long long) * (PC_TOTAL + 2), st));
+        HIP_TRY(hipMemsetAsync(d.list_cursors, 0, sizeof(uint32_t) * (LB_REGIONS * 32 + 2), st));
+        launch_single_pass(h, &a);
+    } else {
+        MDX_TRY(build_list_two_pass(h, &a, false, res));
+    }
+    if (prune) (void)launch_exact_prune(h, a, PRUNE_MW_BELOW_UNFUSED, nullptr, nullptr, nullptr);
+    MDX_TRY(mdx_remap_constraints(h));
+    HIP_TRY(hipGetLastError());
+    uint32_t flags0 = 0;
+    unsigned long long npairs_pruned = 0;
+    MDX_TRY(read_list_totals(h, single, &flags0, res, &npairs_pruned));
+    MDX_TRY(list_flags_error(flags0 & 1u));
+    if (single && (flags0 & (16u | 32u))) {
+        // a tile beyond the LDS buffers, or a list that outgrew the arrays: count + fill sizes them afresh
+        // (the role lists and the constraint remap above do not depend on the pair list and stand)
+        const uint32_t keep = flags0 & ~(16u | 32u);
+        HIP_TRY(hipMemcpyAsync(d.flags_dev, &keep, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (knobs.list_debug) fprintf(stderr, "[mdx] single-pass list build fell back: flags %u, T %u, E %u MC %u, cap_e %llu cap_m %u regions %u\n",
+                                      flags0, T, res->E, res->MC, (unsigned long long)h->cap_entries, h->cap_mchunks, a.n_regions);
+        MDX_TRY(build_list_two_pass(h, &a, (flags0 & 32u) != 0, res));
+        if (prune) (void)launch_exact_prune(h, a, PRUNE_MW_BELOW_UNFUSED, nullptr, nullptr, nullptr);
+        MDX_TRY(read_list_totals(h, false, &flags0, res, &npairs_pruned));
+    }
+    MDX_TRY(list_flags_error(flags0));
+    if (prune) res->npairs = npairs_pruned;
+    return MDX_OK;
+}
 
 int mdx_rebuild(mdx_handle* h) {
     MdxRange range_rebuild("mdx list rebuild");
@@ -2072,247 +2172,49 @@ int mdx_rebuild(mdx_handle* h) {
         HIP_TRY(hipEventRecord(e0, h->stream));
     }
     DeviceState& d = h->d;
-    // Every rebuild but a handle's first (and a few unusual ones) takes the fused chain above: MDX_REBUILD_FUSED=0 for A/B.
-    static const bool fused_env = [] { const char* e = std::getenv("MDX_REBUILD_FUSED"); return !(e && e[0] == '0'); }();
-    static const bool two_pass_env0 = [] { const char* e = std::getenv("MDX_LIST_TWO_PASS"); return e && e[0] == '1'; }();
-    bool fast = fused_env && !two_pass_env0 && d.entries && d.masks && h->cap_entries && h->cap_mchunks && h->T > 0 && h->n_local > 0;
+    hipStream_t st = h->stream;
+    const RebuildKnobs& knobs = rebuild_knobs();
+
+    // ---- which chain: every rebuild but a handle's first (and a few unusual ones) takes the fused one ----
+    bool fast = knobs.fused && !knobs.two_pass && d.entries && d.masks && h->cap_entries && h->cap_mchunks && h->T > 0 && h->n_local > 0;
     for (int k = 0; k < 3; ++k) if (!h->per[k] && !h->have_local_bounds) fast = false;      // (a vacuum system: the grid follows the atoms' bounding box)
     if (!fast) MDX_TRY(mdx_unsort_state(h));  // dynamic state -> caller-order staging
     const bool was_in_slot_space = h->in_slot_space;
     MDX_TRY(setup_grid(h));
-    if (fast && (size_t)h->ncells + 1 > ((size_t)1 << 21)) { fast = false; MDX_TRY(mdx_unsort_state(h)); }   // (the grid scan is a chain of at most 32 windows)
-    if (fast && was_in_slot_space && !h->in_slot_space) fast = false;      // (setup_grid had to grow the slot-space arrays and moved the state to the staging)
-    const uint32_t N = h->n_local;   // atoms simulated here (all of them on a single GPU)
-    const GridParams g = h->grid;
-    hipStream_t st = h->stream;
+    if ((size_t)h->ncells + 1 > ((size_t)1 << 21)) fast = false;      // (the grid scan is a chain of at most 32 windows)
+    if (was_in_slot_space && !h->in_slot_space) fast = false;         // (setup_grid had to grow the slot-space arrays and moved the state to the staging)
+
+    // ---- the chain ----
     RebuildResult res;
-    bool fast_done = false;
+    bool fell_back = false;
     if (fast) {
-        bool fell_back = false;
         MDX_TRY(rebuild_fast(h, &res, &fell_back));
-        fast_done = !fell_back;
-        if (fell_back) { MDX_TRY(mdx_unsort_state(h)); h->stats.rebuild_fallbacks++; }
+        if (fell_back) h->stats.rebuild_fallbacks++;
     }
-    uint32_t E = res.E, MC = res.MC;
-    unsigned long long npairs = res.npairs;
-    const bool prune = !std::isinf(h->r_list) && mdx_nb_variant(h) >= 2;   // the whole-tile kernel ignores imask
-    if (!fast_done) {
-    h->cell_count_clean = false;     // (this chain leaves the histogram behind)
-    {   // slot_of = invalid, cell counters and cursors = 0, error bits = 0: one launch instead of four fills
-        const uint32_t n_max = std::max<uint32_t>(h->N, h->ncells + 1);
-        hipLaunchKernelGGL(rebuild_clear_kernel, dim3(div_up(n_max, 256)), dim3(256), 0, st, d.slot_of, h->N, d.cell_count,
-                           d.cell_cursor, h->ncells + 1, d.flags_dev);
+    if (!fast || fell_back) {
+        MDX_TRY(mdx_unsort_state(h));      // (nothing to do unless the fused chain was given up after setup_grid, or fell back)
+        res = RebuildResult{};
+        MDX_TRY(rebuild_unfused(h, &res));
     }
-    hipLaunchKernelGGL(bin_atoms_kernel, dim3(div_up(N, 256)), dim3(256), 0, st, d.pos_orig, N, g, d.lflag, d.cell_of,
-                       d.cell_count, d.flags_dev + 1);
-    MDX_TRY(mdx_exclusive_scan_u32(h, d.cell_count, d.cell_start, h->ncells + 1));
-    hipLaunchKernelGGL(column_tiles_kernel, dim3(div_up(h->ncol + 1, 256)), dim3(256), 0, st, d.cell_start,
-                       h->ncol, g.nzb, d.col_tiles);
-    MDX_TRY(mdx_exclusive_scan_u32(h, d.col_tiles, d.tile_start, h->ncol + 1));
-    hipLaunchKernelGGL(scatter_kernel, dim3(div_up(N, 256)), dim3(256), 0, st, d.cell_of, d.cell_start,
-                       d.cell_cursor, d.sorted_tmp, N);
-    hipLaunchKernelGGL(cell_rank_kernel, dim3(div_up(N, 256)), dim3(256), 0, st, N, d.cell_of, d.cell_start,
-                       d.pos_orig, d.sorted_tmp, d.sorted_orig);
-    h->slot_of_clean = true;
-    uint32_t T = 0, flags[4] = {0, 0, 0, 0};
-    MDX_TRY(readback(h, RbSrc{{d.tile_start + h->ncol, d.flags_dev, nullptr, nullptr}, {1, 4, 0, 0}}));
-    T = h->h_rb[0];
-    for (int k = 0; k < 4; ++k) flags[k] = h->h_rb[1 + k];
-    if (flags[1]) { mdx_set_error("non-finite position at neighbour rebuild"); return MDX_ENAN; }
-    if (T + 1 > h->cap_tiles) { mdx_set_error("internal: tile capacity exceeded"); return MDX_EDEVICE; }
-    h->T = T;
-    h->S = (T + 1) * MDX_TILE;
-    const uint32_t S = h->S, NC = (T + 1) * MDX_CL_PER_TILE;
+    h->E = res.E; h->MC = res.MC;
 
-    hipLaunchKernelGGL(tile_col_kernel, dim3(div_up(h->ncol, 256)), dim3(256), 0, st, d.tile_start, h->ncol,
-                       d.tile_col);
-    hipLaunchKernelGGL(assign_tiles_kernel, dim3(div_up(T + 1, 4)), dim3(256), 0, st, T, g.nzb, d.tile_col,
-                       d.tile_start, d.cell_start, d.sorted_orig, d.pos_orig, d.gid, d.orig_of, d.slot_of, h->kind_split ? 1 : 0,
-                       d.lflag, d.o_qs, d.o_lj);
-    hipLaunchKernelGGL(gather_slots_kernel, dim3(div_up(S, 256)), dim3(256), 0, st, S, d.orig_of, d.gid, d.lflag,
-                       d.pos_orig, d.vel_orig, d.o_qs, d.o_lj, d.o_invm, d.posq, d.lj, d.vel, d.ref, d.force,
-                       d.slot_flags, d.path, d.dprune);
-    hipLaunchKernelGGL(cluster_bbox_kernel, dim3(div_up(NC, 256)), dim3(256), 0, st, NC, d.orig_of, d.posq,
-                       d.slot_flags, d.cl_lo, d.cl_hi, d.lj, d.cl_kind);
-    h->in_slot_space = true;
-
-    // ---- pair list: count, scan, fill ----
-    ListArgs a{};
-    a.T = T; a.g = g;
-    a.r_build = std::isinf(h->r_list) ? h->r_list : h->r_list * (1.0f + 1e-5f) + 1e-4f;
-    a.tile_col = d.tile_col; a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
-    a.orig_of = d.orig_of; a.slot_of = d.slot_of; a.gid = d.gid; a.slot_flags = d.slot_flags;
-    a.excl_off = d.excl_off; a.excl_idx = d.excl_idx;
-    a.counts = d.list_counts; a.entry_cnt = d.entry_cnt; a.mchunk_cnt = d.mchunk_cnt;
-    a.entry_off = d.entry_off; a.mchunk_off = d.mchunk_off; a.entries = d.entries; a.masks = d.masks;
-    a.err = d.flags_dev; a.null_cluster = T * MDX_CL_PER_TILE;
-    a.mask_layout = mdx_nb_variant(h) >= 2 ? 2 : 1;
-    a.half = mdx_nb_half(h) ? 1 : 0;
-    a.cell_start = d.cell_start;
-    a.posq = d.posq;
-    if (!d.pair_count) ALLOC(d.pair_count, PC_TOTAL + 2);
-    a.pair_count = d.pair_count;
-    E = 0; MC = 0; npairs = 0;
-    // Single pass when the arrays of the previous build are there to be reused (every rebuild but the first): one
-    // search of every tile's neighbourhood instead of count + scan + fill.  MDX_LIST_TWO_PASS=1 keeps the two passes.
-    static const bool two_pass_env = [] { const char* e = std::getenv("MDX_LIST_TWO_PASS"); return e && e[0] == '1'; }();
-    // The single pass is launched and NOT waited for: the exact pruning, the bonded role lists and the constraint remap
-    // queue up behind it, and its cursors and overflow bits are read at the one synchronisation at the end.  A tile that
-    // did not fit has an empty list (counts 0) by then, so what ran behind it was safe; count + fill then builds afresh.
-    bool speculative = false, roles_done = false;
-    if (d.entries && d.masks && h->cap_entries && h->cap_mchunks && T && !two_pass_env) {
-        if (!d.list_cursors) ALLOC(d.list_cursors, LB_REGIONS * 32 + 2);     // 64 regions x one 128-B line, + the two totals
-        HIP_TRY(hipMemsetAsync(d.pair_count, 0, sizeof(unsigned long long) * (PC_TOTAL + 2), st));
-        HIP_TRY(hipMemsetAsync(d.list_cursors, 0, sizeof(uint32_t) * (LB_REGIONS * 32 + 2), st));
-        a.cursors = reinterpret_cast<unsigned long long*>(d.list_cursors);
-        a.n_regions = 1;
-        while (a.n_regions < (uint32_t)LB_REGIONS && a.n_regions * 128u <= T) a.n_regions <<= 1;      // >= 64 tiles per region
-        a.region_cap_e = (uint32_t)(std::min<uint64_t>(h->cap_entries, 0xFFFFFFFFull) / a.n_regions) & ~7u;
-        a.region_cap_m = h->cap_mchunks / a.n_regions;
-        a.list_grid = (div_up(T, LB_WAVES) + 7u) & ~7u;
-        uint32_t rf_blocks = 0;
-        if (h->n_roles) {      // bonded role lists into slot space: count + scan here, the fill as extra workgroups of the list build
-            hipLaunchKernelGGL(role_count_kernel, dim3(div_up(S + 1, 256)), dim3(256), 0, st, S, d.orig_of, d.gid,
-                               d.lflag, d.role_off_o, d.role_cnt_s);
-            MDX_TRY(mdx_exclusive_scan_u32(h, d.role_cnt_s, d.role_off_s, S + 1));
-            a.rf_S = S; a.rf_role_off_o = d.role_off_o; a.rf_rec_o = d.role_rec_o; a.rf_role_off_s = d.role_off_s;
-            a.rf_rec_s = d.role_rec_s; a.rf_lflag = d.lflag; a.rf_tri_o = d.tri_o; a.rf_tri_s = d.tri_s;
-            rf_blocks = div_up(S, LB_WAVES * 64);
-            roles_done = true;
-        }
-        if (g.npop > 1) hipLaunchKernelGGL((build_list_kernel<LB_SINGLE, LB_PLAIN_DD>), dim3(a.list_grid + rf_blocks), dim3(LB_WAVES * 64), 0, st, a);
-        else hipLaunchKernelGGL(build_list_kernel<LB_SINGLE>, dim3(a.list_grid + rf_blocks), dim3(LB_WAVES * 64), 0, st, a);
-        speculative = true;
-    }
-    // A region of the single-pass build fills at cap / n_regions, which an imbalance between the regions reaches before the
-    // totals reach cap: while a list grows (equilibration, a shrinking box, an inhomogeneous solute) every rebuild would then
-    // run the speculative pass AND count + fill with the arrays unchanged.  After such an overflow the arrays are sized with
-    // half as much room again as the list needs, so the overflow is paid once (round-2 advisor finding).
-    bool grow_for_regions = false;
-    auto two_pass = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(d.pair_count, 0, sizeof(unsigned long long) * (PC_TOTAL + 2), st));
-        HIP_TRY(hipMemsetAsync(d.entry_cnt + T, 0, sizeof(uint32_t), st));
-        HIP_TRY(hipMemsetAsync(d.mchunk_cnt + T, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(build_list_kernel<LB_COUNT>, dim3((div_up(T, LB_WAVES) + 7u) & ~7u), dim3(LB_WAVES * 64), 0, st, a);
-        MDX_TRY(mdx_exclusive_scan_u32(h, d.entry_cnt, d.entry_off, T + 1));
-        MDX_TRY(mdx_exclusive_scan_u32(h, d.mchunk_cnt, d.mchunk_off, T + 1));
-        hipLaunchKernelGGL(pair_sum_kernel, dim3(1), dim3(64), 0, st, d.pair_count);
-        MDX_TRY(readback(h, RbSrc{{d.flags_dev, d.entry_off + T, d.mchunk_off + T, reinterpret_cast<const uint32_t*>(d.pair_count + PC_TOTAL)}, {4, 1, 1, 2}}));
-        for (int k = 0; k < 4; ++k) flags[k] = h->h_rb[k];
-        E = h->h_rb[4]; MC = h->h_rb[5];
-        npairs = (unsigned long long)h->h_rb[6] | ((unsigned long long)h->h_rb[7] << 32);
-        if (flags[0] & 3u) { mdx_set_error("exclusion table overflow while building the pair list"); return MDX_EPARAM; }
-        if (E > h->cap_entries || !d.entries || (grow_for_regions && (double)h->cap_entries < 1.5 * (double)E)) {
-            h->cap_entries = (uint64_t)(E * (grow_for_regions ? 1.5 : 1.25)) + 1024;
-            ALLOC(d.entries, h->cap_entries);
-            ALLOC(d.entries_in, h->cap_entries);   // dual list: the pruning pass of the pair kernel fills it
-            a.entries = d.entries;
-        }
-        if (MC > h->cap_mchunks || !d.masks || (grow_for_regions && (double)h->cap_mchunks < 1.5 * (double)MC)) {
-            h->cap_mchunks = (uint32_t)(MC * (grow_for_regions ? 1.5 : 1.25)) + 64;
-            ALLOC(d.masks, (size_t)h->cap_mchunks * 64);
-            a.masks = d.masks;
-        }
-        h->E = E; h->MC = MC;
-        hipLaunchKernelGGL(build_list_kernel<LB_FILL>, dim3((div_up(T, LB_WAVES) + 7u) & ~7u), dim3(LB_WAVES * 64), 0, st, a);
-        return MDX_OK;
-    };
-    if (!speculative) MDX_TRY(two_pass());
-    static const bool exact_prune = [] { const char* e = std::getenv("MDX_EXACT_PRUNE"); return !(e && e[0] == '0'); }();   // A/B knob
-    auto launch_prune = [&]() {
-        if (!(prune && T && exact_prune)) return;
-        const uint8_t* const kinds = h->kind_split ? d.cl_kind : nullptr;
-        const float rb = a.r_build;
-        const float shx = h->per[0] ? h->box_hi[0] - h->box_lo[0] : 0.f, shy = h->per[1] ? h->box_hi[1] - h->box_lo[1] : 0.f,
-                    shz = h->per[2] ? h->box_hi[2] - h->box_lo[2] : 0.f;
-        if (T < 2048u)          // a few hundred tiles: eight waves per tile (one wave per tile is a 1/3-empty chip waiting for its longest list)
-            hipLaunchKernelGGL(prune_list_mw_kernel<8>, dim3(T), dim3(512), 0, st, T, rb * rb, shx, shy, shz, d.posq, d.list_counts,
-                               d.entry_off, d.entries, a.null_cluster, d.pair_count, (const uint32_t*)nullptr, (uint32_t*)nullptr, kinds);
-        else
-            hipLaunchKernelGGL(prune_list_kernel<false>, dim3((div_up(T, 4) + 7u) & ~7u), dim3(256), 0, st, T, rb * rb, shx, shy, shz,
-                               d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, (const uint32_t*)nullptr, (uint32_t*)nullptr, kinds,
-                               PruneInner{});
-    };
-    launch_prune();
-
-    // ---- bonded role lists into slot space ----
-    if (h->n_roles && !roles_done) {
-        hipLaunchKernelGGL(role_count_kernel, dim3(div_up(S + 1, 256)), dim3(256), 0, st, S, d.orig_of, d.gid,
-                           d.lflag, d.role_off_o, d.role_cnt_s);
-        MDX_TRY(mdx_exclusive_scan_u32(h, d.role_cnt_s, d.role_off_s, S + 1));
-        hipLaunchKernelGGL(role_fill_kernel, dim3(div_up(S, 256)), dim3(256), 0, st, S, d.orig_of, d.gid, d.lflag,
-                           d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev, d.tri_o, d.tri_s);
-    }
-    MDX_TRY(mdx_remap_constraints(h));
-    HIP_TRY(hipGetLastError());
-    unsigned long long npairs_pruned = 0;
-    auto read_counts = [&]() -> int {
-        if (speculative) hipLaunchKernelGGL(cursor_sum_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned long long*>(d.list_cursors),
-                                            d.list_cursors + LB_REGIONS * 32);
-        hipLaunchKernelGGL(pair_sum_kernel, dim3(1), dim3(64), 0, st, d.pair_count);
-        MDX_TRY(readback(h, RbSrc{{d.flags_dev, d.list_cursors ? d.list_cursors + LB_REGIONS * 32 : nullptr,
-                                   reinterpret_cast<const uint32_t*>(d.pair_count + PC_TOTAL), nullptr}, {4, 2, 4, 0}}));
-        for (int k = 0; k < 4; ++k) flags[k] = h->h_rb[k];
-        if (speculative) {
-            E = h->h_rb[4]; MC = h->h_rb[5];
-            npairs = (unsigned long long)h->h_rb[6] | ((unsigned long long)h->h_rb[7] << 32);
-        }
-        npairs_pruned = (unsigned long long)h->h_rb[8] | ((unsigned long long)h->h_rb[9] << 32);
-        return MDX_OK;
-    };
-    MDX_TRY(read_counts());
-    if (speculative) {
-        if (flags[0] & 1u) { mdx_set_error("exclusion table overflow while building the pair list"); return MDX_EPARAM; }
-        if (flags[0] & (16u | 32u)) {
-            // a tile beyond the LDS buffers, or a list that outgrew the arrays: count + fill sizes them afresh
-            // (the role lists and the constraint remap above do not depend on the pair list and stand)
-            const uint32_t keep = flags[0] & ~(16u | 32u);
-            HIP_TRY(hipMemcpyAsync(d.flags_dev, &keep, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            speculative = false;
-            grow_for_regions = (flags[0] & 32u) != 0;
-            if (std::getenv("MDX_LIST_DEBUG")) fprintf(stderr, "[mdx] single-pass list build fell back: flags %u, T %u, E %u MC %u, cap_e %llu cap_m %u regions %u\n",
-                                                       flags[0], T, E, MC, (unsigned long long)h->cap_entries, h->cap_mchunks, a.n_regions);
-            MDX_TRY(two_pass());
-            launch_prune();
-            MDX_TRY(read_counts());
-        } else {
-            h->E = E; h->MC = MC;
-        }
-    }
-    if (prune && exact_prune) npairs = npairs_pruned;
-    if (flags[0] & 8u) { mdx_set_error("a constrained / virtual-site atom is missing from the local atom set"); return MDX_EPARAM; }
-    if (flags[0] & 3u) { mdx_set_error("exclusion table overflow while building the pair list"); return MDX_EPARAM; }
-    if (flags[0] & 4u) {
-        mdx_set_error("a bonded partner of an owned atom is missing from the local atom set (halo too thin)");
-        return MDX_EPARAM;
-    }
-
-    res.T = T;
-    }   // (the unfused chain)
+    // ---- what both chains leave to do ----
     const uint32_t T = h->T, S = h->S, NC = (T + 1) * MDX_CL_PER_TILE;
-    {
-        const TileOrderPlan plan = tile_order_plan(h, T);
-        if (!res.classified) {
-            h->tile_split = false; h->n_interior = 0;
-            if (plan.split) MDX_TRY(mdx_classify_tiles(h, plan.lpt));
-        }
-        if (!res.ordered) {
-            h->tile_lpt_on = false;
-            if (plan.lpt) MDX_TRY(mdx_order_tiles_by_length(h, plan.grouped));
-        }
+    const TileOrderPlan plan = tile_order_plan(h, T);
+    if (!res.classified) {
+        h->tile_split = false; h->n_interior = 0;
+        if (plan.split) MDX_TRY(mdx_classify_tiles(h, plan.lpt));
+    }
+    if (!res.ordered) {
+        h->tile_lpt_on = false;
+        if (plan.lpt) MDX_TRY(mdx_order_tiles_by_length(h, plan.grouped));
     }
     h->list_valid = true;
     h->forces_valid = false;
     h->rebuild_count++; h->steps_since_rebuild = 0;
     mdx_dd_note_rebuild(h);
-    // dual pair list: the step loop of a half-list run walks a rolling-pruned inner list.  What moves an atom inside
-    // the step loop feeds its path accumulator: the drift pass, SHAKE, and - for the ghosts of a decomposed handle - the
-    // halo unpack; a virtual site inside the triangle of its parents never moves further than they do (anything else
-    // keeps the plain list)
-    h->inner_skin = h->inner_skin_auto > 0.f ? h->inner_skin_auto : c_inner_skin(h->cfg);
-    h->dual_on = !h->dual_auto_off && mdx_nb_half(h) && prune && h->inner_skin > 0.f && h->inner_skin < h->cfg.skin &&
-                 (h->n_vsites == 0 || h->vsites_convex);
+    h->inner_skin = next_inner_skin(h);
+    h->dual_on = dual_list_wanted(h, h->inner_skin);
     h->prune_pending = !(res.inner_built && h->dual_on);      // (the fused chain's pruning pass has written the inner list of these positions)
     h->inner_from_rebuild = !h->prune_pending;
     if (h->inner_from_rebuild) ++h->inner_rebuilds;
@@ -2320,10 +2222,9 @@ int mdx_rebuild(mdx_handle* h) {
     h->tail_w = 0; h->tail_tiles = 0;
     if (h->dual_on && h->tile_lpt_on && h->tile_lpt_grouped && !h->alch_on) mdx_tail_plan(h, T, &h->tail_w, &h->tail_tiles);
     if (!d.inner_count) { ALLOC(d.inner_count, MDX_EPART + 8); HIP_TRY(hipMemsetAsync(d.inner_count, 0, sizeof(unsigned long long) * (MDX_EPART + 8), st)); }
-    uint64_t nmask = (uint64_t)MC * 8;
-    h->stats.n_atoms = N; h->stats.n_slots = S; h->stats.n_tiles = T; h->stats.n_clusters = NC;
-    h->stats.n_list_entries = E; h->stats.n_masked_entries = nmask;
-    h->stats.n_cluster_pairs = (mdx_nb_variant(h) >= 2) ? npairs : (uint64_t)E * 8;
+    h->stats.n_atoms = h->n_local; h->stats.n_slots = S; h->stats.n_tiles = T; h->stats.n_clusters = NC;
+    h->stats.n_list_entries = res.E; h->stats.n_masked_entries = (uint64_t)res.MC * 8;
+    h->stats.n_cluster_pairs = (mdx_nb_variant(h) >= 2) ? res.npairs : (uint64_t)res.E * 8;
     if (h->profile) {
         float ms = 0.f;
         HIP_TRY(hipEventRecord(e1, st)); HIP_TRY(hipEventSynchronize(e1));
@@ -2334,35 +2235,11 @@ int mdx_rebuild(mdx_handle* h) {
     return MDX_OK;
 }
 
-// ---- tiles by decreasing list length ------------------------------------------------------------------------------------
-// A launch of a few thousand tiles is 2-3 rounds of waves per SIMD; in spatial order the long lists (owned bricks, box
-// interior) and the short ones (halo shells, faces of a non-periodic system) come in runs, and the launch ends when the
-// last long list does.  Longest first is the classic list-scheduling order: the short lists fill the tail.  A counting
-// sort over the chunk count (129 buckets), one small launch per rebuild.
-// One workgroup, LDS histogram and cursors (atomics on a hundred global words would queue: a returning atomic on one address is
-// served every ~35 ns, tools/ubench/grid_barrier.hip - 70 us for the fullest bucket of a 9 k-tile launch).
-// is_int (may be null): the interior / boundary split of a decomposed handle - interior tiles first, each part by length.
-// group_tiles > 0 (large single-device systems): the order is by length INSIDE each of the eight contiguous tile ranges the pair
-// kernel hands to the eight XCDs (group_tiles tiles each), so a range stays on its XCD's L2 and still runs longest list first.
-__global__ __launch_bounds__(1024) void lpt_order_kernel(uint32_t T, const ListCounts* __restrict__ counts, const uint32_t* __restrict__ is_int,
-                                                         uint32_t* __restrict__ order, uint32_t group_tiles) {
-    constexpr uint32_t NB = 8 * LPT_BUCKETS;
-    __shared__ uint32_t s_hist[NB], s_cur[NB];
-    for (uint32_t b = threadIdx.x; b < NB; b += blockDim.x) s_hist[b] = 0;
-    __syncthreads();
-    auto bucket = [&](uint32_t t) {
-        const uint32_t nch = (counts[t].n_masked + counts[t].n_plain) >> 3;
-        const uint32_t major = group_tiles ? min(t / group_tiles, 7u) : ((is_int && !is_int[t]) ? 1u : 0u);
-        return major * LPT_BUCKETS + LPT_BUCKETS - 1u - min(nch, LPT_BUCKETS - 1u);   // bucket 0 = the longest lists
-    };
-    for (uint32_t t = threadIdx.x; t < T; t += blockDim.x) atomicAdd(&s_hist[bucket(t)], 1u);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (uint32_t b = 0; b < NB; ++b) { s_cur[b] = run; run += s_hist[b]; }
-    }
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < T; t += blockDim.x) order[atomicAdd(&s_cur[bucket(t)], 1u)] = t;
+// the counting sort above as a launch of its own: the unfused chain, and tile orders asked for outside a rebuild
+__global__ __launch_bounds__(SCAN1_THREADS) void lpt_order_kernel(uint32_t T, const ListCounts* __restrict__ counts, const uint32_t* __restrict__ is_int,
+                                                                  uint32_t* __restrict__ order, uint32_t group_tiles) {
+    __shared__ LptSortLds s_sort;
+    (void)lpt_counting_sort(T, counts, group_tiles, is_int, order, s_sort);
 }
 
 // ---- decomposed handle: interior / boundary tiles ---------------------------------------------------------------------
@@ -2410,7 +2287,7 @@ int mdx_classify_tiles(mdx_handle* h, bool by_length) {
     hipLaunchKernelGGL(tile_class_kernel, dim3(div_up(T, 4)), dim3(256), 0, st, T, d.slot_flags, d.list_counts, d.entry_off, d.entries,
                        d.tile_bnd);
     MDX_TRY(mdx_exclusive_scan_u32(h, d.tile_bnd, d.tile_scan, T + 1));
-    if (by_length) hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, st, T, d.list_counts, d.tile_bnd, d.tile_order, 0u);
+    if (by_length) hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(SCAN1_THREADS), 0, st, T, d.list_counts, d.tile_bnd, d.tile_order, 0u);
     else hipLaunchKernelGGL(tile_order_kernel, dim3(div_up(T, 256)), dim3(256), 0, st, T, d.tile_bnd, d.tile_scan, d.tile_order);
     uint32_t n_int = 0;
     HIP_TRY(hipMemcpyAsync(&n_int, d.tile_scan + T, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -2429,12 +2306,8 @@ int mdx_order_tiles_by_length(mdx_handle* h, bool grouped) {
         d.cap_tile_lpt = h->cap_tiles + 1;
         ALLOC(d.tile_lpt, d.cap_tile_lpt);
     }
-    uint32_t group_tiles = 0;
-    if (grouped) {      // the pair kernel's XCD ranges: ceil(workgroups / 8) workgroups of TPB tiles each (mdx_nonbonded.hip)
-        const uint32_t wpt = (uint32_t)mdx_nb_wpt_half(h, T), tpb = std::max(wpt, (uint32_t)MDX_NB_WAVES) / wpt;
-        group_tiles = (((T + tpb - 1) / tpb + 7) >> 3) * tpb;
-    }
-    hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(1024), 0, st, T, d.list_counts, (const uint32_t*)nullptr, d.tile_lpt, group_tiles);
+    const uint32_t group_tiles = grouped ? mdx_lpt_group_tiles(T, (uint32_t)mdx_nb_wpt_half(h, T)) : 0u;
+    hipLaunchKernelGGL(lpt_order_kernel, dim3(1), dim3(SCAN1_THREADS), 0, st, T, d.list_counts, (const uint32_t*)nullptr, d.tile_lpt, group_tiles);
     HIP_TRY(hipGetLastError());
     h->tile_lpt_on = true; h->tile_lpt_grouped = grouped;
     return MDX_OK;
@@ -2490,15 +2363,8 @@ int mdx_extract_neighbors(mdx_handle* h, uint32_t* offsets, uint32_t* idx) {
 // ghost sets stay as they are: a restraint role has no partner, so no atom has to join the halo.
 int mdx_refill_roles(mdx_handle* h) {
     if (!h->in_slot_space || !h->list_valid || !h->n_roles) return MDX_OK;      // (the next rebuild fills them)
-    DeviceState& d = h->d;
-    hipStream_t st = h->stream;
-    const uint32_t S = h->S;
-    hipLaunchKernelGGL(role_count_kernel, dim3(div_up(S + 1, 256)), dim3(256), 0, st, S, d.orig_of, d.gid,
-                       d.lflag, d.role_off_o, d.role_cnt_s);
-    MDX_TRY(mdx_exclusive_scan_u32(h, d.role_cnt_s, d.role_off_s, S + 1));
-    hipLaunchKernelGGL(role_fill_kernel, dim3(div_up(S, 256)), dim3(256), 0, st, S, d.orig_of, d.gid, d.lflag,
-                       d.slot_of, d.role_off_o, d.role_rec_o, d.role_off_s, d.role_rec_s, d.flags_dev, d.tri_o, d.tri_s);
+    MDX_TRY(roles_to_slots(h, h->S, true, true, nullptr));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MDX_OK;
 }

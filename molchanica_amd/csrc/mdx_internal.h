@@ -218,9 +218,8 @@ struct DeviceState {
     uint32_t* cell_of = nullptr;      // [N]
     uint32_t* cell_count = nullptr;   // [ncells+1]
     uint32_t* cell_start = nullptr;   // [ncells+1]
-    uint32_t* cell_cursor = nullptr;  // [ncells]
-    uint32_t* sorted_orig = nullptr;  // [N]
-    uint32_t* sorted_tmp = nullptr;   // [N] the cells' members as the atomic scatter left them, before the rank sort
+    uint32_t* sorted_orig = nullptr;  // [N] (first the atoms' arrival ranks in their cells: rb_prep_kernel)
+    uint32_t* sorted_tmp = nullptr;   // [N] the cells' members in arrival order, before the rank sort
     uint32_t* col_tiles = nullptr;    // [ncol+1]
     uint32_t* tile_start = nullptr;   // [ncol+1]
     uint32_t* tile_col = nullptr;     // [T]

@@ -15,7 +15,8 @@ stretch = None
 # STEP_TL_END_FRAC: search backwards from this fraction of the run (bench.py ends with profiled, unfused tails)
 for end in range(int((len(idx) - 1) * float(os.environ.get('STEP_TL_END_FRAC', '1.0'))), n_steps, -1):
     seg = rows[idx[end - n_steps]:idx[end]]
-    if not any(short(r[0]) in ("build_list_kernel", "bin_atoms_kernel", "kinetic_kernel", "rb_prep_kernel") for r in seg):
+    # (rb_prep_kernel opens a rebuild of either chain)
+    if not any(short(r[0]) in ("build_list_kernel", "kinetic_kernel", "rb_prep_kernel") for r in seg):
         stretch = (idx[end - n_steps], idx[end]); break
 a, b = stretch
 t0 = rows[a][1]
