@@ -291,6 +291,13 @@ uint64_t mdx_step_count(const mdx_handle* h);
  * (offsets[N] = total), then again with idx sized offsets[N]. */
 int mdx_neighbor_list(mdx_handle* h, uint32_t* offsets /* [N+1] */, uint32_t* idx /* or NULL */);
 
+/* Debugging read-out: the cluster-pair list of the current spatial caches, copied to the host word for word as the device holds
+ * it.  which: 0 the per-tile counts (n_masked, n_plain: 2 words per tile), 1 the tiles' entry offsets (tiles + 1 words), 2 the
+ * entries (2 words each: j-cluster, image code | i-cluster mask << 8) up to the furthest end of a tile's run, 3 the entries of the
+ * inner list over the same extent, 4 the inner list's chunk-loop bounds (8 words per tile), 5 slot -> atom (64 words per tile,
+ * 0xFFFFFFFF: a dummy).  *n_out: the number of 32-bit words (0: the handle has no such array); dst == NULL asks for it alone. */
+int mdx_debug_pair_lists(mdx_handle* h, int which, uint32_t* dst, uint64_t capacity, uint64_t* n_out);
+
 /* (enable 3, decomposed handles: every phase of the step in its production arrangement - see mdx_comm_diag) */
 /* HydrogenConstraint::{Flexible, Shake{shake_tolerance}, Linear{order, iter}} as the reference's UI hands it over
  * [ref: src/ui/panels/md.rs:362-371; LINCS_ORDER_DEFAULT, LINCS_ITER_DEFAULT, SHAKE_TOL_DEFAULT of the dynamics crate].

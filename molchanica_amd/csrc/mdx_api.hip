@@ -1757,6 +1757,37 @@ extern "C" int mdx_debug_half_stats(mdx_handle* h, unsigned long long out[6]) {
     return MDX_OK;
 }
 
+// The pair list as the device holds it (include/mdx.h), for tests that compare lists word for word.
+extern "C" int mdx_debug_pair_lists(mdx_handle* h, int which, uint32_t* dst, uint64_t capacity, uint64_t* n_out) {
+    if (!h || !n_out || which < 0 || which > 5) FAIL(MDX_EPARAM, "bad argument");
+    if (!h->in_slot_space || !h->d.list_counts || !h->d.entry_off) FAIL(MDX_EPARAM, "spatial caches not built");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const DeviceState& d = h->d;
+    const uint32_t T = h->T;
+    const void* src = nullptr;
+    uint64_t n = 0;
+    if (which == 0) { src = d.list_counts; n = 2ull * T; }
+    else if (which == 1) { src = d.entry_off; n = (uint64_t)T + 1; }
+    else if (which == 4) { src = d.inner_nch; n = d.inner_nch ? 8ull * T : 0; }
+    else if (which == 5) { src = d.orig_of; n = (uint64_t)T * MDX_TILE; }
+    else {
+        // the single-pass build cuts the entry array into regions: its extent is the furthest end of a tile's run
+        std::vector<ListCounts> cnt(T);
+        std::vector<uint32_t> off((size_t)T + 1);
+        if (T) HIP_TRY(hipMemcpy(cnt.data(), d.list_counts, sizeof(ListCounts) * T, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(off.data(), d.entry_off, sizeof(uint32_t) * ((size_t)T + 1), hipMemcpyDeviceToHost));
+        uint64_t ext = 0;
+        for (uint32_t t = 0; t < T; ++t) ext = std::max<uint64_t>(ext, (uint64_t)off[t] + cnt[t].n_masked + cnt[t].n_plain);
+        src = which == 2 ? d.entries : d.entries_in;
+        n = src ? 2 * ext : 0;
+    }
+    *n_out = n;
+    if (!dst) return MDX_OK;
+    if (capacity < n) FAIL(MDX_EPARAM, "capacity below the number of words");
+    if (n) HIP_TRY(hipMemcpy(dst, src, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
 // ---- position restraints (include/mdx.h) -----------------------------------------------------------------------------
 // One ROLE_POSRE record per restrained atom, last in its caller-order role list, and one parameter set per restraint behind the
 // force field's.  A new set rebuilds the caller-order tables from the ones on the device with the old restraint records taken out,

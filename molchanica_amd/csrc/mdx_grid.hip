@@ -953,9 +953,28 @@ __global__ __launch_bounds__(LB_WAVES * 64) void build_list_kernel(ListArgs a) {
 // inner_nch[8 t]).  The force call behind a rebuild then WALKS the inner list instead of being a pruning pass over the Verlet
 // list: 569 -> 418 us at 1 M atoms, for one more ballot per cluster pair here.  The quick accept is off in this flavour (every
 // surviving cluster pair needs its distances for the second test anyway).
+//
+// HITBITS (the default; MDX_PRUNE_HITBITS=0 runs the ballot body described so far, launch for launch): that body is bound by its scalar
+// half - a ballot, s_cmp, s_cselect, s_or and a branch on the outcome per cluster pair, 177 M scalar against 183 M vector instructions per
+// launch at 1 M atoms, on the one scalar unit four SIMDs share.  The kept set is "any lane: d2 < r2" per cluster pair and does not care when the 64
+// lanes' answers are combined: each lane keeps its own answers, one bit per tested cluster pair and radius, in vector registers,
+// and the wave ORs them together once per two entries (prune_or_wave).  Per tested cluster pair that leaves the distance, a
+// subtraction and a funnel shift per radius on the vector side and the wave-uniform skip of what the bounding boxes did not
+// let through on the scalar side; the inner-radius test no longer hangs on the outcome of the outer one.  The quick accept is
+// back for both radii (NTRY tries per cluster pair, lane = (ci, entry)): a pair sure inside the inner radius is sure at both and is
+// skipped, one sure only at the list radius still needs its lanes for the inner one.  Same kept set, same lists, bit for bit.
 struct PruneInner { uint2* entries_in; uint32_t* inner_nch; float rin2; WptRule rule; };
-template <bool INNER>
-__global__ __launch_bounds__(256) void prune_list_kernel(uint32_t T, float r2, float shx, float shy, float shz,
+// OR over the 64 lanes of a wave, wave-uniform: four DPP steps inside each row of 16, then the four rows' values
+__device__ __forceinline__ uint32_t prune_or_wave(uint32_t v) {
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);       // quad_perm [1, 0, 3, 2]
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);       // quad_perm [2, 3, 0, 1]
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);      // row_half_mirror
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);      // row_mirror
+    return __builtin_amdgcn_readlane(v, 0) | __builtin_amdgcn_readlane(v, 16) | __builtin_amdgcn_readlane(v, 32) |
+           __builtin_amdgcn_readlane(v, 48);
+}
+template <bool INNER, int NTRY, bool HITBITS>
+__device__ __forceinline__ void prune_list_body(uint32_t T, float r2, float shx, float shy, float shz,
                                                          const float4* __restrict__ posq, ListCounts* __restrict__ counts,
                                                          const uint32_t* __restrict__ entry_off, uint2* __restrict__ entries,
                                                          uint32_t null_cluster, unsigned long long* __restrict__ pair_count,
@@ -989,11 +1008,16 @@ __global__ __launch_bounds__(256) void prune_list_kernel(uint32_t T, float r2, f
     // cluster pair.  What the try leaves open gets the exact test - the kept set is the same either way.  (The counters
     // say the pass is bound by VALU + SALU issue - 108 M + 107 M instructions per launch, the scalar half being the
     // ballot / branch bookkeeping per cluster pair - so more tries cost what they save.)
-    constexpr int NTRY = INNER ? 0 : PRUNE_TRIES;
     constexpr int TI[6] = {0, 7, 3, 0, 7, 4}, TJ[6] = {0, 7, 4, 7, 0, 3};
-    float4 rep[NTRY ? NTRY : 1];
+    // (HITBITS: the tries' i-atoms wait in LDS, not in registers - the hit-bit body has none to spare at eight waves per SIMD)
+    __shared__ float4 s_i[HITBITS && NTRY ? 4 : 1][HITBITS && NTRY ? 64 : 1];
+    float4 rep[!HITBITS && NTRY ? NTRY : 1];
+    if constexpr (HITBITS && NTRY > 0) {
+        s_i[wave][lane] = posq[(size_t)t * MDX_TILE + lane];
+    } else {
 #pragma unroll
-    for (int k = 0; k < NTRY; ++k) rep[k] = posq[(size_t)t * MDX_TILE + (lane & 7) * MDX_CLUSTER + TI[k]];
+        for (int k = 0; k < NTRY; ++k) rep[k] = posq[(size_t)t * MDX_TILE + (lane & 7) * MDX_CLUSTER + TI[k]];
+    }
     // interaction kinds (cl_kind, null: every cluster pair may interact): which i-clusters hold an atom with a Lennard-Jones
     // well / a charged atom.  A cluster pair with no kind in common - oxygens of a four-site water against hydrogens and M sites -
     // has no force between any of its atoms and leaves the list whatever the distances say.
@@ -1006,6 +1030,7 @@ __global__ __launch_bounds__(256) void prune_list_kernel(uint32_t T, float r2, f
     const uint32_t e0 = entry_off[t], nmc = cnt.n_masked >> 3, nchunks = (cnt.n_masked + cnt.n_plain) >> 3;
     uint32_t kept = 0, wcur = 0;                   // wcur: plain entries written back so far
     uint32_t wcur_in = 0;                          // (INNER) ... and into the inner list
+    uint32_t kept_v = 0;                           // (HITBITS) kept cluster pairs, counted in the first lane of each entry
     // two-deep prefetch, as in the pair kernel: the entries of chunk c + 2 and the atoms of chunk c + 1 are in flight while
     // chunk c is tested (one-deep, the atom load waited for the entry load it depends on at the top of every chunk)
     uint2 ent_n = make_uint2(null_cluster, 13u), ent_nn = make_uint2(null_cluster, 13u);
@@ -1033,34 +1058,95 @@ __global__ __launch_bounds__(256) void prune_list_kernel(uint32_t T, float r2, f
         }
         const uint32_t y_in = newy;
         uint32_t newy_in = newy & 0xFFu;           // (INNER) this lane's entry word with the inner mask
-        unsigned long long acc = 0ull;             // bit e * 8 + ci: cluster pair (ci, e) has an atom pair inside r for sure
+        if constexpr (!HITBITS) {
+            unsigned long long acc = 0ull;             // bit e * 8 + ci: cluster pair (ci, e) has an atom pair inside r for sure
 #pragma unroll
-        for (int k = 0; k < NTRY; ++k) {
-            const float4 q = s_j[wave][(lane & ~7) + TJ[k]];
-            const float dx = rep[k].x - q.x, dy = rep[k].y - q.y, dz = rep[k].z - q.z;
-            acc |= __ballot(dx * dx + dy * dy + dz * dz < r2);
-        }
-#pragma unroll 2
-        for (int e = 0; e < 8; ++e) {
-            const float4 q = s_j[wave][e * 8 + jj];
-            const uint32_t y = __builtin_amdgcn_readlane(y_in, e * 8);
-            const uint32_t sure = (uint32_t)(acc >> (e * 8)) & 0xFFu;
-            uint32_t any = sure, anyin = 0u;
-            // only the i-clusters the bounding-box test let through (~5 of 8) and the quick accept left open
-            // (all eight, branch-free: 357 us per rebuild at 1 M atoms; this: 278 us)
-#pragma unroll
-            for (int ci = 0; ci < 8; ++ci) {
-                if (!(((y >> 8) & ~sure) & (1u << ci))) continue;
-                const float dx = xi[ci] - q.x, dy = yi[ci] - q.y, dz = zi[ci] - q.z;
-                const float d2 = dx * dx + dy * dy + dz * dz;
-                const bool hit = __ballot(d2 < r2) != 0ull;
-                any |= (hit ? 1u : 0u) << ci;
-                if (INNER && hit) anyin |= (__ballot(d2 < pin.rin2) != 0ull ? 1u : 0u) << ci;
+            for (int k = 0; k < NTRY; ++k) {
+                const float4 q = s_j[wave][(lane & ~7) + TJ[k]];
+                const float dx = rep[k].x - q.x, dy = rep[k].y - q.y, dz = rep[k].z - q.z;
+                acc |= __ballot(dx * dx + dy * dy + dz * dz < r2);
             }
-            const uint32_t im = (y >> 8) & any;
-            kept += __popc(im & 0xFFu);
-            if ((lane >> 3) == e) newy = (y & 0xFFu) | ((im & 0xFFu) << 8);
-            if (INNER && (lane >> 3) == e) newy_in = (y & 0xFFu) | ((((y >> 8) & anyin) & 0xFFu) << 8);
+#pragma unroll 2
+            for (int e = 0; e < 8; ++e) {
+                const float4 q = s_j[wave][e * 8 + jj];
+                const uint32_t y = __builtin_amdgcn_readlane(y_in, e * 8);
+                const uint32_t sure = (uint32_t)(acc >> (e * 8)) & 0xFFu;
+                uint32_t any = sure, anyin = 0u;
+                // only the i-clusters the bounding-box test let through (~5 of 8) and the quick accept left open
+                // (all eight, branch-free: 357 us per rebuild at 1 M atoms; this: 278 us)
+#pragma unroll
+                for (int ci = 0; ci < 8; ++ci) {
+                    if (!(((y >> 8) & ~sure) & (1u << ci))) continue;
+                    const float dx = xi[ci] - q.x, dy = yi[ci] - q.y, dz = zi[ci] - q.z;
+                    const float d2 = dx * dx + dy * dy + dz * dz;
+                    const bool hit = __ballot(d2 < r2) != 0ull;
+                    any |= (hit ? 1u : 0u) << ci;
+                    if (INNER && hit) anyin |= (__ballot(d2 < pin.rin2) != 0ull ? 1u : 0u) << ci;
+                }
+                const uint32_t im = (y >> 8) & any;
+                kept += __popc(im & 0xFFu);
+                if ((lane >> 3) == e) newy = (y & 0xFFu) | ((im & 0xFFu) << 8);
+                if (INNER && (lane >> 3) == e) newy_in = (y & 0xFFu) | ((((y >> 8) & anyin) & 0xFFu) << 8);
+            }
+        } else {
+            // quick accept: this lane's cluster pair is (i-cluster lane & 7, entry lane >> 3)
+            unsigned long long sure_r = 0ull, sure_in = 0ull;      // bit e * 8 + ci: an atom pair inside r / inside rin for sure
+            if constexpr (NTRY > 0) {
+                bool s_r = false, s_in = false;
+#pragma unroll
+                for (int k = 0; k < NTRY; ++k) {
+                    const float4 q = s_j[wave][(lane & ~7) + TJ[k]], p = s_i[wave][(lane & 7) * MDX_CLUSTER + TI[k]];
+                    const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+                    const float d2 = dx * dx + dy * dy + dz * dz;
+                    s_r |= d2 < r2;
+                    if (INNER) s_in |= d2 < pin.rin2;
+                }
+                sure_r = __ballot(s_r);
+                if (INNER) sure_in = __ballot(s_in);
+            }
+            // This lane's hit bits of entries 2w and 2w + 1: the sign of d2 - r2 (set <=> d2 < r2: a difference of floats keeps its
+            // sign, and equal values give +0) is shifted into a word per radius, one v_alignbit per test, in the order the open cluster
+            // pairs come - no compare, no select, no constant per position.  The wave ORs the two words once per entry pair; row w
+            // of the wave (the lanes of entries 2w, 2w + 1) keeps them.
+            uint32_t mine = 0u;
+#pragma unroll 1
+            for (int w = 0; w < 4; ++w) {
+                uint32_t hr = 0u, hi = 0u;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int e = w * 2 + k;
+                    const float4 q = s_j[wave][e * 8 + jj];
+                    const uint32_t y = __builtin_amdgcn_readlane(y_in, e * 8);
+                    // only the i-clusters the bounding-box test let through (~5 of 8) and the quick accept left open
+                    const uint32_t open = (y >> 8) & ~(uint32_t)((INNER ? sure_in : sure_r) >> (e * 8)) & 0xFFu;
+#pragma unroll
+                    for (int ci = 0; ci < 8; ++ci) {
+                        if (!(open & (1u << ci))) continue;
+                        const float dx = xi[ci] - q.x, dy = yi[ci] - q.y, dz = zi[ci] - q.z;
+                        const float d2 = dx * dx + dy * dy + dz * dz;
+                        hr = __builtin_amdgcn_alignbit(hr, __float_as_uint(d2 - r2), 31);
+                        if (INNER) hi = __builtin_amdgcn_alignbit(hi, __float_as_uint(d2 - pin.rin2), 31);
+                    }
+                }
+                const uint32_t hb = prune_or_wave(INNER ? hr | (hi << 16) : hr);      // (at most 16 tests per entry pair)
+                if ((lane >> 4) == w) mine = hb;
+            }
+            // lane (ci = lane & 7, entry le = lane >> 3) finds its cluster pair's bit: the last test shifted in sits at bit 0, and
+            // behind this lane's came the open i-clusters above ci of its entry and, for the first entry of a pair, all of the second's
+            const int le = lane >> 3, lci = lane & 7;
+            const uint32_t open_me = (y_in >> 8) & ~(uint32_t)((INNER ? sure_in : sure_r) >> (le * 8)) & 0xFFu;
+            const uint32_t open_next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)open_me, 0x128, 0xF, 0xF, true);      // row_ror:8 = lane ^ 8
+            const uint32_t at = __popc(open_me >> (lci + 1)) + ((le & 1) ? 0u : __popc(open_next));
+            const bool tested = (open_me >> lci) & 1u;
+            const unsigned long long hit_r = __ballot(tested && ((mine >> at) & 1u)) | sure_r;      // bit e * 8 + ci
+            const unsigned long long hit_in = INNER ? __ballot(tested && ((mine >> (16 + at)) & 1u)) | sure_in : 0ull;
+            const uint32_t any = (uint32_t)(hit_r >> (le * 8)) & 0xFFu;
+            uint32_t anyin = (uint32_t)(hit_in >> (le * 8)) & 0xFFu;
+            anyin &= any;                              // (an inner hit counts where the list radius hit, as in the ballot body)
+            const uint32_t im = (y_in >> 8) & any & 0xFFu;
+            newy = (y_in & 0xFFu) | (im << 8);
+            if (INNER) newy_in = (y_in & 0xFFu) | (((y_in >> 8) & anyin & 0xFFu) << 8);
+            kept_v += (lane & 7) == 0 ? __popc(im) : 0u;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier();
         ghost_hit |= ((newy >> 8) & 0xFFu) != 0u && ent.x >= first_ghost_cluster && ent.x < null_cluster;
@@ -1095,11 +1181,33 @@ __global__ __launch_bounds__(256) void prune_list_kernel(uint32_t T, float r2, f
         if (lane < 8) pin.inner_nch[(size_t)t * 8 + lane] = nmc + (nin_pad >> 3);
     }
     const bool any_ghost = __any(ghost_hit);
+    if constexpr (HITBITS) {
+#pragma unroll
+        for (int k = 32; k > 0; k >>= 1) kept_v += __shfl_xor(kept_v, k);
+        kept = kept_v;
+    }
     if (lane == 0) {
         counts[t].n_plain = np_pad;
         if (kept) atomicAdd(pc_slot(pair_count, t, 1), (unsigned long long)kept);
         if (tile_int) tile_int[t] = (!any_ghost && t * MDX_CL_PER_TILE < first_ghost_cluster) ? 1u : 0u;
     }
+}
+
+#define PRUNE_LIST_PARAMS                                                                                                            \
+    uint32_t T, float r2, float shx, float shy, float shz, const float4* __restrict__ posq, ListCounts* __restrict__ counts,         \
+    const uint32_t* __restrict__ entry_off, uint2* __restrict__ entries, uint32_t null_cluster,                                      \
+    unsigned long long* __restrict__ pair_count, const uint32_t* __restrict__ rb_ctl, uint32_t* __restrict__ tile_int,                 \
+    const uint8_t* __restrict__ cl_kind, PruneInner pin
+#define PRUNE_LIST_ARGS T, r2, shx, shy, shz, posq, counts, entry_off, entries, null_cluster, pair_count, rb_ctl, tile_int, cl_kind, pin
+// the ballot pass (MDX_PRUNE_HITBITS=0)
+template <bool INNER>
+__global__ __launch_bounds__(256) void prune_list_kernel(PRUNE_LIST_PARAMS) {
+    prune_list_body<INNER, INNER ? 0 : PRUNE_TRIES, false>(PRUNE_LIST_ARGS);
+}
+// the hit-bit pass with NTRY quick-accept tries, held to the eight waves per SIMD of the ballot pass
+template <bool INNER, int NTRY>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void prune_list_hb_kernel(PRUNE_LIST_PARAMS) {
+    prune_list_body<INNER, NTRY, true>(PRUNE_LIST_ARGS);
 }
 
 // The same pass for systems of a few hundred tiles, W waves per tile: one wave per tile leaves such a launch at the
@@ -1757,7 +1865,11 @@ struct RebuildKnobs {
     int inner_mode;        // MDX_REBUILD_INNER: the inner list out of the fused chain's pruning pass - 0 never, 1 flexible systems, 2 always
     uint32_t mw_below;     // MDX_PRUNE_MW_BELOW: the fused chain prunes with eight waves per tile below this many tiles
     bool list_debug;       // MDX_LIST_DEBUG: say on stderr why a single-pass build fell back
+    bool prune_hitbits;    // MDX_PRUNE_HITBITS=0: the one-wave pruning pass combines the lanes' answers per cluster pair (ballots), as it did
+    int prune_tries[2];    // MDX_PRUNE_TRIES / MDX_PRUNE_TRIES_INNER (0 .. 3): quick-accept tries of prune_list_kernel<false / true> with hit bits
 };
+// quick-accept tries per cluster pair of the hit-bit pass, [0] without and [1] with the inner list (profiles/prune_hitbits_ab.txt)
+constexpr int PRUNE_HB_TRIES[2] = {1, 1};
 // One wave per tile is a launch as long as its longest list: one rank of 8 of the 1 M-atom box - 3.3 k tiles, the owned ones with
 // ~150 chunks - took 233 us where the whole box, five times the work, takes 256.  Eight waves per tile below these tile counts: the
 // fused chain's was measured on decomposed handles, the unfused chain keeps the value it was first given (a few hundred tiles: one
@@ -1775,6 +1887,9 @@ static const RebuildKnobs& rebuild_knobs() {
         const char* const mw = std::getenv("MDX_PRUNE_MW_BELOW");
         r.mw_below = mw ? (uint32_t)std::atoi(mw) : PRUNE_MW_BELOW_FUSED;
         r.list_debug = std::getenv("MDX_LIST_DEBUG") != nullptr;
+        r.prune_hitbits = env("MDX_PRUNE_HITBITS")[0] != '0';
+        const char* const tr[2] = {std::getenv("MDX_PRUNE_TRIES"), std::getenv("MDX_PRUNE_TRIES_INNER")};
+        for (int k = 0; k < 2; ++k) r.prune_tries[k] = tr[k] ? std::min(std::max(std::atoi(tr[k]), 0), 3) : PRUNE_HB_TRIES[k];
         return r;
     }();
     return k;
@@ -1908,12 +2023,19 @@ static bool launch_exact_prune(mdx_handle* h, const ListArgs& a, uint32_t mw_bel
     if (a.T < mw_below)
         hipLaunchKernelGGL(prune_list_mw_kernel<8>, dim3(a.T), dim3(512), 0, st, a.T, r2, shx, shy, shz, d.posq, d.list_counts,
                            d.entry_off, d.entries, a.null_cluster, d.pair_count, rb_ctl, tint, kinds);
-    else if (inner)
-        hipLaunchKernelGGL(prune_list_kernel<true>, one_wave_grid, dim3(256), 0, st, a.T, r2, shx, shy, shz,
-                           d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, rb_ctl, tint, kinds, *inner);
-    else
-        hipLaunchKernelGGL(prune_list_kernel<false>, one_wave_grid, dim3(256), 0, st, a.T, r2, shx, shy, shz,
-                           d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, rb_ctl, tint, kinds, PruneInner{});
+    else {
+        using PruneFn = void (*)(uint32_t, float, float, float, float, const float4*, ListCounts*, const uint32_t*, uint2*, uint32_t,
+                                 unsigned long long*, const uint32_t*, uint32_t*, const uint8_t*, PruneInner);
+        static const PruneFn hitbits[2][4] = {
+            {prune_list_hb_kernel<false, 0>, prune_list_hb_kernel<false, 1>, prune_list_hb_kernel<false, 2>, prune_list_hb_kernel<false, 3>},
+            {prune_list_hb_kernel<true, 0>, prune_list_hb_kernel<true, 1>, prune_list_hb_kernel<true, 2>, prune_list_hb_kernel<true, 3>}};
+        static const PruneFn ballots[2] = {prune_list_kernel<false>, prune_list_kernel<true>};
+        const RebuildKnobs& knobs = rebuild_knobs();
+        const int fl = inner ? 1 : 0;
+        hipLaunchKernelGGL(knobs.prune_hitbits ? hitbits[fl][knobs.prune_tries[fl]] : ballots[fl], one_wave_grid, dim3(256), 0, st, a.T, r2,
+                           shx, shy, shz, d.posq, d.list_counts, d.entry_off, d.entries, a.null_cluster, d.pair_count, rb_ctl, tint, kinds,
+                           inner ? *inner : PruneInner{});
+    }
     return inner && a.T >= mw_below;
 }
 

@@ -82,6 +82,7 @@ def load_library():
     lib.mdx_step_count.argtypes = [H]
     lib.mdx_step_count.restype = C.c_uint64
     lib.mdx_neighbor_list.argtypes = [H, _u32p, _u32p]
+    lib.mdx_debug_pair_lists.argtypes = [H, C.c_int, _u32p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.mdx_profile.argtypes = [H, C.c_int]
     lib.mdx_get_stats.argtypes = [H, C.POINTER(CStats)]
     lib.mdx_get_skin.argtypes = [H, _fp, C.POINTER(C.c_int)]
@@ -604,6 +605,24 @@ class MdState:
         idx = np.zeros(max(int(off[-1]), 1), dtype=np.uint32)
         _check(lib.mdx_neighbor_list(self._h, off.ctypes.data_as(_u32p), idx.ctypes.data_as(_u32p)))
         return off, idx[: int(off[-1])]
+
+    PAIR_LIST_ARRAYS = ("counts", "entry_off", "entries", "entries_in", "inner_nch", "orig_of")
+
+    def debug_pair_lists(self):
+        """-> the cluster-pair list as the device holds it (mdx_debug_pair_lists): uint32 arrays by name, `counts` [T, 2],
+        `entries` / `entries_in` [E, 2], `inner_nch` [T, 8], `orig_of` [T, 64]; an array the handle does not have is empty."""
+        lib = load_library()
+        out = {}
+        for which, name in enumerate(self.PAIR_LIST_ARRAYS):
+            n = C.c_uint64(0)
+            _check(lib.mdx_debug_pair_lists(self._h, which, None, 0, C.byref(n)))
+            a = np.zeros(int(n.value), dtype=np.uint32)
+            if a.size:
+                _check(lib.mdx_debug_pair_lists(self._h, which, a.ctypes.data_as(_u32p), a.size, C.byref(n)))
+            out[name] = a
+        for name, w in (("counts", 2), ("entries", 2), ("entries_in", 2), ("inner_nch", 8), ("orig_of", 64)):
+            out[name] = out[name].reshape(-1, w)
+        return out
 
     # -- callers either side of step (SURVEY §8f) -------------------------------------------------
     def minimize_energy(self, max_iters: int, external_forces=None, f_tol: float = 0.0):
