@@ -573,6 +573,42 @@ int      mdx_single_point_between_mols(const mdx_system* sys, const mdx_config* 
 int      mdx_score_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_poses,
                          const float* poses /* [n_poses][count][3] */, float* out /* [n_poses][n_groups] */, uint32_t n_groups);
 
+/* ---- a library of GUEST ligands against the resident atoms (screening: one receptor, many candidates) -----------------------------
+ * A guest ligand is described by the caller and never enters the handle: the handle holds the receptor and its solvent and is built
+ * once; every ligand of the library comes with its own parameters, its own pair lists and its own poses.  Rows of all ligands follow
+ * each other in library order, ligand m's n_poses rows together.  The row of pose p of ligand m is what mdx_score_poses returns on a
+ * second handle that holds the same atoms at the same positions plus ligand m appended as one more energy group L:
+ *   - columns 0 .. n_groups-1 are M[L][b] against the resident groups - EVERY resident atom is environment, no group is skipped;
+ *   - column n_groups is the intra-ligand element M[L][L]: the plain pairs (in neither list) once each plus the scaled 1-4 pairs;
+ *   - same cutoffs, real-space Coulomb treatment, combining rule and minimum image per pair as mdx_score_poses; no SPME mesh term.
+ * excl_pairs do not interact (1-2, 1-3).  pairs14 are taken out of the plain pairs and evaluated from records made as a resident
+ * atom's: sigma_ij by the combining rule, 4 scale14_lj eps_ij, scale14_coulomb coulomb_k q_i q_j; left out under
+ * MDX_OVR_BONDED_DISABLED.  MDX_OVR_LJ_DISABLED / MDX_OVR_COULOMB_DISABLED zero the guest's eps / charge as mdx_create does a resident
+ * atom's.  Pair order inside a pair and repeats inside one list do not matter for excl_pairs; a 1-4 pair listed twice counts twice.
+ * The handle is not changed (positions, lists, caches, snapshots, the table mdx_score_poses keeps for its resident range): a handle
+ * that screened continues bit for bit like one that did not.  A (ligand, pose) gives the same bits alone, in a library of any size
+ * and order, at any place in it.
+ * best_pose_or_null[m] / best_score_or_null[m]: with S = the sum over the columns, in column order, of (double) of the fp32 row, the
+ * ligand-local index of the pose with the smallest S (the lowest index on a tie) and that S, picked on the device; 0xFFFFFFFF and
+ * +infinity for a ligand with n_poses == 0.
+ * MDX_EPARAM (mdx_last_error names the ligand and the reason; all outputs are left untouched): no groups set or n_groups is not the
+ * group count; a needed pointer is NULL; count == 0 or count > MDX_POSE_MAX_ATOMS; a pair index >= count or a pair of an atom with
+ * itself; a pair in both lists; a coordinate, charge, sigma or eps that is not finite, or a negative sigma or eps; an alchemical
+ * window is active; the handle is decomposed.  MDX_ENAN: a non-finite row (atoms on top of each other).  n_ligands == 0, or a library
+ * without a single pose, succeeds and does nothing. */
+typedef struct mdx_guest_ligand {
+    uint32_t count;                 /* atoms, 1..MDX_POSE_MAX_ATOMS */
+    const float* charge;            /* [count] e */
+    const float* lj_sigma;          /* [count] A, per atom */
+    const float* lj_eps;            /* [count] kcal/mol, per atom */
+    uint32_t n_excl;  const uint32_t* excl_pairs;   /* [n_excl][2] ligand-local, a != b: no interaction (1-2, 1-3) */
+    uint32_t n_pairs14; const uint32_t* pairs14;    /* [n_pairs14][2] ligand-local: out of the plain pairs, evaluated scaled */
+    uint32_t n_poses; const float* poses;           /* [n_poses][count][3] A, each one whole molecule; n_poses may be 0 */
+} mdx_guest_ligand;
+int      mdx_screen_ligands(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs,
+                            float* rows /* [sum n_poses][n_groups + 1] */, uint32_t n_groups,
+                            uint32_t* best_pose_or_null /* [n_ligands] */, double* best_score_or_null /* [n_ligands] */);
+
 /* ---- the same batch with gradients: per-atom forces, net force and torque per pose (what a local pose refinement follows) -------
  * Preconditions, refusals and the treatment of the handle are exactly those of mdx_score_poses; forces == NULL is MDX_EPARAM too, and
  * a refused call leaves all three output buffers untouched.  With S_p = the sum over b of the row mdx_score_poses returns for pose p,

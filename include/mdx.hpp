@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -168,6 +169,20 @@ public:
         const uint32_t n = (uint32_t)(poses.size() / (3 * (size_t)count));
         std::vector<float> out((size_t)n * g);
         check(mdx_score_poses(h_, first, count, n, poses.data(), out.data(), g));
+        return out;
+    }
+    /// mdx_screen_ligands: rows [sum n_poses][n_groups + 1] of a library of guest ligands against the resident atoms (the last column
+    /// is the ligand's own pairs); best_pose / best_score (if not null) receive per ligand the pose with the smallest row sum and that sum.
+    std::vector<float> screen_ligands(const std::vector<mdx_guest_ligand>& ligs, std::vector<uint32_t>* best_pose = nullptr,
+                                      std::vector<double>* best_score = nullptr) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        size_t n = 0;
+        for (const mdx_guest_ligand& l : ligs) n += l.n_poses;
+        std::vector<float> out(n * ((size_t)g + 1));
+        if (best_pose) best_pose->assign(ligs.size(), 0xFFFFFFFFu);
+        if (best_score) best_score->assign(ligs.size(), std::numeric_limits<double>::infinity());
+        check(mdx_screen_ligands(h_, (uint32_t)ligs.size(), ligs.data(), out.data(), g, best_pose ? best_pose->data() : nullptr,
+                                 best_score ? best_score->data() : nullptr));
         return out;
     }
     /// mdx_pose_forces: forces [n_poses][count][3] kcal/mol/A on the atoms of every pose (minus the gradient of the sum of its row);

@@ -96,6 +96,17 @@ class CSearchOpts(C.Structure):
                 ("seed", C.c_uint64), ("refine", CFlexOpts)]
 
 
+class CGuestLigand(C.Structure):
+    """mdx_guest_ligand"""
+    _fields_ = [("count", C.c_uint32), ("charge", _fp), ("lj_sigma", _fp), ("lj_eps", _fp),
+                ("n_excl", C.c_uint32), ("excl_pairs", _u32p), ("n_pairs14", C.c_uint32), ("pairs14", _u32p),
+                ("n_poses", C.c_uint32), ("poses", _fp)]
+
+
+# mdx_screen_ligands(h, n_ligands, ligs, rows, n_groups, best_pose_or_null, best_score_or_null)
+SCREEN_LIGANDS_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), _fp, C.c_uint32, _u32p, C.POINTER(C.c_double)]
+
+
 class CEnergies(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "kinetic", "potential", "potential_nonbonded", "potential_bonded",
@@ -358,3 +369,50 @@ class MdSystem:
         s.n_vsites = int(self.vsite_idx.shape[0])
         s.vsite_idx, s.vsite_w = p(self.vsite_idx, _u32p), p(self.vsite_w, _fp)
         return s
+
+
+@dataclass
+class GuestLigand:
+    """A ligand `MdState.screen_ligands` scores without it being part of the handle (`mdx_guest_ligand`): per-atom parameters, its own
+    pair lists in ligand-local indices and its poses.  excl_pairs do not interact (1-2, 1-3); pairs14 are evaluated scaled."""
+    charge: np.ndarray                    # [count] e
+    lj_sigma: np.ndarray                  # [count] A, per atom
+    lj_eps: np.ndarray                    # [count] kcal/mol, per atom
+    excl_pairs: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.uint32))
+    pairs14: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.uint32))
+    poses: np.ndarray | None = None       # [P, count, 3] A, each one whole molecule; None: no poses
+
+    @property
+    def count(self) -> int:
+        return int(np.asarray(self.charge).reshape(-1).shape[0])
+
+    @property
+    def n_poses(self) -> int:
+        return 0 if self.poses is None else int(np.asarray(self.poses).reshape(-1, max(self.count, 1), 3).shape[0])
+
+    def with_poses(self, poses) -> "GuestLigand":
+        """The same ligand (arrays shared) with other poses."""
+        return GuestLigand(self.charge, self.lj_sigma, self.lj_eps, self.excl_pairs, self.pairs14, poses)
+
+    @classmethod
+    def from_system(cls, sys: MdSystem, lo: int, hi: int, poses=None) -> "GuestLigand":
+        """The molecule [lo, hi) of an MdSystem as a guest: sigma and eps per atom through lj_type, the exclusion CSR as pairs (a < b,
+        each once; a pair that is also a 1-4 pair belongs to pairs14 alone, as mdx_create classes it), indices made local.  Raises
+        ValueError when a pair links the range to an atom outside it."""
+        sys.normalise()
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= sys.n_atoms:
+            raise ValueError("GuestLigand.from_system: atom range out of bounds")
+        from .topology import pairs_from_csr      # (topology imports this module)
+        t = sys.lj_type[lo:hi].astype(np.int64)
+        ex = pairs_from_csr(sys.excl_offsets, sys.excl_idx, lo, hi)
+        p14 = sys.pairs14_idx.astype(np.int64).reshape(-1, 2)
+        inside14 = (p14 >= lo) & (p14 < hi)
+        if (ex < lo).any() or (ex >= hi).any() or (inside14[:, 0] != inside14[:, 1]).any():
+            raise ValueError("GuestLigand.from_system: an exclusion or 1-4 pair links the range to an atom outside it")
+        p14 = np.unique(np.sort(p14[inside14[:, 0]] - lo, axis=1), axis=0).reshape(-1, 2)
+        ex = ex - lo
+        n = hi - lo
+        ex = ex[~np.isin(ex[:, 0] * n + ex[:, 1], p14[:, 0] * n + p14[:, 1])]
+        return cls(charge=sys.charge[lo:hi].copy(), lj_sigma=sys.lj_sigma[t].astype(np.float32), lj_eps=sys.lj_eps[t].astype(np.float32),
+                   excl_pairs=ex.astype(np.uint32), pairs14=p14.astype(np.uint32), poses=poses)

@@ -172,7 +172,7 @@ static void free_device(mdx_handle* h) {
                     d.role_off_s, d.role_rec_s, d.role_prm, d.tri_o, d.tri_s, d.tri_shape, d.ctl, d.energy,
                     d.flags_dev, d.bonded_part, d.bbox_red, d.pair_count, d.inner_count, d.pme_force, d.wstep_s, d.path, d.dprune, d.force_b, d.force_c, d.cons_o, d.cons_s, d.cons_tmp, d.cons_mask, d.cons_cnt, d.cons_off, d.cons_vir, d.vsite_o, d.vsite_s, d.gsite_o, d.gsite_s, d.gsite_tmp, d.pme_q, d.pme_f,
                     d.pme_theta, d.pme_q2, d.pme_f2, d.scratch4, d.tile_bnd, d.tile_scan, d.tile_order, d.tile_lpt, d.rb_ctl, d.scan_chain, d.grp, d.grp_mat, d.fl_hot, d.fl_slab, d.star_o, d.star_s, d.ewald_tab,
-                    d.ps_cls, d.ps_p14, d.ps_stage, d.ps_slab, d.ps_rows, d.ps_fslab, d.ps_fout, d.ps_rigid, d.ps_flex, d.ps_flex_tab, d.ps_search, d.ps_cl, d.ps_cl_mat};
+                    d.ps_cls, d.ps_p14, d.ps_stage, d.ps_slab, d.ps_rows, d.ps_fslab, d.ps_fout, d.ps_rigid, d.ps_flex, d.ps_flex_tab, d.ps_search, d.ps_cl, d.ps_cl_mat, d.gs_blk, d.gs_best};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     d = DeviceState{};
 }
@@ -242,7 +242,7 @@ static int create_impl(const mdx_system* s, const mdx_config* c, int device, mdx
         q[i] = (nb_off || coul_off) ? 0.f : s->charge[i];
         qs[i] = q[i] * sqrt_ke;
         const float ep_eff = (nb_off || lj_off) ? 0.f : ep;
-        lj[i] = make_float2(geom ? std::sqrt(sg) : 0.5f * sg, std::sqrt(24.0f * ep_eff));
+        lj[i] = mdx_pack_lj(geom, sg, ep_eff);
         ljraw[i] = make_float2(sg, ep_eff);
         mass[i] = s->mass[i];
         invm[i] = fixed ? 0.f : MDX_ACC_CONV / s->mass[i];
@@ -355,11 +355,8 @@ static int create_impl(const mdx_system* s, const mdx_config* c, int device, mdx
         }
         for (uint32_t k = 0; k < s->n_pairs14; ++k) {
             const uint32_t a = s->pairs14_idx[2 * k], b = s->pairs14_idx[2 * k + 1];
-            const float sa = ljraw[a].x, sb = ljraw[b].x;
-            const float sig = geom ? std::sqrt(sa * sb) : 0.5f * (sa + sb);
-            const float eps = std::sqrt(ljraw[a].y * ljraw[b].y);
-            add_term(s->pairs14_idx + 2 * k, 2, ROLE_PAIR14, sig, 4.0f * c->scale14_lj * eps,
-                     c->scale14_coulomb * c->coulomb_k * q[a] * q[b]);
+            const float4 p = mdx_pair14_params(*c, ljraw[a], ljraw[b], q[a], q[b]);
+            add_term(s->pairs14_idx + 2 * k, 2, ROLE_PAIR14, p.x, p.y, p.z);
         }
         if (pme_on)
             for (uint32_t i = 0; i < N; ++i)

@@ -299,6 +299,9 @@ struct DeviceState {
     void* ps_search = nullptr;
     // mdx_pose_rmsd / mdx_cluster_poses (mdx_pose_cluster.hip): the block of one call (ClLayout) and the pair matrix - fp32 rmsd or bits
     void* ps_cl = nullptr; void* ps_cl_mat = nullptr;
+    // mdx_screen_ligands: the block of one chunk of guest poses (GuestLayout: records, guest tables, coordinates, slab, rows) and the
+    // best pose of every ligand carried across the chunks.  Nothing of the resident-pose buffers above is touched by a screening.
+    void* gs_blk = nullptr; void* gs_best = nullptr;
 };
 
 struct MdxDecomp;   // mdx_comm.h: the handle is one rank of a spatially decomposed box
@@ -369,6 +372,7 @@ struct mdx_handle {
     // mdx_refine_poses_flex: what ps_flex_tab was built for (with ps_first / ps_count / ps_epoch) and how many dihedral terms it holds
     bool fx_valid = false; uint32_t fx_first = 0, fx_count = 0, fx_root = 0, fx_flags = 0, fx_terms = 0; uint64_t fx_epoch = 0;
     std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0, ps_cap_search = 0, ps_cap_cl = 0, ps_cap_cl_mat = 0;
+    size_t gs_cap_blk = 0, gs_cap_best = 0;      // bytes of gs_blk / gs_best
     bool alch_on = false; double alch_lambda = 0.0; uint32_t alch_lo = 0, alch_hi = 0;
     float sc_alpha = 0.5f, sc_sigma_min = 3.0f;   // soft core of the alchemical window (mdx_set_alchemical_softcore)
     std::vector<double> foreign_lams;             // mdx_set_foreign_lambdas (survives window changes; empty: none)
@@ -655,6 +659,22 @@ static inline void mdx_refresh_uni_lj(mdx_handle* h) {
     const bool ok = !off && mdx_uniform_lj(reinterpret_cast<const float*>(h->h_lj.data()), h->h_lj.size(),
                                            h->cfg.combining_rule == MDX_COMBINE_GEOMETRIC, h->alch_on, &c);
     h->uni_lj = ok; h->uni_c = ok ? c : 0.f;
+}
+
+// An atom's packed LJ record as the pair kernels read it: (sqrt(sigma) under the geometric rule, sigma / 2 under Lorentz-Berthelot;
+// sqrt(24 eps)).  eps_eff is the atom's eps after the overrides.  mdx_create packs every resident atom with it, mdx_screen_ligands every
+// guest atom: one expression, one set of bits.
+static inline float2 mdx_pack_lj(bool geometric, float sigma, float eps_eff) {
+    return make_float2(geometric ? std::sqrt(sigma) : 0.5f * sigma, std::sqrt(24.0f * eps_eff));
+}
+// The record of a scaled 1-4 pair from its atoms' (sigma, eps_eff) and charges after the overrides: x = sigma_ij by the combining
+// rule, y = 4 scale14_lj eps_ij, z = scale14_coulomb k_e q_a q_b (mdx_create: the ROLE_PAIR14 parameter set; mdx_screen_ligands)
+static inline float4 mdx_pair14_params(const mdx_config& c, float2 raw_a, float2 raw_b, float qa, float qb) {
+    const bool geom = c.combining_rule == MDX_COMBINE_GEOMETRIC;
+    const float sa = raw_a.x, sb = raw_b.x;
+    const float sig = geom ? std::sqrt(sa * sb) : 0.5f * (sa + sb);
+    const float eps = std::sqrt(raw_a.y * raw_b.y);
+    return make_float4(sig, 4.0f * c.scale14_lj * eps, c.scale14_coulomb * c.coulomb_k * qa * qb, 0.f);
 }
 
 // constraints / virtual sites (mdx_constraints.hip)

@@ -53,6 +53,14 @@
 // round that ended - Metropolis on the refinement's objective, current and best pose in the walker's search record - and perturbs the
 // current pose into the staging buffer for the next; n_rounds x (1 + 2 max_evals) + 1 launches per chunk, one read-back, one wait.
 //
+// mdx_screen_ligands: the energy flavour for GUEST ligands - described by the caller, never entered into the handle (src/screening: one
+// receptor, a library of candidates).  The same kernel body under GUEST = true: PoseLigand<GUEST> is the one place the two ligand
+// sources differ - a resident ligand is a range of the handle's atoms, the same for every pose of the launch, with its rows behind
+// slot_of and its own pairs in the handle's table; a guest pose carries a PoseRec into the chunk's staged tables, so one launch holds
+// ligands of different sizes.  The environment walk, the strips, the fold, the own-pair loops and the slab are the resident ones; a
+// guest skips no group, and its slab rows have one more column for its own pairs.  guest_best_kernel picks the best pose per ligand
+// from the chunk's summed rows and carries it across chunks.
+//
 // What is written once: the unit-order sum of a slab (pose_units_sum: the four kernels that add the 17 units take it from there, which
 // is why rows_out / rigid_out of a refinement are the bits mdx_score_poses / mdx_pose_forces return), the stages of an evaluation
 // (step_gather, step_store, step_max_speed; centroid, rigid and inertia stand once in pose_step), the B(theta) loop
@@ -75,6 +83,10 @@
 
 struct Pose14 { uint32_t a, b; float sig, e4, qq; };      // ligand-local atoms; sigma_ij, 4 scale eps_ij, scale k_e q_i q_j
 
+// A guest pose (mdx_screen_ligands): where its ligand lies in the chunk's tables.  atom: first row of the charge / LJ tables; cls: first
+// byte of its class map [count^2]; p14, n14: its 1-4 records; xyz: first float of the pose's coordinates.
+struct PoseRec { uint32_t atom, count, cls, p14, n14, xyz; };
+
 struct PoseArgs {
     NbParams p;
     GridParams g;
@@ -89,6 +101,10 @@ struct PoseArgs {
     float box[3], inv_box[3];      // periodic axes (0: none)
     const uint8_t* cls; const Pose14* p14; uint32_t n14;
     const uint32_t* frozen;        // REFINE: [poses of the chunk], non-zero = the pose has finished, its workgroups return at once
+    // GUEST: the ligand is the caller's, not the handle's.  first / count / L are unused; cls and p14 are the chunk's tables, poses its
+    // coordinates, and the slab rows are G + 1 wide (column G: the ligand's own pairs)
+    const PoseRec* rec;            // [poses of the chunk]
+    const float* gq; const float2* glj;      // [ligand atoms of the chunk]: q sqrt(k_e), the packed LJ record (mdx_pack_lj)
 };
 
 __device__ __forceinline__ float pose_mimg(float d, float box, float inv) { return box > 0.f ? d - rintf(d * inv) * box : d; }
@@ -103,8 +119,44 @@ __device__ __forceinline__ void pose_fold(double& dacc, uint32_t key, double* ro
     dacc = 0.0;
 }
 
-template <int COUL, bool GEOM, bool FORCE, bool REFINE = false>
+// The ligand of a pose: its size, where its coordinates and its own-pair tables lie, its charge and LJ rows.  Resident (GUEST = false): a
+// range of the handle's atoms, the same for every pose of the launch, rows through slot_of.  GUEST: the pose's record - one launch
+// carries ligands of different sizes - and rows from the chunk's guest tables.  Every member but the rows is uniform over the
+// workgroup; the guest's come through readfirstlane so that count and the strip count stay in scalar registers, as `wave` does.
+template <bool GUEST>
+struct PoseLigand {
+    uint32_t count, n14, W;        // W: width of a slab row
+    const float* xyz; const uint8_t* cls; const Pose14* p14;
+    uint32_t atom;
+    __device__ __forceinline__ PoseLigand(const PoseArgs& a, uint32_t pose) {
+        if constexpr (GUEST) {
+            const PoseRec r = a.rec[pose];
+            count = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.count);
+            n14 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.n14);
+            atom = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.atom);
+            xyz = a.poses + (uint32_t)__builtin_amdgcn_readfirstlane((int)r.xyz);
+            cls = a.cls + (uint32_t)__builtin_amdgcn_readfirstlane((int)r.cls);
+            p14 = a.p14 + (uint32_t)__builtin_amdgcn_readfirstlane((int)r.p14);
+            W = a.G + 1u;
+        } else {
+            count = a.count; n14 = a.n14; atom = a.first; W = a.G;
+            xyz = a.poses + (size_t)pose * count * 3;
+            cls = a.cls; p14 = a.p14;
+        }
+    }
+    // charge (q sqrt(k_e)) and packed LJ record of ligand atom i
+    __device__ __forceinline__ void row(const PoseArgs& a, uint32_t i, float& q, float2& lj) const {
+        if constexpr (GUEST) { q = a.gq[atom + i]; lj = a.glj[atom + i]; }
+        else {
+            const uint32_t s = a.slot_of[atom + i];
+            if (s != MDX_INVALID) { q = a.posq[s].w; lj = a.lj[s]; }
+        }
+    }
+};
+
+template <int COUL, bool GEOM, bool FORCE, bool REFINE = false, bool GUEST = false>
 __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
+    static_assert(!GUEST || (!FORCE && !REFINE), "guest ligands: the energy flavour only");
     extern __shared__ double s_f[];      // FORCE: [4 waves][xyz][fstride] (nothing otherwise)
     if (REFINE && a.frozen[blockIdx.y] != 0u) return;      // (uniform over the workgroup, before any barrier)
     __shared__ float4 s_xyzq[MDX_POSE_MAX_ATOMS];
@@ -113,16 +165,16 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
     __shared__ float s_bb[4][6];
     const uint32_t tid = threadIdx.x, unit = blockIdx.x, pose = blockIdx.y;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t count = a.count;
+    const PoseLigand<GUEST> lig(a, pose);
+    const uint32_t count = lig.count;
 
     // ---- the pose: rows in LDS, bounding box ----
     float4 me = make_float4(0.f, 0.f, 0.f, 0.f); float2 mlj = make_float2(0.f, 0.f);
     float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
     if (tid < count) {
-        const uint32_t s = a.slot_of[a.first + tid];
-        const float* x = a.poses + ((size_t)pose * count + tid) * 3;
+        const float* x = lig.xyz + (size_t)tid * 3;
         me = make_float4(x[0], x[1], x[2], 0.f);
-        if (s != MDX_INVALID) { me.w = a.posq[s].w; mlj = a.lj[s]; }
+        lig.row(a, tid, me.w, mlj);
         lo[0] = hi[0] = me.x; lo[1] = hi[1] = me.y; lo[2] = hi[2] = me.z;
     }
     s_xyzq[tid] = me; s_lj[tid] = mlj;
@@ -141,7 +193,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
         lo[d] = fminf(fminf(s_bb[0][d], s_bb[1][d]), fminf(s_bb[2][d], s_bb[3][d]));
         hi[d] = fmaxf(fmaxf(s_bb[0][3 + d], s_bb[1][3 + d]), fmaxf(s_bb[2][3 + d], s_bb[3][3 + d]));
     }
-    double* out = a.slab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * a.G;
+    double* out = a.slab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * lig.W;
     const uint32_t fstride = ((count + 7u) >> 3) << 3;
     double* fout = FORCE ? a.fslab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * count * 3u : nullptr;
 
@@ -151,7 +203,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
         const uint32_t n2 = count * count;
         for (uint32_t i = tid; i < n2; i += 256u) {
             const uint32_t ia = i / count, ib = i - ia * count;
-            if (ia >= ib || a.cls[i] != 0) continue;
+            if (ia >= ib || lig.cls[i] != 0) continue;
             const float4 pa = s_xyzq[ia], pb = s_xyzq[ib];
             const float2 la = s_lj[ia];
             const float dx = pose_mimg(pa.x - pb.x, a.box[0], a.inv_box[0]), dy = pose_mimg(pa.y - pb.y, a.box[1], a.inv_box[1]),
@@ -161,8 +213,8 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
                                                                        fx, fy, fz, e1, e2, nullptr, nullptr, nullptr, 0.f);
             acc += (double)(e1 + e2);
         }
-        for (uint32_t k = tid; k < a.n14; k += 256u) {
-            const Pose14 r = a.p14[k];
+        for (uint32_t k = tid; k < lig.n14; k += 256u) {
+            const Pose14 r = lig.p14[k];
             const float4 pa = s_xyzq[r.a], pb = s_xyzq[r.b];
             const float dx = pose_mimg(pa.x - pb.x, a.box[0], a.inv_box[0]), dy = pose_mimg(pa.y - pb.y, a.box[1], a.inv_box[1]),
                         dz = pose_mimg(pa.z - pb.z, a.box[2], a.inv_box[2]);
@@ -174,7 +226,9 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
         for (int m = 32; m > 0; m >>= 1) acc += __shfl_xor(acc, m);
         if (lane == 0) s_row[wave][0] = acc;
         __syncthreads();
-        if (tid < a.G) out[tid] = tid == a.L ? ((s_row[0][0] + s_row[1][0]) + s_row[2][0]) + s_row[3][0] : 0.0;
+        // the ligand's element: column L of a resident ligand's row, the column behind the groups of a guest's
+        const uint32_t own = GUEST ? a.G : a.L;
+        if (tid < lig.W) out[tid] = tid == own ? ((s_row[0][0] + s_row[1][0]) + s_row[2][0]) + s_row[3][0] : 0.0;
         if (FORCE && tid < count) {
             // thread ia: the force on ligand atom ia from the ligand's other atoms, ib in order, then the 1-4 records that name it
             const uint32_t ia = tid;
@@ -182,7 +236,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
             const float2 la = s_lj[ia];
             double f0 = 0.0, f1 = 0.0, f2 = 0.0;
             for (uint32_t ib = 0; ib < count; ++ib) {
-                if (ib == ia || a.cls[ib * count + ia] != 0) continue;      // (the map is symmetric: this row is read coalesced)
+                if (ib == ia || lig.cls[ib * count + ia] != 0) continue;      // (the map is symmetric: this row is read coalesced)
                 const float4 pb = s_xyzq[ib];
                 const float dx = pose_mimg(pa.x - pb.x, a.box[0], a.inv_box[0]), dy = pose_mimg(pa.y - pb.y, a.box[1], a.inv_box[1]),
                             dz = pose_mimg(pa.z - pb.z, a.box[2], a.inv_box[2]);
@@ -191,8 +245,8 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
                                                                             fx, fy, fz, e1, e2, nullptr, nullptr, nullptr, 0.f);
                 f0 += (double)fx; f1 += (double)fy; f2 += (double)fz;
             }
-            for (uint32_t k = 0; k < a.n14; ++k) {
-                const Pose14 r = a.p14[k];
+            for (uint32_t k = 0; k < lig.n14; ++k) {
+                const Pose14 r = lig.p14[k];
                 if (r.a != ia && r.b != ia) continue;
                 const float4 p0 = s_xyzq[r.a], p1 = s_xyzq[r.b];
                 const float dx = pose_mimg(p0.x - p1.x, a.box[0], a.inv_box[0]), dy = pose_mimg(p0.y - p1.y, a.box[1], a.inv_box[1]),
@@ -269,7 +323,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
                     const uint32_t s = (t * MDX_CL_PER_TILE + ci) * MDX_CLUSTER + (uint32_t)ii;
                     const uint32_t o = a.orig_of[s];
                     const uint32_t ge = o == MDX_INVALID ? 0xFFFFFFFFu : (uint32_t)a.grp[a.gid[o]];
-                    const bool live = o != MDX_INVALID && ge != a.L;
+                    const bool live = o != MDX_INVALID && (GUEST || ge != a.L);      // (a guest skips no group: every resident atom is environment)
                     if (!__ballot(live)) continue;
                     if (__ballot(live && ge != cur_g && dacc != 0.0)) pose_fold(dacc, cur_g, row, lane);
                     if (live && dacc == 0.0) cur_g = ge;
@@ -305,6 +359,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
     pose_fold(dacc, cur_g, row, lane);
     __syncthreads();
     if (tid < a.G) out[tid] = ((s_row[0][tid] + s_row[1][tid]) + s_row[2][tid]) + s_row[3][tid];
+    if (GUEST && tid == 0u) out[a.G] = 0.0;
     if (FORCE)
         for (uint32_t i = tid; i < count * 3u; i += 256u) {
             const uint32_t ia = i / 3u, k = (i - ia * 3u) * fstride + ia;
@@ -620,9 +675,12 @@ __global__ __launch_bounds__(256) void pose_refine_step_kernel(StepArgs a) { pos
 __global__ __launch_bounds__(256) void pose_flex_step_kernel(StepArgs a) { pose_step<true>(a); }
 
 template <int COUL>
-static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force, bool refine = false) {
+static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force, bool refine = false, bool guest = false) {
     const dim3 g(POSE_UNITS + 1u, n), b(256);
-    if (refine) {
+    if (guest) {
+        if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, false, false, true>), g, b, 0, h->stream, a);
+        else hipLaunchKernelGGL((pose_score_kernel<COUL, false, false, false, true>), g, b, 0, h->stream, a);
+    } else if (refine) {
         const size_t lds = sizeof(double) * 12u * (((a.count + 7u) >> 3) << 3);
         if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, true, true>), g, b, lds, h->stream, a);
         else hipLaunchKernelGGL((pose_score_kernel<COUL, false, true, true>), g, b, lds, h->stream, a);
@@ -635,12 +693,12 @@ static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n
 }
 
 // the pose pass of n poses under the handle's Coulomb treatment
-static void pose_launch(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, bool force, bool refine) {
+static void pose_launch(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, bool force, bool refine, bool guest = false) {
     switch (mode) {
-    case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, force, refine); break;
-    case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, force, refine); break;
-    case CM_RF: launch_poses<CM_RF>(h, a, geom, n, force, refine); break;
-    default: launch_poses<CM_EWALD>(h, a, geom, n, force, refine); break;
+    case CM_SHIFTED: launch_poses<CM_SHIFTED>(h, a, geom, n, force, refine, guest); break;
+    case CM_SOFT: launch_poses<CM_SOFT>(h, a, geom, n, force, refine, guest); break;
+    case CM_RF: launch_poses<CM_RF>(h, a, geom, n, force, refine, guest); break;
+    default: launch_poses<CM_EWALD>(h, a, geom, n, force, refine, guest); break;
     }
 }
 
@@ -836,6 +894,233 @@ extern "C" int mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, ui
     if (n_poses == 0) return MDX_OK;
     if (!poses || !forces) FAIL(MDX_EPARAM, "null argument");
     return pose_run(h, "mdx_pose_forces", first, count, n_poses, poses, rows_or_null, n_groups, forces, rigid_or_null);
+}
+
+// ---- mdx_screen_ligands: a library of guest ligands against the resident atoms ---------------------------------------------------------------
+// A guest is described by the caller and never enters the handle: its charge / LJ rows, class map and 1-4 records are staged per chunk
+// beside its poses (GuestLayout), a PoseRec per pose says where, and the GUEST instantiation of pose_score_kernel reads them where the
+// resident one goes through slot_of and the handle's table.  Rows are n_groups + 1 wide: every resident group, then the ligand's own
+// pairs.  Nothing of the handle's state or of the resident-pose cache (ps_*) is written.
+struct GuestBest { double score; uint32_t pose, pad; };      // smallest row sum of a ligand so far and its ligand-local pose
+
+// The best pose of every ligand that has poses in the chunk: the thread of the first such pose walks the ligand's run in pose order
+// (lig_of[p] = (ligand, ligand-local pose); a ligand's poses are consecutive), S = the fp32-rounded row added in column order in fp64 -
+// what a host gets from the returned rows - and a strictly smaller S replaces the carried one: the lowest index wins a tie, also
+// across chunks.  One writer per ligand, no atomics.
+__global__ __launch_bounds__(256) void guest_best_kernel(uint32_t n, uint32_t W, const double* __restrict__ rows, const uint2* __restrict__ lig_of,
+                                                         GuestBest* __restrict__ best) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t m = lig_of[p].x;
+    if (p > 0u && lig_of[p - 1u].x == m) return;
+    GuestBest b = best[m];
+    for (uint32_t k = p; k < n && lig_of[k].x == m; ++k) {
+        double S = 0.0;
+        for (uint32_t c = 0; c < W; ++c) S += (double)(float)rows[(size_t)k * W + c];
+        if (S < b.score) { b.score = S; b.pose = lig_of[k].y; }
+    }
+    best[m] = b;
+}
+
+// The device block of one chunk of n guest poses: what the host stages ([0, up_end): records, (ligand, pose) words, charge and LJ rows
+// of the chunk's ligands, their 1-4 records, the coordinates, the class maps), then the units' slab and the summed rows.
+struct GuestLayout {
+    size_t rec, ligof, q, lj, p14, xyz, cls, up_end, slab, rows, end;
+    GuestLayout(size_t n, size_t atoms, size_t n14, size_t nxyz, size_t ncls, uint32_t W) {
+        auto al = [](size_t x) { return (x + 15u) / 16u * 16u; };
+        rec = 0;
+        ligof = al(rec + sizeof(PoseRec) * n);
+        q = al(ligof + sizeof(uint2) * n);
+        lj = al(q + sizeof(float) * atoms);
+        p14 = al(lj + sizeof(float2) * atoms);
+        xyz = al(p14 + sizeof(Pose14) * n14);
+        cls = al(xyz + sizeof(float) * nxyz);
+        up_end = cls + ncls;
+        slab = al(up_end);
+        rows = slab + sizeof(double) * n * (POSE_UNITS + 1u) * W;
+        end = rows + sizeof(double) * n * W;
+    }
+};
+
+// A guest's own pairs: the class map [count^2] (0 plain, 1 excluded, 2 scaled 1-4) of its two pair lists; null, or why the lists are refused
+static const char* guest_class_map(const mdx_guest_ligand& g, std::vector<uint8_t>& cls) {
+    const uint32_t n = g.count;
+    cls.assign((size_t)n * n, 0);
+    for (int list = 0; list < 2; ++list) {
+        const uint32_t np = list ? g.n_pairs14 : g.n_excl;
+        const uint32_t* pr = list ? g.pairs14 : g.excl_pairs;
+        const uint8_t mine = list ? 2 : 1;
+        for (uint32_t k = 0; k < np; ++k) {
+            const uint32_t a = pr[2 * (size_t)k], b = pr[2 * (size_t)k + 1];
+            if (a >= n || b >= n) return "a pair names an atom outside the ligand";
+            if (a == b) return "a pair of an atom with itself";
+            uint8_t& c = cls[(size_t)a * n + b];
+            if (c != 0 && c != mine) return "a pair is in both the exclusion and the 1-4 list";
+            c = mine; cls[(size_t)b * n + a] = mine;
+        }
+    }
+    return nullptr;
+}
+
+extern "C" int mdx_screen_ligands(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, float* rows_out, uint32_t n_groups,
+                                  uint32_t* best_pose, double* best_score) {
+    const std::string who = "mdx_screen_ligands";
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_ligands == 0) return MDX_OK;
+    if (!ligs) FAIL(MDX_EPARAM, "null argument");
+    const uint32_t G = h->n_grp, W = G + 1u;
+    if (!G) FAIL(MDX_EPARAM, "no energy groups are set (mdx_set_energy_groups)");
+    if (n_groups != G) FAIL(MDX_EPARAM, "n_groups must be the number of groups (mdx_energy_group_count)");
+    if (h->dd || h->n_local != h->N) FAIL(MDX_EPARAM, who + " on a decomposed handle (single-device handles only)");
+    if (h->alch_on) FAIL(MDX_EPARAM, who + " while an alchemical window is active");
+    std::vector<size_t> pstart((size_t)n_ligands + 1, 0);      // first pose of every ligand in the library's pose order
+    std::vector<uint8_t> cls;
+    for (uint32_t m = 0; m < n_ligands; ++m) {
+        const mdx_guest_ligand& g = ligs[m];
+        const std::string lig = who + ": ligand " + std::to_string(m) + ": ";
+        if (g.count == 0 || g.count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, lig + "count must be in 1..MDX_POSE_MAX_ATOMS (256)");
+        if (!g.charge || !g.lj_sigma || !g.lj_eps || (g.n_excl && !g.excl_pairs) || (g.n_pairs14 && !g.pairs14) || (g.n_poses && !g.poses))
+            FAIL(MDX_EPARAM, lig + "null argument");
+        for (uint32_t i = 0; i < g.count; ++i) {
+            if (!std::isfinite(g.charge[i]) || !std::isfinite(g.lj_sigma[i]) || !std::isfinite(g.lj_eps[i]))
+                FAIL(MDX_EPARAM, lig + "non-finite charge, sigma or eps");
+            if (g.lj_sigma[i] < 0.f || g.lj_eps[i] < 0.f) FAIL(MDX_EPARAM, lig + "negative sigma or eps");
+        }
+        if (const char* why = guest_class_map(g, cls)) FAIL(MDX_EPARAM, lig + why);
+        const size_t nx = 3 * (size_t)g.count * g.n_poses;
+        for (size_t k = 0; k < nx; ++k)
+            if (!std::isfinite(g.poses[k])) FAIL(MDX_EPARAM, lig + "non-finite pose coordinate");
+        pstart[m + 1] = pstart[m] + g.n_poses;
+    }
+    const size_t total = pstart[n_ligands];
+    if (total == 0) return MDX_OK;
+    if (!rows_out) FAIL(MDX_EPARAM, "null argument");
+    const bool want_best = best_pose || best_score;
+
+    HIP_TRY(hipSetDevice(h->device));
+    MDX_TRY(mdx_ensure_ready(h));          // what the matrix would see: list, constraints and virtual sites of the current state
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+
+    // the chunks: POSE_CHUNK consecutive poses of the library; every chunk names the ligands it holds poses of (first .. last)
+    struct Chunk { size_t p0; uint32_t n, m0, m1; size_t atoms, n14, nxyz, ncls; };
+    std::vector<Chunk> chunks;
+    size_t need = 0;
+    {
+        uint32_t m = 0;
+        for (size_t p0 = 0; p0 < total; p0 += POSE_CHUNK) {
+            Chunk c{p0, (uint32_t)std::min<size_t>(POSE_CHUNK, total - p0), 0, 0, 0, 0, 0, 0};
+            while (pstart[m + 1] <= p0) ++m;
+            c.m0 = m;
+            for (uint32_t k = m; k < n_ligands && pstart[k] < p0 + c.n; ++k) {
+                if (ligs[k].n_poses == 0) continue;
+                const size_t cnt = ligs[k].count, np = std::min(pstart[k + 1], p0 + c.n) - std::max(pstart[k], p0);
+                c.m1 = k; c.atoms += cnt; c.ncls += cnt * cnt; c.nxyz += 3 * cnt * np;
+                c.n14 += (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) ? 0u : ligs[k].n_pairs14;
+            }
+            need = std::max(need, GuestLayout(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W).end);
+            chunks.push_back(c);
+        }
+    }
+    MDX_TRY(pose_grow(&d.gs_blk, h->gs_cap_blk, need));
+    std::vector<GuestBest> best;
+    if (want_best) {
+        best.assign(n_ligands, GuestBest{INFINITY, 0xFFFFFFFFu, 0u});
+        MDX_TRY(pose_grow(&d.gs_best, h->gs_cap_best, sizeof(GuestBest) * best.size()));
+        HIP_TRY(hipMemcpyAsync(d.gs_best, best.data(), sizeof(GuestBest) * best.size(), hipMemcpyHostToDevice, st));
+    }
+
+    PoseArgs a{};
+    int mode = 0; bool geom = false, samecut = false;
+    mdx_fill_nb_params(h, a.p, &mode, &geom, &samecut);
+    a.g = h->grid;
+    a.posq = d.posq; a.lj = d.lj; a.orig_of = d.orig_of; a.gid = d.gid; a.grp = d.grp; a.slot_of = d.slot_of;
+    a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
+    a.G = G; a.L = 0xFFFFFFFFu;
+    a.r_cull = std::isfinite(h->r_list) ? h->r_list + 0.01f : INFINITY;
+    for (int k = 0; k < 3; ++k) {
+        a.box[k] = h->per[k] ? h->box_hi[k] - h->box_lo[k] : 0.f;
+        a.inv_box[k] = h->per[k] ? 1.0f / a.box[k] : 0.f;
+    }
+    const mdx_config& cfg = h->cfg;
+    const bool lj_off = (cfg.overrides & MDX_OVR_LJ_DISABLED) != 0, coul_off = (cfg.overrides & MDX_OVR_COULOMB_DISABLED) != 0;
+    const bool skip14 = (cfg.overrides & MDX_OVR_BONDED_DISABLED) != 0, geometric = cfg.combining_rule == MDX_COMBINE_GEOMETRIC;
+    const float sqrt_ke = std::sqrt(cfg.coulomb_k);
+
+    std::vector<float> res(total * W);
+    std::vector<double> rows((size_t)std::min<size_t>(total, POSE_CHUNK) * W);
+    std::vector<unsigned char> up;
+    unsigned char* blk = (unsigned char*)d.gs_blk;
+    for (const Chunk& c : chunks) {
+        const GuestLayout lay(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W);
+        up.assign(lay.up_end, 0);
+        PoseRec* rec = (PoseRec*)(up.data() + lay.rec);
+        uint2* ligof = (uint2*)(up.data() + lay.ligof);
+        float* gq = (float*)(up.data() + lay.q);
+        float2* glj = (float2*)(up.data() + lay.lj);
+        Pose14* p14 = (Pose14*)(up.data() + lay.p14);
+        float* xyz = (float*)(up.data() + lay.xyz);
+        uint32_t atom = 0, n14 = 0, nx = 0, ncls = 0, p = 0;
+        for (uint32_t m = c.m0; m <= c.m1; ++m) {
+            const mdx_guest_ligand& g = ligs[m];
+            if (g.n_poses == 0) continue;
+            const uint32_t cnt = g.count;
+            // rows and records as mdx_create makes a resident atom's: the overrides zero eps and charge first
+            std::vector<float2> raw(cnt);
+            std::vector<float> q(cnt);
+            for (uint32_t i = 0; i < cnt; ++i) {
+                raw[i] = make_float2(g.lj_sigma[i], lj_off ? 0.f : g.lj_eps[i]);
+                q[i] = coul_off ? 0.f : g.charge[i];
+                gq[atom + i] = q[i] * sqrt_ke;
+                glj[atom + i] = mdx_pack_lj(geometric, raw[i].x, raw[i].y);
+            }
+            (void)guest_class_map(g, cls);
+            std::memcpy(up.data() + lay.cls + ncls, cls.data(), cls.size());
+            const uint32_t first14 = n14;
+            for (uint32_t k = 0; !skip14 && k < g.n_pairs14; ++k) {
+                const uint32_t i = g.pairs14[2 * (size_t)k], j = g.pairs14[2 * (size_t)k + 1];
+                const float4 prm = mdx_pair14_params(cfg, raw[i], raw[j], q[i], q[j]);
+                p14[n14++] = Pose14{i, j, prm.x, prm.y, prm.z};
+            }
+            const size_t l0 = std::max(pstart[m], c.p0) - pstart[m], l1 = std::min(pstart[m + 1], c.p0 + c.n) - pstart[m];
+            for (size_t l = l0; l < l1; ++l, ++p) {
+                rec[p] = PoseRec{atom, cnt, ncls, first14, n14 - first14, nx};
+                ligof[p] = make_uint2(m, (uint32_t)l);
+                std::memcpy(xyz + nx, g.poses + 3 * (size_t)cnt * l, sizeof(float) * 3 * cnt);
+                nx += 3 * cnt;
+            }
+            atom += cnt; ncls += cnt * cnt;
+        }
+        HIP_TRY(hipMemcpyAsync(blk, up.data(), lay.up_end, hipMemcpyHostToDevice, st));
+        a.rec = (const PoseRec*)(blk + lay.rec);
+        a.gq = (const float*)(blk + lay.q); a.glj = (const float2*)(blk + lay.lj);
+        a.cls = blk + lay.cls; a.p14 = (const Pose14*)(blk + lay.p14);
+        a.poses = (const float*)(blk + lay.xyz);
+        a.slab = (double*)(blk + lay.slab);
+        double* drows = (double*)(blk + lay.rows);
+        mdx_prof_begin(h, 0);
+        pose_launch(h, a, mode, geom, c.n, false, false, true);
+        hipLaunchKernelGGL(pose_sum_kernel, dim3((c.n * W + 255u) / 256u), dim3(256), 0, st, c.n, W, a.slab, drows);
+        if (want_best)
+            hipLaunchKernelGGL(guest_best_kernel, dim3((c.n + 255u) / 256u), dim3(256), 0, st, c.n, W, drows, (const uint2*)(blk + lay.ligof),
+                               (GuestBest*)d.gs_best);
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rows.data(), drows, sizeof(double) * (size_t)c.n * W, hipMemcpyDeviceToHost, st));
+        if (want_best && &c == &chunks.back())
+            HIP_TRY(hipMemcpyAsync(best.data(), d.gs_best, sizeof(GuestBest) * best.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t k = 0; k < (size_t)c.n * W; ++k) {
+            if (!std::isfinite(rows[k])) FAIL(MDX_ENAN, who + ": non-finite energy in a row");
+            res[c.p0 * W + k] = (float)rows[k];
+        }
+    }
+    std::memcpy(rows_out, res.data(), sizeof(float) * res.size());
+    for (uint32_t m = 0; want_best && m < n_ligands; ++m) {
+        if (best_pose) best_pose[m] = best[m].pose;
+        if (best_score) best_score[m] = best[m].score;
+    }
+    return MDX_OK;
 }
 
 // ---- mdx_refine_poses and mdx_refine_poses_flex: one loop, the rigid and the flexible state record ---------------------------------------

@@ -17,9 +17,10 @@ import os
 
 import numpy as np
 
-from ._abi import (CCommDiag, CFlexOpts, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
+from ._abi import (CCommDiag, CFlexOpts, CGuestLigand, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
                    CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, FUSED_TRIAD_INFO_ARGTYPES, POSE_RMSD_ARGTYPES,
-                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, VEL, MdConfig, MdSystem)
+                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, SCREEN_LIGANDS_ARGTYPES, VEL, GuestLigand,
+                   MdConfig, MdSystem)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDX_LIB") or os.path.join(_HERE, "libmdx.so")   # MDX_LIB: A/B builds of the same ABI
@@ -181,6 +182,7 @@ def load_library():
                                      C.POINTER(CSearchOpts), _fp, _fp, C.c_uint32, C.POINTER(C.c_double), _fp, _u32p, _u32p]
     lib.mdx_pose_rmsd.argtypes = POSE_RMSD_ARGTYPES
     lib.mdx_cluster_poses.argtypes = CLUSTER_POSES_ARGTYPES
+    lib.mdx_screen_ligands.argtypes = SCREEN_LIGANDS_ARGTYPES
     _lib = lib
     return lib
 
@@ -297,6 +299,53 @@ class MdState:
         out = np.zeros((a.shape[0], max(n, 1)), dtype=np.float32)
         _check(lib.mdx_score_poses(self._h, int(first), a.shape[1], a.shape[0], a.ctypes.data_as(_fp), out.ctypes.data_as(_fp), n))
         return out[:, :n] if n else out[:, :0]
+
+    def screen_ligands(self, ligands, best=False):
+        """`mdx_screen_ligands`: a library of guest ligands - `GuestLigand`s, none of them part of the handle - against the resident
+        atoms.  -> a list with one float32 array [P_m, n_groups + 1] per ligand: the columns of score_poses() against every resident
+        group (no group is skipped), then the ligand's own pairs.  best=True: also (best_pose uint32 [M], best_score float64 [M]) - per
+        ligand the pose with the smallest row sum (lowest index on a tie) and that sum, picked on the device; 0xFFFFFFFF and inf for a
+        ligand without poses.  The handle is left as it is."""
+        ligands = list(ligands)
+        M = len(ligands)
+        recs = (CGuestLigand * max(M, 1))()
+        keep = []      # the arrays the records point into
+
+        def arr(a, dtype, shape, what, m):
+            try:
+                a = np.ascontiguousarray(a, dtype=dtype).reshape(shape)
+            except (TypeError, ValueError):
+                raise ParamError(f"screen_ligands: ligand {m}: {what} has the wrong shape or type") from None
+            keep.append(a)
+            return a
+
+        counts = []
+        for m, g in enumerate(ligands):
+            if not isinstance(g, GuestLigand):
+                raise ParamError("screen_ligands: ligands must be GuestLigand objects")
+            n = g.count
+            if not 1 <= n <= POSE_MAX_ATOMS:
+                raise ParamError(f"screen_ligands: ligand {m}: count must be in 1..{POSE_MAX_ATOMS}")
+            q, sg, ep = (arr(v, np.float32, (n,), w, m) for v, w in ((g.charge, "charge"), (g.lj_sigma, "lj_sigma"), (g.lj_eps, "lj_eps")))
+            ex = arr(g.excl_pairs, np.uint32, (-1, 2), "excl_pairs", m)
+            p14 = arr(g.pairs14, np.uint32, (-1, 2), "pairs14", m)
+            ps = arr(np.zeros((0, n, 3), np.float32) if g.poses is None else g.poses, np.float32, (-1, n, 3), "poses", m)
+            r = recs[m]
+            r.count, r.charge, r.lj_sigma, r.lj_eps = n, q.ctypes.data_as(_fp), sg.ctypes.data_as(_fp), ep.ctypes.data_as(_fp)
+            r.n_excl, r.excl_pairs = ex.shape[0], ex.ctypes.data_as(_u32p) if ex.size else None
+            r.n_pairs14, r.pairs14 = p14.shape[0], p14.ctypes.data_as(_u32p) if p14.size else None
+            r.n_poses, r.poses = ps.shape[0], ps.ctypes.data_as(_fp) if ps.size else None
+            counts.append(ps.shape[0])
+        lib = load_library()
+        G = int(lib.mdx_energy_group_count(self._h))
+        out = np.zeros((max(sum(counts), 1), G + 1), dtype=np.float32)
+        bp = np.full(max(M, 1), 0xFFFFFFFF, np.uint32)
+        bs = np.full(max(M, 1), np.inf, np.float64)
+        _check(lib.mdx_screen_ligands(self._h, M, recs, out.ctypes.data_as(_fp), G, bp.ctypes.data_as(_u32p) if best else None,
+                                      bs.ctypes.data_as(C.POINTER(C.c_double)) if best else None))
+        edges = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        rows = [out[edges[m]:edges[m + 1]].copy() for m in range(M)]
+        return (rows, (bp[:M], bs[:M])) if best else rows
 
     def pose_forces(self, first: int, poses, rows=True, rigid=False):
         """`mdx_pose_forces`: the force on every atom of each of P alternative placements of the atoms [first, first + count) - minus

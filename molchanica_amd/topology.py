@@ -86,6 +86,17 @@ def csr_from_pairs(n_atoms: int, pairs: np.ndarray):
     return offsets, both[:, 1].astype(np.uint32)
 
 
+def pairs_from_csr(offsets: np.ndarray, idx: np.ndarray, lo: int, hi: int) -> np.ndarray:
+    """The inverse of csr_from_pairs for the atoms [lo, hi): every (i, j) of their rows with i != j as a sorted pair, each once, in
+    GLOBAL indices -> int64 [P, 2].  A partner outside [lo, hi) stays in the list: the caller decides what that means."""
+    off = np.asarray(offsets, dtype=np.int64)
+    ii = np.repeat(np.arange(lo, hi, dtype=np.int64), np.diff(off[lo:hi + 1]))
+    jj = np.asarray(idx, dtype=np.int64)[off[lo]:off[hi]]
+    keep = ii != jj
+    pairs = np.sort(np.stack([ii[keep], jj[keep]], 1), axis=1)
+    return np.unique(pairs, axis=0).reshape(-1, 2)
+
+
 def ligand_automorphisms(n: int, bonds, keys, mask=None, cap: int = CLUSTER_MAX_PERMS) -> np.ndarray:
     """The symmetry images `MdState.pose_rmsd` / `cluster_poses` take: the automorphisms of the bond graph on n atoms that preserve the
     per-atom `keys` (e.g. the LJ type index), the identity first, de-duplicated by their action on the atoms of `mask` ([n] booleans,
