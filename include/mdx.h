@@ -815,6 +815,56 @@ int      mdx_cluster_poses(mdx_handle* h, uint32_t count, uint32_t n_poses, cons
                            uint32_t* leader_out_or_null /* [n_poses] */, uint32_t* cluster_of_out_or_null /* [n_poses] */,
                            float* rmsd_to_leader_out_or_null /* [n_poses] */, uint32_t* size_out_or_null /* [n_poses] */);
 
+/* ---- solubility mixing diagnostics of the resident state (the number the shrinking-box workflow exists to produce:
+ * compute_solubility_diagnostics, src/properties/mixing_analysis.rs:277-709, called at sol_shrinking_box.rs:1530-1562) -----------------
+ * "Has the solute stayed mixed with the water?" for n_copies copies of one solute: live (mdx_solubility_mixing) and in every stored
+ * snapshot while a layout is set (mdx_snapshot_read_solubility).  The call reads the handle's positions on the device; the handle is not
+ * changed and continues bit for bit like one that made no such call; two calls on the same state return the same bits.
+ *
+ * Inputs.  mdx_set_solute_copies: n_copies contiguous copies of atoms_per_copy atoms from first_atom (the reference's
+ * atom_posits[..solute_end] in chunks of atoms_per_solute); sel = indices inside a copy (the reference passes the non-hydrogens), NULL / 0
+ * = all; the selected atoms of copy c are first_atom + c atoms_per_copy + sel[k], in the order of sel.  n_copies == 0 switches it off.
+ * The waters are the oxygens (first sites) of mdx_set_water_layout, n_w of them.  n_s = n_copies n_sel selected atoms.
+ * Cell and distances.  L_axis = box_hi - box_lo of the handle's current box, in fp32; every distance is minimum image in it by the
+ * library's convention d <- d - rintf(d (1.0f / L)) L per axis, in fp32 for the pair sums; d2 = dx dx + dy dy + dz dz in fp32.
+ * Widths.  sigma in {4, 7, 10} A, each min(sigma, 0.9 half) then max(., 1), half = 0.5 max(min(Lx, Ly, Lz), 1), in fp32.
+ * Local mixing.  For a selected atom and a sigma: S = sum over the selected atoms of the OTHER copies of exp(-d2 / 2 sigma^2), W = the
+ * same sum over the water oxygens; every term is exp2(d2 k) in fp32 with k = fp32(-log2(e) / 2 sigma^2), the sums are fp64.  With
+ * S' = S / max(1, n_s - n_sel) and W' = W / n_w the atom's score is clamp(2 W' / (S' + W'), 0, 1), or 0 where S' + W' <= FLT_EPSILON.
+ * local_mixing = the mean over the three sigma of the mean over the atoms (fp64).
+ * Aggregation.  Two copies touch when any pair of their selected atoms has d2 <= 4.2f 4.2f (fp32).  From the touch graph: p = (largest
+ * connected component - 1) / (n_copies - 1), c = copies with a contact / n_copies, f = touching pairs / (n_copies (n_copies - 1) / 2), each
+ * the fp32 ratio of the two integers (largest_cluster_fraction, contacted_fraction, contact_pair_fraction).  aggregation_penalty =
+ * clamp(0.55 p^1.25 + 0.30 c^2 + 0.15 sqrt(f), 0, 1), aggregation_factor = exp(-3.5 penalty).  Fewer than two copies: factor 1, the
+ * other four 0.
+ * Dispersion.  Per copy, in fp64: anchor = wrap(first selected atom), centre = wrap(mean over the selected atoms of anchor +
+ * image(atom - anchor)), wrap(x) = x - L floor((x - box_lo) / L), image(d) = d - L rint(d / L).  solute_dispersion = clamp(rms over all
+ * copy pairs of |image(centre_b - centre_a)| / sqrt((Lx^2 + Ly^2 + Lz^2) / 12), 0, 1); 1 with one copy.
+ * Scalars (fp64, each field rounded to fp32 once).  mixture_score = local_mixing (0.60 + 0.40 solute_dispersion); raw_score =
+ * clamp(aggregation_factor mixture_score, 0, 1); score = ln(1 + 80 raw_score) / ln(81).
+ * Deviations from the reference.  It drops non-finite positions silently; here a non-finite coordinate among the selected atoms or the
+ * oxygens returns MDX_ENAN, like every other read of a blown-up state.  Its octree occupancy variant (compute_solubility_cell_list, the
+ * "BH" number) is not part of this library: its fp32 octant decisions make parity a matter of luck, and it is linear-time on the host.
+ *
+ * atom_sums (optional): S and W before normalisation, fp64 [n_copies n_sel][3 sigmas][2] - what a viewer colours atoms by.
+ * MDX_EPARAM (mdx_last_error says which; a refused call writes nothing to any output): a decomposed handle; a handle that is not periodic
+ * in all three dimensions (the score needs a cell); no solute layout or no water layout; a solute range that overlaps the water range or
+ * reaches beyond the atom array (checked when the layout is set and again at every call - the water layout may change in between);
+ * n_copies > MDX_SOLUTE_MAX_COPIES (the contact bit matrix stays at 2 MiB); atoms_per_copy == 0; a sel index >= atoms_per_copy or a
+ * repeated one; mdx_snapshot_read_solubility of a snapshot taken while the layout was off.
+ * One wait per call; the tail (scores, union-find, centres: O(n_copies^2)) runs on the host from one read-back.  Under mdx_profile(1) the
+ * device time of the pair kernel is added to nb_ms_sum, of the gather to bonded_ms_sum, of the slab sum to integ_ms_sum. */
+#define MDX_SOLUTE_MAX_COPIES 4096u
+typedef struct mdx_solubility {   /* SolubilityMixingDiagnostics, same order */
+    float score, raw_score, local_mixing, solute_dispersion, mixture_score,
+          aggregation_factor, aggregation_penalty, largest_cluster_fraction,
+          contacted_fraction, contact_pair_fraction;
+} mdx_solubility;
+int      mdx_set_solute_copies(mdx_handle* h, uint32_t first_atom, uint32_t n_copies, uint32_t atoms_per_copy,
+                               const uint32_t* sel_or_null /* [n_sel] */, uint32_t n_sel);
+int      mdx_solubility_mixing(mdx_handle* h, mdx_solubility* out, double* atom_sums_or_null /* [n_copies * n_sel][3][2] */);
+int      mdx_snapshot_read_solubility(mdx_handle* h, uint32_t k, mdx_solubility* out);
+
 /* ---- multi-GPU: one periodic box spatially decomposed over the GPUs of a node (the reference is
  * single-device, src/util.rs:1086 `CudaContext::new(0)`, so this is new capability, not parity) -------------------
  * One rank (process or thread) per GPU.  Every rank creates a handle from the SAME global system (static per-atom data

@@ -297,6 +297,27 @@ public:
         return r;
     }
 
+    /// mdx_set_solute_copies: n_copies contiguous copies of atoms_per_copy atoms from first_atom are the solute of solubility();
+    /// `sel`: indices inside a copy (the reference passes the non-hydrogens), empty = all; n_copies == 0 switches it off.
+    void set_solute_copies(uint32_t first_atom, uint32_t n_copies, uint32_t atoms_per_copy, const std::vector<uint32_t>& sel = {}) {
+        check(mdx_set_solute_copies(h_, first_atom, n_copies, atoms_per_copy, sel.empty() ? nullptr : sel.data(), (uint32_t)sel.size()));
+        n_solute_rows_ = (size_t)n_copies * (sel.empty() ? atoms_per_copy : sel.size());
+    }
+    /// mdx_solubility_mixing: `compute_solubility_diagnostics` (src/properties/sol_shrinking_box.rs:1539) of the current state, on the
+    /// device (mdx.h states the rule).  `atom_sums`, when given, receives S and W per selected atom and sigma, [n_copies n_sel][3][2].
+    mdx_solubility solubility(std::vector<double>* atom_sums = nullptr) {
+        mdx_solubility s{};
+        if (atom_sums) atom_sums->assign(6 * n_solute_rows_, 0.0);
+        check(mdx_solubility_mixing(h_, &s, atom_sums && !atom_sums->empty() ? atom_sums->data() : nullptr));
+        return s;
+    }
+    /// mdx_snapshot_read_solubility: the record of stored snapshot k (taken while a solute layout was set).
+    mdx_solubility snapshot_solubility(uint32_t k) {
+        mdx_solubility s{};
+        check(mdx_snapshot_read_solubility(h_, k, &s));
+        return s;
+    }
+
     /// `md.cell = SimBox::new(lo, hi)` + `md.rebuild_spatial_caches()` (sol_shrinking_box.rs:600-603, 632).
     void set_cell(const SimBox& b) { check(mdx_set_box(h_, b.bounds_low.data(), b.bounds_high.data())); }
     SimBox cell() const {
@@ -466,6 +487,7 @@ private:
         check(mdx_upload(h_, which, v.data()));
     }
     mdx_handle* h_ = nullptr;
+    size_t n_solute_rows_ = 0;      // n_copies n_sel of the last set_solute_copies
     uint32_t n_ = 0, n_waters_ = 0, water_sites_ = 0, n_foreign_ = 0;
 };
 

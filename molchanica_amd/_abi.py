@@ -45,6 +45,25 @@ _u8p = C.POINTER(C.c_uint8)
 POSE_RMSD_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_uint32, _fp, C.c_uint32, _fp, _u8p, C.c_uint32, _u32p, _fp]
 CLUSTER_POSES_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_uint32, _fp, C.POINTER(C.c_double), _u8p, C.c_uint32, _u32p, C.c_float, _u32p, _u32p,
                           _u32p, _fp, _u32p]
+SOLUTE_MAX_COPIES = 4096         # MDX_SOLUTE_MAX_COPIES: the most solute copies mdx_set_solute_copies takes
+
+
+class CSolubility(C.Structure):
+    """mdx_solubility: the reference's SolubilityMixingDiagnostics, same order."""
+    _fields_ = [(n, C.c_float) for n in (
+        "score", "raw_score", "local_mixing", "solute_dispersion", "mixture_score", "aggregation_factor", "aggregation_penalty",
+        "largest_cluster_fraction", "contacted_fraction", "contact_pair_fraction")]
+
+    def as_dict(self) -> dict:
+        return {n: np.float32(getattr(self, n)) for n, _ in self._fields_}
+
+
+# mdx_set_solute_copies(h, first_atom, n_copies, atoms_per_copy, sel_or_null, n_sel), mdx_solubility_mixing(h, out, atom_sums_or_null)
+# and mdx_snapshot_read_solubility(h, k, out)
+SET_SOLUTE_COPIES_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32]
+SOLUBILITY_MIXING_ARGTYPES = [C.c_void_p, C.POINTER(CSolubility), C.POINTER(C.c_double)]
+SNAPSHOT_READ_SOLUBILITY_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CSolubility)]
+
 # mdx_fused_triad_info(h, out[4]): eligible, distinct shapes, the last fused launch took the triad flavour, 0
 FUSED_TRIAD_INFO_ARGTYPES = [C.c_void_p, _u32p]
 

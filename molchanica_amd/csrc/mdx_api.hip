@@ -172,7 +172,7 @@ static void free_device(mdx_handle* h) {
                     d.role_off_s, d.role_rec_s, d.role_prm, d.tri_o, d.tri_s, d.tri_shape, d.ctl, d.energy,
                     d.flags_dev, d.bonded_part, d.bbox_red, d.pair_count, d.inner_count, d.pme_force, d.wstep_s, d.path, d.dprune, d.force_b, d.force_c, d.cons_o, d.cons_s, d.cons_tmp, d.cons_mask, d.cons_cnt, d.cons_off, d.cons_vir, d.vsite_o, d.vsite_s, d.gsite_o, d.gsite_s, d.gsite_tmp, d.pme_q, d.pme_f,
                     d.pme_theta, d.pme_q2, d.pme_f2, d.scratch4, d.tile_bnd, d.tile_scan, d.tile_order, d.tile_lpt, d.rb_ctl, d.scan_chain, d.grp, d.grp_mat, d.fl_hot, d.fl_slab, d.star_o, d.star_s, d.ewald_tab,
-                    d.ps_cls, d.ps_p14, d.ps_stage, d.ps_slab, d.ps_rows, d.ps_fslab, d.ps_fout, d.ps_rigid, d.ps_flex, d.ps_flex_tab, d.ps_search, d.ps_cl, d.ps_cl_mat, d.gs_blk, d.gs_best};
+                    d.ps_cls, d.ps_p14, d.ps_stage, d.ps_slab, d.ps_rows, d.ps_fslab, d.ps_fout, d.ps_rigid, d.ps_flex, d.ps_flex_tab, d.ps_search, d.ps_cl, d.ps_cl_mat, d.gs_blk, d.gs_best, d.mx_blk};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     d = DeviceState{};
 }

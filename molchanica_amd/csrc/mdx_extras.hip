@@ -389,6 +389,10 @@ static int take_snapshot(mdx_handle* h) {
         sn.between.resize((size_t)h->n_grp * h->n_grp);
         MDX_TRY(mdx_groups_evaluate(h, sn.between.data()));
     }
+    if (mdx_mixing_on(h)) {      // SolubilityMixingDiagnostics (src/properties/sol_shrinking_box.rs:1539), per snapshot
+        sn.solubility.resize(1);
+        MDX_TRY(mdx_mixing_evaluate(h, sn.solubility.data(), nullptr));
+    }
     if (h->alch_on && !h->foreign_lams.empty()) {      // BAR / MBAR inputs (mdx_foreign.hip); the reciprocal part is that of sn.e
         sn.foreign.resize(h->foreign_lams.size());
         MDX_TRY(mdx_foreign_evaluate(h, sn.foreign.data()));

@@ -302,6 +302,8 @@ struct DeviceState {
     // mdx_screen_ligands: the block of one chunk of guest poses (GuestLayout: records, guest tables, coordinates, slab, rows) and the
     // best pose of every ligand carried across the chunks.  Nothing of the resident-pose buffers above is touched by a screening.
     void* gs_blk = nullptr; void* gs_best = nullptr;
+    // mdx_solubility_mixing (mdx_mixing.hip): the block of one call (MxLayout: sel, slab partial sums, flag, sums, contact bits, gathered atoms)
+    void* mx_blk = nullptr;
 };
 
 struct MdxDecomp;   // mdx_comm.h: the handle is one rank of a spatially decomposed box
@@ -373,6 +375,8 @@ struct mdx_handle {
     bool fx_valid = false; uint32_t fx_first = 0, fx_count = 0, fx_root = 0, fx_flags = 0, fx_terms = 0; uint64_t fx_epoch = 0;
     std::vector<uint32_t> fx_bonds; size_t ps_cap_flex = 0, ps_cap_flex_tab = 0, ps_cap_search = 0, ps_cap_cl = 0, ps_cap_cl_mat = 0;
     size_t gs_cap_blk = 0, gs_cap_best = 0;      // bytes of gs_blk / gs_best
+    // mdx_set_solute_copies: mx_copies contiguous copies of mx_apc atoms from mx_first, the selected indices inside a copy (mx_copies == 0: off)
+    uint32_t mx_first = 0, mx_copies = 0, mx_apc = 0; std::vector<uint32_t> mx_sel; size_t mx_cap = 0;      // mx_cap: bytes of mx_blk
     bool alch_on = false; double alch_lambda = 0.0; uint32_t alch_lo = 0, alch_hi = 0;
     float sc_alpha = 0.5f, sc_sigma_min = 3.0f;   // soft core of the alchemical window (mdx_set_alchemical_softcore)
     std::vector<double> foreign_lams;             // mdx_set_foreign_lambdas (survives window changes; empty: none)
@@ -471,7 +475,8 @@ struct mdx_handle {
     uint32_t snap_handlers[MDX_SNAP_HANDLERS] = {};   // mdx_set_snapshot_handlers: cadence per handler (0 = off); snap_every stays the plain cadence of mdx_set_snapshot_cadence
     double time_ps = 0.0;
     struct Snapshot { double time; uint64_t step; mdx_energies e; std::vector<float> pos, vel, frc; std::vector<mdx_hbond> hbonds; std::vector<float> between; uint32_t handler_mask = 0;
-                      std::vector<double> foreign; };   // foreign: dU_k of mdx_set_foreign_lambdas (empty: taken without)
+                      std::vector<double> foreign;      // foreign: dU_k of mdx_set_foreign_lambdas (empty: taken without)
+                      std::vector<mdx_solubility> solubility; };   // one record while a solute layout is set (mdx_set_solute_copies; empty: taken without)
     // md.water views and hydrogen-bond detection (mdx_set_water_layout / mdx_set_hbond_detection)
     uint32_t water_first = 0, n_waters = 0, water_sites = 0;
     std::vector<uint8_t> hb_heavy; float hb_dmax = 2.5f, hb_angle_min = 120.f;
@@ -710,6 +715,8 @@ uint32_t mdx_steps_to_next_event(const mdx_handle* h);            // chunk lengt
 bool mdx_energy_wanted_at(const mdx_handle* h, uint64_t step);    // does something read the energies after step `step`?
 int mdx_finalize_energy_cache(mdx_handle* h);                     // e_pending -> e_cache (kinetic energy, constraint virial, read-back)
 int mdx_groups_evaluate(mdx_handle* h, float* out /* [n_grp^2] */);   // energy_potential_between_mols of the current state (mdx_groups.hip)
+bool mdx_mixing_on(const mdx_handle* h);      // a solute layout is set and, with the water layout and the cell as they are now, can be evaluated
+int mdx_mixing_evaluate(mdx_handle* h, mdx_solubility* out, double* atom_sums_or_null);   // mdx_solubility_mixing of the current state (mdx_mixing.hip)
 int mdx_foreign_evaluate(mdx_handle* h, double* du /* [foreign_lams.size()] */);   // foreign-lambda dU_k of the current state (mdx_foreign.hip); the
                                                                      // reciprocal part comes from the last energy evaluation, which must be of this state
 int mdx_launch_scale_velocities(mdx_handle* h, float lambda, const double* com_v_or_null);

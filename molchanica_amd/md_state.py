@@ -20,7 +20,8 @@ import numpy as np
 from ._abi import (CCommDiag, CFlexOpts, CGuestLigand, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
                    CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, FUSED_TRIAD_INFO_ARGTYPES, POSE_RMSD_ARGTYPES,
                    MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, SCREEN_LIGANDS_ARGTYPES, VEL, GuestLigand,
-                   MdConfig, MdSystem)
+                   MdConfig, MdSystem, CSolubility, SET_SOLUTE_COPIES_ARGTYPES, SNAPSHOT_READ_SOLUBILITY_ARGTYPES, SOLUBILITY_MIXING_ARGTYPES,
+                   SOLUTE_MAX_COPIES)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDX_LIB") or os.path.join(_HERE, "libmdx.so")   # MDX_LIB: A/B builds of the same ABI
@@ -183,6 +184,9 @@ def load_library():
     lib.mdx_pose_rmsd.argtypes = POSE_RMSD_ARGTYPES
     lib.mdx_cluster_poses.argtypes = CLUSTER_POSES_ARGTYPES
     lib.mdx_screen_ligands.argtypes = SCREEN_LIGANDS_ARGTYPES
+    lib.mdx_set_solute_copies.argtypes = SET_SOLUTE_COPIES_ARGTYPES
+    lib.mdx_solubility_mixing.argtypes = SOLUBILITY_MIXING_ARGTYPES
+    lib.mdx_snapshot_read_solubility.argtypes = SNAPSHOT_READ_SOLUBILITY_ARGTYPES
     _lib = lib
     return lib
 
@@ -793,6 +797,10 @@ class MdState:
                 snap["energy_data"]["foreign_du"] = du
                 if self._foreign_lams is not None and self._foreign_lams.shape[0] == n_f:
                     snap["energy_data"]["foreign_lambdas"] = self._foreign_lams.copy()
+            if self._n_solute_rows:      # SolubilityMixingDiagnostics of the snapshot (absent: taken while the layout was off)
+                sol = CSolubility()
+                if lib.mdx_snapshot_read_solubility(self._h, k, C.byref(sol)) == MDX_OK:
+                    snap["solubility"] = sol.as_dict()
             n_hb = int(lib.mdx_snapshot_hbond_count(self._h, k))
             hb = (CHBond * max(n_hb, 1))()
             if n_hb:
@@ -822,6 +830,38 @@ class MdState:
                                                  arr["h0"].ctypes.data_as(_fp), arr["h1"].ctypes.data_as(_fp),
                                                  arr["m"].ctypes.data_as(_fp) if "m" in arr else None))
         return arr
+
+    # -- solubility mixing diagnostics (include/mdx.h states the rule) -----------------------------
+    _n_solute_rows = 0
+
+    def set_solute_copies(self, first_atom: int, n_copies: int, atoms_per_copy: int, sel=None):
+        """`mdx_set_solute_copies`: n_copies contiguous copies of atoms_per_copy atoms from first_atom are the solute of solubility()
+        (the reference's atom_posits[..solute_end] in chunks of atoms_per_solute, src/properties/sol_shrinking_box.rs:1539); sel: indices
+        inside a copy (the reference passes the non-hydrogens), None = all.  n_copies = 0 switches it off.  Needs set_water_layout()."""
+        s = None
+        if sel is not None:
+            s = np.asarray(sel)
+            if s.dtype.kind not in "iu" or s.ndim != 1 or (s < 0).any():
+                raise ParamError("set_solute_copies: sel must be unsigned integers [n_sel]")
+            s = np.ascontiguousarray(s, dtype=np.uint32)
+            if s.shape[0] == 0:
+                s = None
+        if not 0 <= int(n_copies) <= SOLUTE_MAX_COPIES:
+            raise ParamError(f"set_solute_copies: n_copies must be in 0..{SOLUTE_MAX_COPIES}")
+        _check(load_library().mdx_set_solute_copies(self._h, int(first_atom), int(n_copies), int(atoms_per_copy),
+                                                    None if s is None else s.ctypes.data_as(_u32p), 0 if s is None else s.shape[0]))
+        self._n_solute_rows = int(n_copies) * (int(atoms_per_copy) if s is None else s.shape[0])
+
+    def solubility(self, atom_sums: bool = False):
+        """`mdx_solubility_mixing`: the reference's SolubilityMixingDiagnostics of the current state, computed on the device -> a dict of
+        float32 under the reference's field names (score, raw_score, local_mixing, solute_dispersion, mixture_score, aggregation_factor,
+        aggregation_penalty, largest_cluster_fraction, contacted_fraction, contact_pair_fraction).  atom_sums=True: -> (dict, float64
+        [n_copies * n_sel, 3, 2]: per selected atom and sigma the sums S over the other copies' atoms and W over the water oxygens,
+        before normalisation).  The handle is left as it is."""
+        out = CSolubility()
+        sums = np.zeros((max(self._n_solute_rows, 1), 3, 2), dtype=np.float64) if atom_sums else None
+        _check(load_library().mdx_solubility_mixing(self._h, C.byref(out), None if sums is None else sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return (out.as_dict(), sums[:self._n_solute_rows]) if atom_sums else out.as_dict()
 
     def set_hbond_detection(self, is_heavy_nosf, max_h_acc_dist: float = 2.5, min_angle_deg: float = 120.0):
         """Hydrogen bonds in every snapshot's energy data (src/md/viewer.rs:917-960); None switches it off."""
