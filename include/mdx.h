@@ -672,6 +672,48 @@ int      mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_
                           float* xform_out_or_null /* [n_poses][7]: q (w, x, y, z), t */, uint32_t* status_out_or_null /* [n_poses] */,
                           uint32_t* evals_out_or_null /* [n_poses] */);
 
+/* ---- guest ligands with gradients and rigid-body refinement: mdx_pose_forces and mdx_refine_poses for a library of mdx_guest_ligand -----
+ * "Score a library, relax every pose, keep the best relaxed pose per ligand" against a receptor handle that is built once.  Both calls
+ * take the library of mdx_screen_ligands; its preconditions and refusals hold (mdx_last_error names the ligand and the reason), the rows
+ * are n_groups + 1 wide with the ligand's own pairs in column n_groups, and all per-pose outputs follow the library's pose order, ligand
+ * m's n_poses entries together.  Coordinate-shaped outputs (forces, poses_out) are ligand-major: per ligand [n_poses][count][3], the
+ * ligands one behind the other - the layout of the ligands' `poses` laid end to end.
+ *
+ * mdx_guest_forces.  For pose p of ligand m
+ *   rows    (where given) the row mdx_screen_ligands returns, bit for bit;
+ *   forces  what mdx_pose_forces returns on a second handle that holds the same atoms at the same positions plus ligand m appended as
+ *           one more group: minus the gradient of the sum over all n_groups + 1 columns - the pair force from every resident atom (no
+ *           group is skipped), from the ligand's plain pairs and from its scaled 1-4 pairs (none under MDX_OVR_BONDED_DISABLED), with
+ *           the softened-Coulomb exception stated at mdx_pose_forces; no SPME mesh term;
+ *   rigid   (where given) (sum_i f_i, sum_i (x_i - c) x f_i) about the unweighted centroid c of the pose as given, on the device in
+ *           fp64, in atom order, of the unrounded forces.
+ * MDX_EPARAM also for forces == NULL; MDX_ENAN: a non-finite row, force, net force or torque (atoms on top of each other).  A refused
+ * or failed call writes nothing.
+ *
+ * mdx_refine_guests.  The stepper of mdx_refine_poses, word for word, with the evaluation of mdx_guest_forces: r = the row (n_groups + 1
+ * columns), S = sum over the columns in column order of (double) r[b], forces and rigid as above.  Options, their refusals and defaults,
+ * the status values and the outputs of the accepted state are those of mdx_refine_poses: rows_out[p] holds the bits mdx_screen_ligands
+ * returns for poses_out[p], rigid_out[p] those mdx_guest_forces returns for it.  A pose that is not finite at evaluation 0 ends with
+ * MDX_REFINE_NONFINITE; the call does not fail for it.  MDX_EPARAM also for opts == NULL or poses_out == NULL.
+ * best_pose_or_null[m] / best_score_or_null[m]: picked on the device from the ACCEPTED rows by the rule of mdx_screen_ligands - a
+ * strictly smaller S wins, the lowest ligand-local index wins a tie - except that a MDX_REFINE_NONFINITE pose never wins; 0xFFFFFFFF
+ * and +infinity for a ligand with no poses or none finite.
+ *
+ * For both: the handle is not changed (positions, lists, caches, snapshots, the tables of the resident pose calls) and continues bit
+ * for bit like one that did not make the call.  A (ligand, pose) gives the same bits alone, in a library of any size and order, at any
+ * place in it.  n_ligands == 0, or a library without a single pose, succeeds and does nothing.  Decomposed handles and active
+ * alchemical windows are refused.  Per chunk of 256 poses of the library the refinement enqueues max_evals x (force pass, step kernel)
+ * and waits once.  Not built for guests: torsional refinement and search. */
+int      mdx_guest_forces(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs,
+                          float* rows_or_null /* [sum n_poses][n_groups + 1] */, uint32_t n_groups,
+                          float* forces /* per ligand [n_poses][count][3] */, float* rigid_or_null /* [sum n_poses][6] */);
+int      mdx_refine_guests(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_refine_opts* opts,
+                           float* poses_out /* per ligand [n_poses][count][3] */,
+                           float* rows_out_or_null /* [sum n_poses][n_groups + 1] */, uint32_t n_groups,
+                           float* rigid_out_or_null /* [sum n_poses][6] */, float* xform_out_or_null /* [sum n_poses][7] */,
+                           uint32_t* status_out_or_null /* [sum n_poses] */, uint32_t* evals_out_or_null /* [sum n_poses] */,
+                           uint32_t* best_pose_or_null /* [n_ligands] */, double* best_score_or_null /* [n_ligands] */);
+
 /* ---- flexible refinement: the same descent with the ligand's torsion angles as further coordinates -------------------------------
  * Preconditions, refusals, the treatment of the handle, the status values, MDX_REFINE_MAX_EVALS_CAP, the defaults of h_start and h_max
  * and the chunks of 256 poses are those of mdx_refine_poses; a refused call writes nothing, and a pose gives the same bits alone or in

@@ -185,6 +185,37 @@ public:
                                  best_score ? best_score->data() : nullptr));
         return out;
     }
+    /// mdx_guest_forces: forces of every pose of a library of guest ligands, per ligand [n_poses][count][3], the ligands one behind the
+    /// other; rows (if not null) receives the rows of screen_ligands, rigid (if not null) [sum n_poses][6].
+    std::vector<float> guest_forces(const std::vector<mdx_guest_ligand>& ligs, std::vector<float>* rows = nullptr, std::vector<float>* rigid = nullptr) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        size_t n = 0, nx = 0;
+        for (const mdx_guest_ligand& l : ligs) { n += l.n_poses; nx += 3 * (size_t)l.count * l.n_poses; }
+        std::vector<float> f(nx);
+        if (rows) rows->assign(n * ((size_t)g + 1), 0.f);
+        if (rigid) rigid->assign(n * 6, 0.f);
+        check(mdx_guest_forces(h_, (uint32_t)ligs.size(), ligs.data(), rows ? rows->data() : nullptr, g, f.data(), rigid ? rigid->data() : nullptr));
+        return f;
+    }
+    /// mdx_refine_guests: refine_poses for a library of guest ligands; the best accepted pose per ligand is picked on the device.
+    struct RefinedGuests {
+        std::vector<float> poses, rows, rigid, xform;      ///< per ligand [n_poses][count][3]; [n][n_groups + 1], [n][6], [n][7], n = sum n_poses
+        std::vector<uint32_t> status, evals;               ///< [n]
+        std::vector<uint32_t> best_pose;                   ///< [n_ligands], 0xFFFFFFFF: no pose, or none finite
+        std::vector<double> best_score;                    ///< [n_ligands]
+    };
+    RefinedGuests refine_guests(const std::vector<mdx_guest_ligand>& ligs, const mdx_refine_opts& opts) {
+        const uint32_t g = mdx_energy_group_count(h_);
+        size_t n = 0, nx = 0;
+        for (const mdx_guest_ligand& l : ligs) { n += l.n_poses; nx += 3 * (size_t)l.count * l.n_poses; }
+        RefinedGuests r;
+        r.poses.assign(nx, 0.f); r.rows.assign(n * ((size_t)g + 1), 0.f); r.rigid.assign(n * 6, 0.f); r.xform.assign(n * 7, 0.f);
+        r.status.assign(n, 0u); r.evals.assign(n, 0u);
+        r.best_pose.assign(ligs.size(), 0xFFFFFFFFu); r.best_score.assign(ligs.size(), std::numeric_limits<double>::infinity());
+        check(mdx_refine_guests(h_, (uint32_t)ligs.size(), ligs.data(), &opts, r.poses.data(), r.rows.data(), g, r.rigid.data(), r.xform.data(),
+                                r.status.data(), r.evals.data(), r.best_pose.data(), r.best_score.data()));
+        return r;
+    }
     /// mdx_pose_forces: forces [n_poses][count][3] kcal/mol/A on the atoms of every pose (minus the gradient of the sum of its row);
     /// rows (if not null) receives the rows of score_poses, rigid (if not null) [n_poses][6]: net force, torque about the pose's centroid.
     std::vector<float> pose_forces(uint32_t first, uint32_t count, const std::vector<float>& poses, std::vector<float>* rows = nullptr,

@@ -124,6 +124,12 @@ class CGuestLigand(C.Structure):
 
 # mdx_screen_ligands(h, n_ligands, ligs, rows, n_groups, best_pose_or_null, best_score_or_null)
 SCREEN_LIGANDS_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), _fp, C.c_uint32, _u32p, C.POINTER(C.c_double)]
+# mdx_guest_forces(h, n_ligands, ligs, rows_or_null, n_groups, forces, rigid_or_null)
+GUEST_FORCES_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), _fp, C.c_uint32, _fp, _fp]
+# mdx_refine_guests(h, n_ligands, ligs, opts, poses_out, rows_out_or_null, n_groups, rigid_out_or_null, xform_out_or_null,
+#                   status_out_or_null, evals_out_or_null, best_pose_or_null, best_score_or_null)
+REFINE_GUESTS_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), C.POINTER(CRefineOpts), _fp, _fp, C.c_uint32, _fp, _fp, _u32p, _u32p,
+                          _u32p, C.POINTER(C.c_double)]
 
 
 class CEnergies(C.Structure):

@@ -61,31 +61,34 @@
 // guest skips no group, and its slab rows have one more column for its own pairs.  guest_best_kernel picks the best pose per ligand
 // from the chunk's summed rows and carries it across chunks.
 //
+// mdx_guest_forces, mdx_refine_guests: the force flavour and the rigid refinement for guests.  One launch holds poses of different
+// sizes, so what the force flavour sized by the ligand's count comes from the pose's record: the unit's block of the force slab
+// (PoseLigand::fslab - a pose's POSE_UNITS + 1 blocks start at (POSE_UNITS + 1) x the offset of its coordinates), fstride and the
+// own-pair unit's tid < count; the launch's dynamic LDS is sized by the chunk's largest ligand and every workgroup lays its own
+// [wave][xyz][fstride] inside it.  Behind the force pass StepLigand<GUEST> mirrors PoseLigand: pose_force_sum and pose_step index every
+// coordinate-shaped buffer through it (guest_force_sum_kernel, guest_refine_step_kernel: further plain kernels over the one body),
+// the stage buffer is the chunk's coordinate block, rows are G + 1 wide, and guest_best reads the accepted fp32 rows.
+//
 // What is written once: the unit-order sum of a slab (pose_units_sum: the four kernels that add the 17 units take it from there, which
 // is why rows_out / rigid_out of a refinement are the bits mdx_score_poses / mdx_pose_forces return), the stages of an evaluation
 // (step_gather, step_store, step_max_speed; centroid, rigid and inertia stand once in pose_step), the B(theta) loop
 // (pose_build_torsions: the flexible step kernel and the search kernel), and on the host the Coulomb dispatch (pose_launch),
 // buffer growth (pose_grow), the block of a chunk (StepLayout), the option checks (refine_opts_check) and the chunk loop with its
-// unpacker (refine_chunks, refine_unpack).
+// unpacker (refine_chunks, refine_unpack); for guests the checks, the plan (mdx_pose_plan.h), the arguments and the staging of a chunk
+// (guest_check, guest_plan / guest_slots / guest_records, guest_ready, guest_stage), shared by the three guest entry points.
 #include "mdx_bonded_dev.h"
 #include "mdx_pair_dev.h"
 #include "mdx_refine_step.h"
 #include "mdx_flex_step.h"
 #include "mdx_search_step.h"
+#include "mdx_pose_plan.h"
 #include <cmath>
 #include <cstring>
 #include <type_traits>
 
 #define FAIL(code, msg) do { mdx_set_error(msg); return (code); } while (0)
 
-#define POSE_UNITS 16u     // environment units per pose: a batch of one pose still spreads over 17 workgroups
-#define POSE_CHUNK 256u    // poses staged per launch (host staging only: it does not enter the arithmetic)
-
-struct Pose14 { uint32_t a, b; float sig, e4, qq; };      // ligand-local atoms; sigma_ij, 4 scale eps_ij, scale k_e q_i q_j
-
-// A guest pose (mdx_screen_ligands): where its ligand lies in the chunk's tables.  atom: first row of the charge / LJ tables; cls: first
-// byte of its class map [count^2]; p14, n14: its 1-4 records; xyz: first float of the pose's coordinates.
-struct PoseRec { uint32_t atom, count, cls, p14, n14, xyz; };
+// (POSE_UNITS, POSE_CHUNK, Pose14 and PoseRec - the record of a guest pose - stand in mdx_pose_plan.h beside the layouts made of them)
 
 struct PoseArgs {
     NbParams p;
@@ -101,8 +104,9 @@ struct PoseArgs {
     float box[3], inv_box[3];      // periodic axes (0: none)
     const uint8_t* cls; const Pose14* p14; uint32_t n14;
     const uint32_t* frozen;        // REFINE: [poses of the chunk], non-zero = the pose has finished, its workgroups return at once
-    // GUEST: the ligand is the caller's, not the handle's.  first / count / L are unused; cls and p14 are the chunk's tables, poses its
-    // coordinates, and the slab rows are G + 1 wide (column G: the ligand's own pairs)
+    // GUEST: the ligand is the caller's, not the handle's.  first / L are unused and count is the host's alone (the chunk's largest
+    // ligand: it sizes the force flavour's dynamic LDS); cls and p14 are the chunk's tables, poses its coordinates, and the slab rows
+    // are G + 1 wide (column G: the ligand's own pairs)
     const PoseRec* rec;            // [poses of the chunk]
     const float* gq; const float2* glj;      // [ligand atoms of the chunk]: q sqrt(k_e), the packed LJ record (mdx_pack_lj)
 };
@@ -127,22 +131,29 @@ template <bool GUEST>
 struct PoseLigand {
     uint32_t count, n14, W;        // W: width of a slab row
     const float* xyz; const uint8_t* cls; const Pose14* p14;
-    uint32_t atom;
+    uint32_t atom, xoff;           // xoff (GUEST): the record's xyz
     __device__ __forceinline__ PoseLigand(const PoseArgs& a, uint32_t pose) {
         if constexpr (GUEST) {
             const PoseRec r = a.rec[pose];
+            xoff = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.xyz);
             count = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.count);
             n14 = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.n14);
             atom = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.atom);
-            xyz = a.poses + (uint32_t)__builtin_amdgcn_readfirstlane((int)r.xyz);
+            xyz = a.poses + xoff;
             cls = a.cls + (uint32_t)__builtin_amdgcn_readfirstlane((int)r.cls);
             p14 = a.p14 + (uint32_t)__builtin_amdgcn_readfirstlane((int)r.p14);
             W = a.G + 1u;
         } else {
-            count = a.count; n14 = a.n14; atom = a.first; W = a.G;
+            count = a.count; n14 = a.n14; atom = a.first; W = a.G; xoff = 0u;
             xyz = a.poses + (size_t)pose * count * 3;
             cls = a.cls; p14 = a.p14;
         }
+    }
+    // the unit's partial forces [count][3] of the force slab: the poses of a guest chunk differ in size, and a pose's POSE_UNITS + 1
+    // blocks start where its coordinates do, scaled
+    __device__ __forceinline__ double* fslab(const PoseArgs& a, uint32_t pose, uint32_t unit) const {
+        if constexpr (GUEST) return a.fslab + (size_t)(POSE_UNITS + 1u) * xoff + (size_t)unit * count * 3u;
+        else return a.fslab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * count * 3u;
     }
     // charge (q sqrt(k_e)) and packed LJ record of ligand atom i
     __device__ __forceinline__ void row(const PoseArgs& a, uint32_t i, float& q, float2& lj) const {
@@ -156,8 +167,7 @@ struct PoseLigand {
 
 template <int COUL, bool GEOM, bool FORCE, bool REFINE = false, bool GUEST = false>
 __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
-    static_assert(!GUEST || (!FORCE && !REFINE), "guest ligands: the energy flavour only");
-    extern __shared__ double s_f[];      // FORCE: [4 waves][xyz][fstride] (nothing otherwise)
+    extern __shared__ double s_f[];      // FORCE: [4 waves][xyz][fstride] of this pose (the launch sizes it by its largest; nothing otherwise)
     if (REFINE && a.frozen[blockIdx.y] != 0u) return;      // (uniform over the workgroup, before any barrier)
     __shared__ float4 s_xyzq[MDX_POSE_MAX_ATOMS];
     __shared__ float2 s_lj[MDX_POSE_MAX_ATOMS];
@@ -195,7 +205,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
     }
     double* out = a.slab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * lig.W;
     const uint32_t fstride = ((count + 7u) >> 3) << 3;
-    double* fout = FORCE ? a.fslab + ((size_t)pose * (POSE_UNITS + 1u) + unit) * count * 3u : nullptr;
+    double* fout = FORCE ? lig.fslab(a, pose, unit) : nullptr;
 
     if (unit == POSE_UNITS) {
         // ---- the ligand's own pairs ----
@@ -390,15 +400,41 @@ __device__ __forceinline__ double pose_rigid_component(uint32_t k, uint32_t coun
     return v;
 }
 
+// The ligand of a pose as the kernels behind the force pass see it - PoseLigand's counterpart there: its size, where atom i lies in
+// every buffer shaped like the coordinates (the staged trial, forces, accepted and input coordinates: at(i), in floats) and where its
+// POSE_UNITS + 1 partial forces start in the force slab (units).  Resident: n atoms, the same for every pose.  GUEST: the pose's record,
+// uniform over the workgroup and kept in scalar registers; the blocks of partial forces start at double (POSE_UNITS + 1) x xyz.
+template <bool GUEST>
+struct StepLigand {
+    uint32_t count, pose, xoff;
+    __device__ __forceinline__ StepLigand(const PoseRec* rec, uint32_t n, uint32_t p) : count(n), pose(p), xoff(0u) {
+        if constexpr (GUEST) {
+            count = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec[p].count);
+            xoff = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec[p].xyz);
+        }
+    }
+    __device__ __forceinline__ size_t at(uint32_t i) const {
+        if constexpr (GUEST) return (size_t)xoff + i * 3u;
+        else return ((size_t)pose * count + i) * 3u;
+    }
+    __device__ __forceinline__ const double* units(const double* fslab, uint32_t i) const {
+        if constexpr (GUEST) return fslab + (size_t)(POSE_UNITS + 1u) * xoff + i * 3u;
+        else return fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + i) * 3u;
+    }
+};
+
 // forces[pose][atom] = the units' partial forces added in unit order (fp64, rounded once); rigid[pose] = (sum_i f_i, sum_i (x_i - c) x f_i),
 // c the unweighted mean of the pose's coordinates as the caller gave them - fp64, atom order, of the unrounded forces.
-__global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, const float* __restrict__ poses, const double* __restrict__ fslab,
-                                                             float* __restrict__ forces, float* __restrict__ rigid) {
+template <bool GUEST>
+__device__ __forceinline__ void pose_force_sum(const PoseRec* rec, uint32_t n, const float* __restrict__ poses, const double* __restrict__ fslab,
+                                               float* __restrict__ forces, float* __restrict__ rigid) {
     __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_c[3];
     const uint32_t tid = threadIdx.x, pose = blockIdx.x;
+    const StepLigand<GUEST> lig(rec, n, pose);
+    const uint32_t count = lig.count;
     if (tid < count) {
-        const double* s = fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
-        const size_t at = ((size_t)pose * count + tid) * 3u;
+        const double* s = lig.units(fslab, tid);
+        const size_t at = lig.at(tid);
         for (uint32_t c = 0; c < 3u; ++c) {
             const double v = pose_units_sum(s + c, (size_t)count * 3u);
             s_v[tid][c] = v; s_x[tid][c] = (double)poses[at + c];
@@ -414,10 +450,19 @@ __global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, con
     __syncthreads();
     if (tid < 6u) rigid[(size_t)pose * 6u + tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
 }
+// one body, two plain kernels (as the step kernels below)
+__global__ __launch_bounds__(256) void pose_force_sum_kernel(uint32_t count, const float* __restrict__ poses, const double* __restrict__ fslab,
+                                                             float* __restrict__ forces, float* __restrict__ rigid) {
+    pose_force_sum<false>(nullptr, count, poses, fslab, forces, rigid);
+}
+__global__ __launch_bounds__(256) void guest_force_sum_kernel(const PoseRec* __restrict__ rec, const float* __restrict__ poses,
+                                                              const double* __restrict__ fslab, float* __restrict__ forces, float* __restrict__ rigid) {
+    pose_force_sum<true>(rec, 0u, poses, fslab, forces, rigid);
+}
 
-#define FLEX_TERM_WORDS 13u      // per dihedral term and evaluation: energy, then the forces on its four atoms
-
-// The step kernel's arguments, both instantiations; the rigid one leaves T, n_terms, eterm and the table pointers zero.
+// The step kernel's arguments, every instantiation; the rigid ones leave T, n_terms, eterm and the table pointers zero.  G is the width
+// of a row.  Guests (rec != null): G is the groups + 1, count is unused, and "[..][count][3]" reads "as the chunk's coordinates lie"
+// (StepLigand).
 struct StepArgs {
     uint32_t count, G, T, n_terms;
     float* stage;                  // [poses of the chunk][count][3]: the trial the force flavour evaluated; receives the next one
@@ -429,6 +474,7 @@ struct StepArgs {
     const mdx_fx_torsion* tor; const mdx_fx_dihedral* dih; const uint32_t* aoff; const uint32_t* aent;
     double box[3];                 // periodic axes (0: none), as the force pass has them
     mdx_fx_opts o;
+    const PoseRec* rec;            // guests: [poses of the chunk] (last: the resident kernels read their arguments where they always did)
 };
 
 __device__ __forceinline__ mdx_rf_state& rf_of(mdx_rf_state& s) { return s; }
@@ -438,10 +484,10 @@ __device__ __forceinline__ mdx_rf_state& rf_of(mdx_fx_state& s) { return s.rf; }
 // Rows and forces of the 17 units added in unit order and rounded where pose_sum_kernel / pose_run and pose_force_sum_kernel round
 // them, the staged trial in fp64; WITH_F (flexible): s_f takes the fp32 force mdx_pose_forces returns - what a host loop has.
 // A non-finite value raises *s_bad.  Ends with a barrier.
-template <bool WITH_F>
-__device__ __forceinline__ void step_gather(const StepArgs& a, uint32_t pose, uint32_t tid, float* s_row, double (*s_v)[3], double (*s_x)[3],
-                                            double (*s_f)[3], uint32_t* s_bad) {
-    const uint32_t count = a.count;
+template <bool WITH_F, bool GUEST>
+__device__ __forceinline__ void step_gather(const StepArgs& a, const StepLigand<GUEST>& lig, uint32_t pose, uint32_t tid, float* s_row,
+                                            double (*s_v)[3], double (*s_x)[3], double (*s_f)[3], uint32_t* s_bad) {
+    const uint32_t count = lig.count;
     bool bad = false;
     if (tid < a.G) {
         const float r = (float)pose_units_sum(a.slab + (size_t)pose * (POSE_UNITS + 1u) * a.G + tid, a.G);
@@ -449,8 +495,8 @@ __device__ __forceinline__ void step_gather(const StepArgs& a, uint32_t pose, ui
         bad = !isfinite(r);
     }
     if (tid < count) {
-        const double* s = a.fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + tid) * 3u;
-        const size_t at = ((size_t)pose * count + tid) * 3u;
+        const double* s = lig.units(a.fslab, tid);
+        const size_t at = lig.at(tid);
         for (uint32_t c = 0; c < 3u; ++c) {
             const double v = pose_units_sum(s + c, (size_t)count * 3u);
             s_v[tid][c] = v; s_x[tid][c] = (double)a.stage[at + c];
@@ -463,16 +509,17 @@ __device__ __forceinline__ void step_gather(const StepArgs& a, uint32_t pose, ui
 }
 
 // the accepted state leaves for the chunk's block: coordinates, row and rigid of a stored trial; the input pose at evaluation 1
-__device__ __forceinline__ void step_store(const StepArgs& a, uint32_t pose, uint32_t tid, uint32_t fl, bool first, const float* s_row,
-                                           const float* s_rigid) {
-    const size_t at = ((size_t)pose * a.count + tid) * 3u;
+template <bool GUEST>
+__device__ __forceinline__ void step_store(const StepArgs& a, const StepLigand<GUEST>& lig, uint32_t pose, uint32_t tid, uint32_t fl, bool first,
+                                           const float* s_row, const float* s_rigid) {
+    const size_t at = lig.at(tid);
     if (fl & MDX_RF_STORE) {
-        if (tid < a.count)
+        if (tid < lig.count)
             for (uint32_t c = 0; c < 3u; ++c) a.y[at + c] = a.stage[at + c];
         if (tid < a.G) a.row[(size_t)pose * a.G + tid] = s_row[tid];
         if (tid < 6u) a.rigid[(size_t)pose * 6u + tid] = s_rigid[tid];
     }
-    if (first && tid < a.count)
+    if (first && tid < lig.count)
         for (uint32_t c = 0; c < 3u; ++c) a.x0[at + c] = a.stage[at + c];
 }
 
@@ -516,8 +563,9 @@ __device__ __forceinline__ void pose_build_torsions(double (*s_x)[3], const mdx_
 // while thread i gathers the forces of the terms that name atom i, in list order), g_k / J_k (thread k, members in atom order), the
 // torsion part of the atom field, and the trial builder: B(theta) in LDS from the input pose, then the rigid image of it.  The rigid
 // instantiation names none of the FLEX arrays (they take no LDS there) and forms the next trial from x0 by rf_coords.
-template <bool FLEX>
+template <bool FLEX, bool GUEST = false>
 __device__ __forceinline__ void pose_step(const StepArgs& a) {
+    static_assert(!(FLEX && GUEST), "guest ligands: the rigid refinement only");
     using State = typename std::conditional<FLEX, mdx_fx_state, mdx_rf_state>::type;
     // s_f, s_g .. s_bc, s_edih and s_tor are FLEX only.  The rigid instantiation must read and write none of them (s_f is handed to
     // step_gather<false>, which does not touch it): an array nobody uses takes no LDS, and that is all that keeps the rigid kernel at
@@ -530,8 +578,10 @@ __device__ __forceinline__ void pose_step(const StepArgs& a) {
     __shared__ State s_st;
     __shared__ mdx_fx_torsion s_tor[MDX_FX_MAX_TORSIONS];
     __shared__ uint32_t s_bad, s_flags;
-    const uint32_t tid = threadIdx.x, pose = blockIdx.x, count = a.count, T = a.T;
+    const uint32_t tid = threadIdx.x, pose = blockIdx.x, T = a.T;
     if (a.frozen[pose] != 0u) return;      // (uniform over the workgroup, before any barrier)
+    const StepLigand<GUEST> lig(a.rec, a.count, pose);
+    const uint32_t count = lig.count;
     uint32_t* const rec = (uint32_t*)((State*)a.st + pose);
     for (uint32_t i = tid; i < sizeof(State) / 4u; i += 256u) ((uint32_t*)&s_st)[i] = rec[i];
     if constexpr (FLEX)
@@ -539,7 +589,7 @@ __device__ __forceinline__ void pose_step(const StepArgs& a) {
     if (tid == 0u) s_bad = 0u;
     __syncthreads();
     mdx_rf_state& rf = rf_of(s_st);
-    step_gather<FLEX>(a, pose, tid, s_row, s_v, s_x, s_f, &s_bad);      // (s_f: written under FLEX only)
+    step_gather<FLEX>(a, lig, pose, tid, s_row, s_v, s_x, s_f, &s_bad);      // (s_f: written under FLEX only)
     // centroid | barrier | rigid by the statement of pose_force_sum_kernel beside the six inertia sums on a wave of their own; the
     // FLEX parts share those two intervals, so the three statements stand here and not in a helper
     if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
@@ -622,7 +672,7 @@ __device__ __forceinline__ void pose_step(const StepArgs& a) {
     if constexpr (FLEX)
         if (s_flags == MDX_RF_STORE && tid < T) s_st.wk[tid] = s_wk[tid];      // (read again only after the next barrier)
     uint32_t fl = s_flags;
-    step_store(a, pose, tid, fl, rf.evals == 1u, s_row, s_rigid);
+    step_store(a, lig, pose, tid, fl, rf.evals == 1u, s_row, s_rigid);
     if (fl == MDX_RF_STORE) {
         double m = 0.0;
         if (tid < count) {
@@ -634,7 +684,7 @@ __device__ __forceinline__ void pose_step(const StepArgs& a) {
         }
         fl = step_max_speed(m, tid, fl, rf, s_m, &s_flags);
     }
-    const size_t at = ((size_t)pose * count + tid) * 3u;
+    const size_t at = lig.at(tid);
     if (!(fl & MDX_RF_FROZEN)) {
         if (tid == 0u) {
             if constexpr (FLEX) fx_trial(s_st, T); else rf_trial(rf);
@@ -673,11 +723,19 @@ __device__ __forceinline__ void pose_step(const StepArgs& a) {
 // object; it measured 0.5 % slower in the flexible arm and no cause was found in the instructions - DESIGN.md 7h.)
 __global__ __launch_bounds__(256) void pose_refine_step_kernel(StepArgs a) { pose_step<false>(a); }
 __global__ __launch_bounds__(256) void pose_flex_step_kernel(StepArgs a) { pose_step<true>(a); }
+__global__ __launch_bounds__(256) void guest_refine_step_kernel(StepArgs a) { pose_step<false, true>(a); }
 
 template <int COUL>
 static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force, bool refine = false, bool guest = false) {
     const dim3 g(POSE_UNITS + 1u, n), b(256);
-    if (guest) {
+    if (guest && (force || refine)) {
+        const size_t lds = sizeof(double) * 12u * (((a.count + 7u) >> 3) << 3);      // (a.count: the chunk's largest ligand)
+        if (refine) {
+            if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, true, true, true>), g, b, lds, h->stream, a);
+            else hipLaunchKernelGGL((pose_score_kernel<COUL, false, true, true, true>), g, b, lds, h->stream, a);
+        } else if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, true, false, true>), g, b, lds, h->stream, a);
+        else hipLaunchKernelGGL((pose_score_kernel<COUL, false, true, false, true>), g, b, lds, h->stream, a);
+    } else if (guest) {
         if (geom) hipLaunchKernelGGL((pose_score_kernel<COUL, true, false, false, true>), g, b, 0, h->stream, a);
         else hipLaunchKernelGGL((pose_score_kernel<COUL, false, false, false, true>), g, b, 0, h->stream, a);
     } else if (refine) {
@@ -896,250 +954,8 @@ extern "C" int mdx_pose_forces(mdx_handle* h, uint32_t first, uint32_t count, ui
     return pose_run(h, "mdx_pose_forces", first, count, n_poses, poses, rows_or_null, n_groups, forces, rigid_or_null);
 }
 
-// ---- mdx_screen_ligands: a library of guest ligands against the resident atoms ---------------------------------------------------------------
-// A guest is described by the caller and never enters the handle: its charge / LJ rows, class map and 1-4 records are staged per chunk
-// beside its poses (GuestLayout), a PoseRec per pose says where, and the GUEST instantiation of pose_score_kernel reads them where the
-// resident one goes through slot_of and the handle's table.  Rows are n_groups + 1 wide: every resident group, then the ligand's own
-// pairs.  Nothing of the handle's state or of the resident-pose cache (ps_*) is written.
-struct GuestBest { double score; uint32_t pose, pad; };      // smallest row sum of a ligand so far and its ligand-local pose
-
-// The best pose of every ligand that has poses in the chunk: the thread of the first such pose walks the ligand's run in pose order
-// (lig_of[p] = (ligand, ligand-local pose); a ligand's poses are consecutive), S = the fp32-rounded row added in column order in fp64 -
-// what a host gets from the returned rows - and a strictly smaller S replaces the carried one: the lowest index wins a tie, also
-// across chunks.  One writer per ligand, no atomics.
-__global__ __launch_bounds__(256) void guest_best_kernel(uint32_t n, uint32_t W, const double* __restrict__ rows, const uint2* __restrict__ lig_of,
-                                                         GuestBest* __restrict__ best) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const uint32_t m = lig_of[p].x;
-    if (p > 0u && lig_of[p - 1u].x == m) return;
-    GuestBest b = best[m];
-    for (uint32_t k = p; k < n && lig_of[k].x == m; ++k) {
-        double S = 0.0;
-        for (uint32_t c = 0; c < W; ++c) S += (double)(float)rows[(size_t)k * W + c];
-        if (S < b.score) { b.score = S; b.pose = lig_of[k].y; }
-    }
-    best[m] = b;
-}
-
-// The device block of one chunk of n guest poses: what the host stages ([0, up_end): records, (ligand, pose) words, charge and LJ rows
-// of the chunk's ligands, their 1-4 records, the coordinates, the class maps), then the units' slab and the summed rows.
-struct GuestLayout {
-    size_t rec, ligof, q, lj, p14, xyz, cls, up_end, slab, rows, end;
-    GuestLayout(size_t n, size_t atoms, size_t n14, size_t nxyz, size_t ncls, uint32_t W) {
-        auto al = [](size_t x) { return (x + 15u) / 16u * 16u; };
-        rec = 0;
-        ligof = al(rec + sizeof(PoseRec) * n);
-        q = al(ligof + sizeof(uint2) * n);
-        lj = al(q + sizeof(float) * atoms);
-        p14 = al(lj + sizeof(float2) * atoms);
-        xyz = al(p14 + sizeof(Pose14) * n14);
-        cls = al(xyz + sizeof(float) * nxyz);
-        up_end = cls + ncls;
-        slab = al(up_end);
-        rows = slab + sizeof(double) * n * (POSE_UNITS + 1u) * W;
-        end = rows + sizeof(double) * n * W;
-    }
-};
-
-// A guest's own pairs: the class map [count^2] (0 plain, 1 excluded, 2 scaled 1-4) of its two pair lists; null, or why the lists are refused
-static const char* guest_class_map(const mdx_guest_ligand& g, std::vector<uint8_t>& cls) {
-    const uint32_t n = g.count;
-    cls.assign((size_t)n * n, 0);
-    for (int list = 0; list < 2; ++list) {
-        const uint32_t np = list ? g.n_pairs14 : g.n_excl;
-        const uint32_t* pr = list ? g.pairs14 : g.excl_pairs;
-        const uint8_t mine = list ? 2 : 1;
-        for (uint32_t k = 0; k < np; ++k) {
-            const uint32_t a = pr[2 * (size_t)k], b = pr[2 * (size_t)k + 1];
-            if (a >= n || b >= n) return "a pair names an atom outside the ligand";
-            if (a == b) return "a pair of an atom with itself";
-            uint8_t& c = cls[(size_t)a * n + b];
-            if (c != 0 && c != mine) return "a pair is in both the exclusion and the 1-4 list";
-            c = mine; cls[(size_t)b * n + a] = mine;
-        }
-    }
-    return nullptr;
-}
-
-extern "C" int mdx_screen_ligands(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, float* rows_out, uint32_t n_groups,
-                                  uint32_t* best_pose, double* best_score) {
-    const std::string who = "mdx_screen_ligands";
-    if (!h) FAIL(MDX_EPARAM, "null handle");
-    if (n_ligands == 0) return MDX_OK;
-    if (!ligs) FAIL(MDX_EPARAM, "null argument");
-    const uint32_t G = h->n_grp, W = G + 1u;
-    if (!G) FAIL(MDX_EPARAM, "no energy groups are set (mdx_set_energy_groups)");
-    if (n_groups != G) FAIL(MDX_EPARAM, "n_groups must be the number of groups (mdx_energy_group_count)");
-    if (h->dd || h->n_local != h->N) FAIL(MDX_EPARAM, who + " on a decomposed handle (single-device handles only)");
-    if (h->alch_on) FAIL(MDX_EPARAM, who + " while an alchemical window is active");
-    std::vector<size_t> pstart((size_t)n_ligands + 1, 0);      // first pose of every ligand in the library's pose order
-    std::vector<uint8_t> cls;
-    for (uint32_t m = 0; m < n_ligands; ++m) {
-        const mdx_guest_ligand& g = ligs[m];
-        const std::string lig = who + ": ligand " + std::to_string(m) + ": ";
-        if (g.count == 0 || g.count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, lig + "count must be in 1..MDX_POSE_MAX_ATOMS (256)");
-        if (!g.charge || !g.lj_sigma || !g.lj_eps || (g.n_excl && !g.excl_pairs) || (g.n_pairs14 && !g.pairs14) || (g.n_poses && !g.poses))
-            FAIL(MDX_EPARAM, lig + "null argument");
-        for (uint32_t i = 0; i < g.count; ++i) {
-            if (!std::isfinite(g.charge[i]) || !std::isfinite(g.lj_sigma[i]) || !std::isfinite(g.lj_eps[i]))
-                FAIL(MDX_EPARAM, lig + "non-finite charge, sigma or eps");
-            if (g.lj_sigma[i] < 0.f || g.lj_eps[i] < 0.f) FAIL(MDX_EPARAM, lig + "negative sigma or eps");
-        }
-        if (const char* why = guest_class_map(g, cls)) FAIL(MDX_EPARAM, lig + why);
-        const size_t nx = 3 * (size_t)g.count * g.n_poses;
-        for (size_t k = 0; k < nx; ++k)
-            if (!std::isfinite(g.poses[k])) FAIL(MDX_EPARAM, lig + "non-finite pose coordinate");
-        pstart[m + 1] = pstart[m] + g.n_poses;
-    }
-    const size_t total = pstart[n_ligands];
-    if (total == 0) return MDX_OK;
-    if (!rows_out) FAIL(MDX_EPARAM, "null argument");
-    const bool want_best = best_pose || best_score;
-
-    HIP_TRY(hipSetDevice(h->device));
-    MDX_TRY(mdx_ensure_ready(h));          // what the matrix would see: list, constraints and virtual sites of the current state
-    DeviceState& d = h->d;
-    hipStream_t st = h->stream;
-
-    // the chunks: POSE_CHUNK consecutive poses of the library; every chunk names the ligands it holds poses of (first .. last)
-    struct Chunk { size_t p0; uint32_t n, m0, m1; size_t atoms, n14, nxyz, ncls; };
-    std::vector<Chunk> chunks;
-    size_t need = 0;
-    {
-        uint32_t m = 0;
-        for (size_t p0 = 0; p0 < total; p0 += POSE_CHUNK) {
-            Chunk c{p0, (uint32_t)std::min<size_t>(POSE_CHUNK, total - p0), 0, 0, 0, 0, 0, 0};
-            while (pstart[m + 1] <= p0) ++m;
-            c.m0 = m;
-            for (uint32_t k = m; k < n_ligands && pstart[k] < p0 + c.n; ++k) {
-                if (ligs[k].n_poses == 0) continue;
-                const size_t cnt = ligs[k].count, np = std::min(pstart[k + 1], p0 + c.n) - std::max(pstart[k], p0);
-                c.m1 = k; c.atoms += cnt; c.ncls += cnt * cnt; c.nxyz += 3 * cnt * np;
-                c.n14 += (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) ? 0u : ligs[k].n_pairs14;
-            }
-            need = std::max(need, GuestLayout(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W).end);
-            chunks.push_back(c);
-        }
-    }
-    MDX_TRY(pose_grow(&d.gs_blk, h->gs_cap_blk, need));
-    std::vector<GuestBest> best;
-    if (want_best) {
-        best.assign(n_ligands, GuestBest{INFINITY, 0xFFFFFFFFu, 0u});
-        MDX_TRY(pose_grow(&d.gs_best, h->gs_cap_best, sizeof(GuestBest) * best.size()));
-        HIP_TRY(hipMemcpyAsync(d.gs_best, best.data(), sizeof(GuestBest) * best.size(), hipMemcpyHostToDevice, st));
-    }
-
-    PoseArgs a{};
-    int mode = 0; bool geom = false, samecut = false;
-    mdx_fill_nb_params(h, a.p, &mode, &geom, &samecut);
-    a.g = h->grid;
-    a.posq = d.posq; a.lj = d.lj; a.orig_of = d.orig_of; a.gid = d.gid; a.grp = d.grp; a.slot_of = d.slot_of;
-    a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
-    a.G = G; a.L = 0xFFFFFFFFu;
-    a.r_cull = std::isfinite(h->r_list) ? h->r_list + 0.01f : INFINITY;
-    for (int k = 0; k < 3; ++k) {
-        a.box[k] = h->per[k] ? h->box_hi[k] - h->box_lo[k] : 0.f;
-        a.inv_box[k] = h->per[k] ? 1.0f / a.box[k] : 0.f;
-    }
-    const mdx_config& cfg = h->cfg;
-    const bool lj_off = (cfg.overrides & MDX_OVR_LJ_DISABLED) != 0, coul_off = (cfg.overrides & MDX_OVR_COULOMB_DISABLED) != 0;
-    const bool skip14 = (cfg.overrides & MDX_OVR_BONDED_DISABLED) != 0, geometric = cfg.combining_rule == MDX_COMBINE_GEOMETRIC;
-    const float sqrt_ke = std::sqrt(cfg.coulomb_k);
-
-    std::vector<float> res(total * W);
-    std::vector<double> rows((size_t)std::min<size_t>(total, POSE_CHUNK) * W);
-    std::vector<unsigned char> up;
-    unsigned char* blk = (unsigned char*)d.gs_blk;
-    for (const Chunk& c : chunks) {
-        const GuestLayout lay(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W);
-        up.assign(lay.up_end, 0);
-        PoseRec* rec = (PoseRec*)(up.data() + lay.rec);
-        uint2* ligof = (uint2*)(up.data() + lay.ligof);
-        float* gq = (float*)(up.data() + lay.q);
-        float2* glj = (float2*)(up.data() + lay.lj);
-        Pose14* p14 = (Pose14*)(up.data() + lay.p14);
-        float* xyz = (float*)(up.data() + lay.xyz);
-        uint32_t atom = 0, n14 = 0, nx = 0, ncls = 0, p = 0;
-        for (uint32_t m = c.m0; m <= c.m1; ++m) {
-            const mdx_guest_ligand& g = ligs[m];
-            if (g.n_poses == 0) continue;
-            const uint32_t cnt = g.count;
-            // rows and records as mdx_create makes a resident atom's: the overrides zero eps and charge first
-            std::vector<float2> raw(cnt);
-            std::vector<float> q(cnt);
-            for (uint32_t i = 0; i < cnt; ++i) {
-                raw[i] = make_float2(g.lj_sigma[i], lj_off ? 0.f : g.lj_eps[i]);
-                q[i] = coul_off ? 0.f : g.charge[i];
-                gq[atom + i] = q[i] * sqrt_ke;
-                glj[atom + i] = mdx_pack_lj(geometric, raw[i].x, raw[i].y);
-            }
-            (void)guest_class_map(g, cls);
-            std::memcpy(up.data() + lay.cls + ncls, cls.data(), cls.size());
-            const uint32_t first14 = n14;
-            for (uint32_t k = 0; !skip14 && k < g.n_pairs14; ++k) {
-                const uint32_t i = g.pairs14[2 * (size_t)k], j = g.pairs14[2 * (size_t)k + 1];
-                const float4 prm = mdx_pair14_params(cfg, raw[i], raw[j], q[i], q[j]);
-                p14[n14++] = Pose14{i, j, prm.x, prm.y, prm.z};
-            }
-            const size_t l0 = std::max(pstart[m], c.p0) - pstart[m], l1 = std::min(pstart[m + 1], c.p0 + c.n) - pstart[m];
-            for (size_t l = l0; l < l1; ++l, ++p) {
-                rec[p] = PoseRec{atom, cnt, ncls, first14, n14 - first14, nx};
-                ligof[p] = make_uint2(m, (uint32_t)l);
-                std::memcpy(xyz + nx, g.poses + 3 * (size_t)cnt * l, sizeof(float) * 3 * cnt);
-                nx += 3 * cnt;
-            }
-            atom += cnt; ncls += cnt * cnt;
-        }
-        HIP_TRY(hipMemcpyAsync(blk, up.data(), lay.up_end, hipMemcpyHostToDevice, st));
-        a.rec = (const PoseRec*)(blk + lay.rec);
-        a.gq = (const float*)(blk + lay.q); a.glj = (const float2*)(blk + lay.lj);
-        a.cls = blk + lay.cls; a.p14 = (const Pose14*)(blk + lay.p14);
-        a.poses = (const float*)(blk + lay.xyz);
-        a.slab = (double*)(blk + lay.slab);
-        double* drows = (double*)(blk + lay.rows);
-        mdx_prof_begin(h, 0);
-        pose_launch(h, a, mode, geom, c.n, false, false, true);
-        hipLaunchKernelGGL(pose_sum_kernel, dim3((c.n * W + 255u) / 256u), dim3(256), 0, st, c.n, W, a.slab, drows);
-        if (want_best)
-            hipLaunchKernelGGL(guest_best_kernel, dim3((c.n + 255u) / 256u), dim3(256), 0, st, c.n, W, drows, (const uint2*)(blk + lay.ligof),
-                               (GuestBest*)d.gs_best);
-        mdx_prof_end(h);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(rows.data(), drows, sizeof(double) * (size_t)c.n * W, hipMemcpyDeviceToHost, st));
-        if (want_best && &c == &chunks.back())
-            HIP_TRY(hipMemcpyAsync(best.data(), d.gs_best, sizeof(GuestBest) * best.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t k = 0; k < (size_t)c.n * W; ++k) {
-            if (!std::isfinite(rows[k])) FAIL(MDX_ENAN, who + ": non-finite energy in a row");
-            res[c.p0 * W + k] = (float)rows[k];
-        }
-    }
-    std::memcpy(rows_out, res.data(), sizeof(float) * res.size());
-    for (uint32_t m = 0; want_best && m < n_ligands; ++m) {
-        if (best_pose) best_pose[m] = best[m].pose;
-        if (best_score) best_score[m] = best[m].score;
-    }
-    return MDX_OK;
-}
-
 // ---- mdx_refine_poses and mdx_refine_poses_flex: one loop, the rigid and the flexible state record ---------------------------------------
-// The refinement's device block of a chunk of n poses (ps_flex): [frozen words | state records | accepted coordinates | rows | rigid |
-// input poses | the dihedral terms' energies and forces]; the first two are zeroed at the start of the chunk, records .. rigid come
-// back in one copy at its end.  state_bytes is sizeof(mdx_rf_state) or sizeof(mdx_fx_state); the rigid refinement has no terms.
-struct StepLayout {
-    size_t frozen, state, y, row, rigid, x0, eterm, end;
-    StepLayout(uint32_t n, size_t per_pose, uint32_t G, size_t state_bytes, uint32_t n_terms) {
-        frozen = 0;
-        state = ((sizeof(uint32_t) * n + 15u) / 16u) * 16u;
-        y = state + state_bytes * n;
-        row = y + sizeof(float) * per_pose * n;
-        rigid = row + sizeof(float) * (size_t)G * n;
-        x0 = rigid + sizeof(float) * 6u * n;
-        eterm = ((x0 + sizeof(float) * per_pose * n + 15u) / 16u) * 16u;
-        end = eterm + sizeof(double) * FLEX_TERM_WORDS * (size_t)n_terms * n;
-    }
-};
+// (StepLayout - the refinement's device block of a chunk - stands in mdx_pose_plan.h)
 
 // The table of one (range, torsion list, flags): the torsions with their moving-set masks, the ligand's dihedral terms in the system's
 // list order, and per ligand atom the (term, role) entries that name it, in list order too - the atom-owned gather.
@@ -1167,13 +983,13 @@ static int refine_opts_check(const std::string& who, const mdx_flex_opts& opts, 
     return MDX_OK;
 }
 
-// the step kernel's arguments for a chunk laid out by `lay`; flex: with the torsion table of flex_table (T torsions, n_terms terms)
-static StepArgs step_args(mdx_handle* h, const PoseArgs& a, uint32_t count, bool flex, uint32_t T, uint32_t n_terms, const StepLayout& lay,
-                          const mdx_fx_opts& o) {
+// the step kernel's arguments for a chunk laid out by `lay` at blk, behind the force pass of `a` (it evaluates the staged trial a.poses
+// into a.slab and a.fslab; W: the width of its rows); flex: with the torsion table of flex_table (T torsions, n_terms terms)
+static StepArgs step_args(mdx_handle* h, const PoseArgs& a, unsigned char* blk, uint32_t count, uint32_t W, bool flex, uint32_t T,
+                          uint32_t n_terms, const StepLayout& lay, const mdx_fx_opts& o) {
     DeviceState& d = h->d;
-    unsigned char* blk = (unsigned char*)d.ps_flex;
     StepArgs r{};
-    r.count = count; r.G = h->n_grp; r.T = T; r.n_terms = n_terms; r.stage = d.ps_stage; r.slab = d.ps_slab; r.fslab = d.ps_fslab;
+    r.count = count; r.G = W; r.T = T; r.n_terms = n_terms; r.stage = const_cast<float*>(a.poses); r.slab = a.slab; r.fslab = a.fslab;
     r.frozen = (uint32_t*)(blk + lay.frozen); r.st = blk + lay.state;
     r.y = (float*)(blk + lay.y); r.row = (float*)(blk + lay.row); r.rigid = (float*)(blk + lay.rigid); r.x0 = (float*)(blk + lay.x0);
     if (flex) {
@@ -1188,11 +1004,12 @@ static StepArgs step_args(mdx_handle* h, const PoseArgs& a, uint32_t count, bool
     return r;
 }
 
-// one evaluation of a chunk: the REFINE force pass, then the step kernel
+// one evaluation of a chunk: the REFINE force pass, then the step kernel (guests: r.rec is set, and the refinement is the rigid one)
 template <bool FLEX>
 static void step_evaluate(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, const StepArgs& r) {
-    pose_launch(h, a, mode, geom, n, true, true);
-    if (FLEX) hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
+    pose_launch(h, a, mode, geom, n, true, true, r.rec != nullptr);
+    if (r.rec) hipLaunchKernelGGL(guest_refine_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
+    else if (FLEX) hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
     else hipLaunchKernelGGL(pose_refine_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
 }
 
@@ -1223,16 +1040,16 @@ static int refine_chunks(mdx_handle* h, PoseArgs& a, int mode, bool geom, uint32
     hipStream_t st = h->stream;
     const uint32_t G = h->n_grp, X = 7u + T;
     const size_t per_pose = 3 * (size_t)count;
-    MDX_TRY(pose_grow(&d.ps_flex, h->ps_cap_flex, StepLayout(POSE_CHUNK, per_pose, G, sizeof(State), n_terms).end));
+    MDX_TRY(pose_grow(&d.ps_flex, h->ps_cap_flex, StepLayout(POSE_CHUNK, per_pose * POSE_CHUNK, G, sizeof(State), n_terms).end));
     std::vector<float> yres(per_pose * n_poses), rres((size_t)n_poses * G), gres(6u * (size_t)n_poses), xres((size_t)X * n_poses),
         dres(FLEX ? n_poses : 0u), tres((size_t)T * n_poses);
     std::vector<uint32_t> sres(n_poses), eres(n_poses);
     std::vector<unsigned char> back;
     for (uint32_t p0 = 0; p0 < n_poses; p0 += POSE_CHUNK) {
         const uint32_t n = std::min(POSE_CHUNK, n_poses - p0);
-        const StepLayout lay(n, per_pose, G, sizeof(State), n_terms);
+        const StepLayout lay(n, per_pose * n, G, sizeof(State), n_terms);
         unsigned char* blk = (unsigned char*)d.ps_flex;
-        const StepArgs r = step_args(h, a, count, FLEX, T, n_terms, lay, o);
+        const StepArgs r = step_args(h, a, blk, count, G, FLEX, T, n_terms, lay, o);
         a.frozen = r.frozen;
         HIP_TRY(hipMemcpyAsync(d.ps_stage, poses + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(blk, 0, lay.y, st));
@@ -1509,7 +1326,7 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
     hipStream_t st = h->stream;
     const uint32_t G = h->n_grp, T = n_torsions, n_terms = h->fx_terms;
     const size_t per_pose = 3 * (size_t)count;
-    MDX_TRY(pose_grow(&d.ps_flex, h->ps_cap_flex, StepLayout(POSE_CHUNK, per_pose, G, sizeof(mdx_fx_state), n_terms).end));
+    MDX_TRY(pose_grow(&d.ps_flex, h->ps_cap_flex, StepLayout(POSE_CHUNK, per_pose * POSE_CHUNK, G, sizeof(mdx_fx_state), n_terms).end));
     MDX_TRY(pose_grow(&d.ps_search, h->ps_cap_search, SearchLayout(POSE_CHUNK, per_pose, G).end));
     std::vector<float> yres(per_pose * n_walkers), rres((size_t)n_walkers * G), dres(n_walkers);
     std::vector<double> scres(n_walkers);
@@ -1518,10 +1335,10 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
     std::vector<unsigned char> back;
     for (uint32_t p0 = 0; p0 < n_walkers; p0 += POSE_CHUNK) {
         const uint32_t n = std::min(POSE_CHUNK, n_walkers - p0);
-        const StepLayout lay(n, per_pose, G, sizeof(mdx_fx_state), n_terms);
+        const StepLayout lay(n, per_pose * n, G, sizeof(mdx_fx_state), n_terms);
         const SearchLayout sl(n, per_pose, G);
         unsigned char* sb = (unsigned char*)d.ps_search;
-        const StepArgs r = step_args(h, a, count, true, T, n_terms, lay, o);
+        const StepArgs r = step_args(h, a, (unsigned char*)d.ps_flex, count, G, true, T, n_terms, lay, o);
         a.frozen = r.frozen;
         SearchArgs s{};
         s.count = count; s.G = G; s.T = T; s.stage = d.ps_stage; s.frozen = r.frozen; s.st = (mdx_fx_state*)r.st; s.y = r.y; s.row = r.row; s.rigid = r.rigid;
@@ -1560,5 +1377,348 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
     if (best_dih_out_or_null) std::memcpy(best_dih_out_or_null, dres.data(), sizeof(float) * dres.size());
     if (best_round_out_or_null) std::memcpy(best_round_out_or_null, brres.data(), sizeof(uint32_t) * brres.size());
     if (stats_out_or_null) std::memcpy(stats_out_or_null, stres.data(), sizeof(uint32_t) * stres.size());
+    return MDX_OK;
+}
+
+// ---- guest ligands: mdx_screen_ligands, mdx_guest_forces, mdx_refine_guests -------------------------------------------------------------------
+// A guest is described by the caller and never enters the handle: its charge / LJ rows, class map and 1-4 records are staged per chunk
+// beside its poses (GuestLayout), a PoseRec per pose says where, and the GUEST instantiations of pose_score_kernel read them where the
+// resident ones go through slot_of and the handle's table.  Rows are n_groups + 1 wide: every resident group, then the ligand's own
+// pairs.  Nothing of the handle's state or of the resident-pose cache (ps_*) is written: a chunk's whole block - staged tables, slabs,
+// sums and, for a refinement, its StepLayout - lies in gs_blk.  The three entry points share the checks (guest_check), the plan
+// (mdx_pose_plan.h), the kernel arguments (guest_ready) and the staging of a chunk (guest_stage).
+struct GuestBest { double score; uint32_t pose, pad; };      // smallest row sum of a ligand so far and its ligand-local pose
+
+// The best pose of every ligand that has poses in the chunk: the thread of the first such pose walks the ligand's run in pose order
+// (lig_of[p] = (ligand, ligand-local pose); a ligand's poses are consecutive), S = the fp32-rounded row added in column order in fp64 -
+// what a host gets from the returned rows - and a strictly smaller S replaces the carried one: the lowest index wins a tie, also
+// across chunks.  One writer per ligand, no atomics.  Row: double (the summed rows of mdx_screen_ligands) or float (the accepted rows
+// of a refinement; st: its state records - a pose that ended MDX_REFINE_NONFINITE is passed over whatever its row holds).
+template <class Row>
+__device__ __forceinline__ void guest_best(uint32_t n, uint32_t W, const Row* __restrict__ rows, const uint2* __restrict__ lig_of,
+                                           const mdx_rf_state* __restrict__ st, GuestBest* __restrict__ best) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t m = lig_of[p].x;
+    if (p > 0u && lig_of[p - 1u].x == m) return;
+    GuestBest b = best[m];
+    for (uint32_t k = p; k < n && lig_of[k].x == m; ++k) {
+        if (st && st[k].frozen != 0u && st[k].status == MDX_RF_NONFINITE) continue;
+        double S = 0.0;
+        for (uint32_t c = 0; c < W; ++c) S += (double)(float)rows[(size_t)k * W + c];
+        if (S < b.score) { b.score = S; b.pose = lig_of[k].y; }
+    }
+    best[m] = b;
+}
+__global__ __launch_bounds__(256) void guest_best_kernel(uint32_t n, uint32_t W, const double* __restrict__ rows, const uint2* __restrict__ lig_of,
+                                                         GuestBest* __restrict__ best) {
+    guest_best(n, W, rows, lig_of, nullptr, best);
+}
+__global__ __launch_bounds__(256) void guest_best_refined_kernel(uint32_t n, uint32_t W, const float* __restrict__ rows,
+                                                                 const uint2* __restrict__ lig_of, const mdx_rf_state* __restrict__ st,
+                                                                 GuestBest* __restrict__ best) {
+    guest_best(n, W, rows, lig_of, st, best);
+}
+
+// A guest's own pairs: the class map [count^2] (0 plain, 1 excluded, 2 scaled 1-4) of its two pair lists; null, or why the lists are refused
+static const char* guest_class_map(const mdx_guest_ligand& g, std::vector<uint8_t>& cls) {
+    const uint32_t n = g.count;
+    cls.assign((size_t)n * n, 0);
+    for (int list = 0; list < 2; ++list) {
+        const uint32_t np = list ? g.n_pairs14 : g.n_excl;
+        const uint32_t* pr = list ? g.pairs14 : g.excl_pairs;
+        const uint8_t mine = list ? 2 : 1;
+        for (uint32_t k = 0; k < np; ++k) {
+            const uint32_t a = pr[2 * (size_t)k], b = pr[2 * (size_t)k + 1];
+            if (a >= n || b >= n) return "a pair names an atom outside the ligand";
+            if (a == b) return "a pair of an atom with itself";
+            uint8_t& c = cls[(size_t)a * n + b];
+            if (c != 0 && c != mine) return "a pair is in both the exclusion and the 1-4 list";
+            c = mine; cls[(size_t)b * n + a] = mine;
+        }
+    }
+    return nullptr;
+}
+
+// A call on a library: its plan, the kernel arguments, the staging buffer
+struct GuestRun {
+    std::vector<GuestShape> shapes;
+    std::vector<size_t> pstart;
+    std::vector<GuestChunk> chunks;
+    std::vector<GuestSlot> slots;
+    std::vector<unsigned char> up;
+    std::vector<GuestBest> best;
+    size_t total = 0;
+    PoseArgs a{};
+    int mode = 0; bool geom = false;
+};
+
+// the refusals that need no device, then the plan
+static int guest_check(mdx_handle* h, const std::string& who, uint32_t n_ligands, const mdx_guest_ligand* ligs, uint32_t n_groups, GuestRun& run) {
+    const uint32_t G = h->n_grp;
+    if (!G) FAIL(MDX_EPARAM, "no energy groups are set (mdx_set_energy_groups)");
+    if (n_groups != G) FAIL(MDX_EPARAM, "n_groups must be the number of groups (mdx_energy_group_count)");
+    if (h->dd || h->n_local != h->N) FAIL(MDX_EPARAM, who + " on a decomposed handle (single-device handles only)");
+    if (h->alch_on) FAIL(MDX_EPARAM, who + " while an alchemical window is active");
+    const bool skip14 = (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) != 0;
+    std::vector<uint8_t> cls;
+    run.shapes.resize(n_ligands);
+    for (uint32_t m = 0; m < n_ligands; ++m) {
+        const mdx_guest_ligand& g = ligs[m];
+        const std::string lig = who + ": ligand " + std::to_string(m) + ": ";
+        if (g.count == 0 || g.count > MDX_POSE_MAX_ATOMS) FAIL(MDX_EPARAM, lig + "count must be in 1..MDX_POSE_MAX_ATOMS (256)");
+        if (!g.charge || !g.lj_sigma || !g.lj_eps || (g.n_excl && !g.excl_pairs) || (g.n_pairs14 && !g.pairs14) || (g.n_poses && !g.poses))
+            FAIL(MDX_EPARAM, lig + "null argument");
+        for (uint32_t i = 0; i < g.count; ++i) {
+            if (!std::isfinite(g.charge[i]) || !std::isfinite(g.lj_sigma[i]) || !std::isfinite(g.lj_eps[i]))
+                FAIL(MDX_EPARAM, lig + "non-finite charge, sigma or eps");
+            if (g.lj_sigma[i] < 0.f || g.lj_eps[i] < 0.f) FAIL(MDX_EPARAM, lig + "negative sigma or eps");
+        }
+        if (const char* why = guest_class_map(g, cls)) FAIL(MDX_EPARAM, lig + why);
+        const size_t nx = 3 * (size_t)g.count * g.n_poses;
+        for (size_t k = 0; k < nx; ++k)
+            if (!std::isfinite(g.poses[k])) FAIL(MDX_EPARAM, lig + "non-finite pose coordinate");
+        run.shapes[m] = GuestShape{g.count, g.n_poses, skip14 ? 0u : g.n_pairs14};
+    }
+    guest_plan(run.shapes, run.pstart, run.chunks);
+    run.total = run.pstart[n_ligands];
+    return MDX_OK;
+}
+
+static GuestLayout guest_layout(const GuestChunk& c, uint32_t W, int gmode) {
+    return GuestLayout(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W, gmode, sizeof(mdx_rf_state));
+}
+
+// the device side of a call that has work: the list of the current state, the block (it follows the largest chunk), the carried best
+// poses, the kernel's arguments but for the chunk's pointers
+static int guest_ready(mdx_handle* h, uint32_t n_ligands, int gmode, bool want_best, GuestRun& run) {
+    HIP_TRY(hipSetDevice(h->device));
+    MDX_TRY(mdx_ensure_ready(h));          // what the matrix would see: list, constraints and virtual sites of the current state
+    DeviceState& d = h->d;
+    const uint32_t G = h->n_grp;
+    size_t need = 0;
+    for (const GuestChunk& c : run.chunks) need = std::max(need, guest_layout(c, G + 1u, gmode).end);
+    MDX_TRY(pose_grow(&d.gs_blk, h->gs_cap_blk, need));
+    if (want_best) {
+        run.best.assign(n_ligands, GuestBest{INFINITY, 0xFFFFFFFFu, 0u});
+        MDX_TRY(pose_grow(&d.gs_best, h->gs_cap_best, sizeof(GuestBest) * run.best.size()));
+        HIP_TRY(hipMemcpyAsync(d.gs_best, run.best.data(), sizeof(GuestBest) * run.best.size(), hipMemcpyHostToDevice, h->stream));
+    }
+    PoseArgs& a = run.a;
+    a = PoseArgs{};
+    bool samecut = false;
+    mdx_fill_nb_params(h, a.p, &run.mode, &run.geom, &samecut);
+    a.g = h->grid;
+    a.posq = d.posq; a.lj = d.lj; a.orig_of = d.orig_of; a.gid = d.gid; a.grp = d.grp; a.slot_of = d.slot_of;
+    a.tile_start = d.tile_start; a.cl_lo = d.cl_lo; a.cl_hi = d.cl_hi;
+    a.G = G; a.L = 0xFFFFFFFFu;
+    a.r_cull = std::isfinite(h->r_list) ? h->r_list + 0.01f : INFINITY;
+    for (int k = 0; k < 3; ++k) {
+        a.box[k] = h->per[k] ? h->box_hi[k] - h->box_lo[k] : 0.f;
+        a.inv_box[k] = h->per[k] ? 1.0f / a.box[k] : 0.f;
+    }
+    return MDX_OK;
+}
+
+// a chunk goes up: records, tables and coordinates in one copy; the kernel's arguments point into its block
+static int guest_stage(mdx_handle* h, const mdx_guest_ligand* ligs, const GuestChunk& c, const GuestLayout& lay, GuestRun& run) {
+    const mdx_config& cfg = h->cfg;
+    const bool lj_off = (cfg.overrides & MDX_OVR_LJ_DISABLED) != 0, coul_off = (cfg.overrides & MDX_OVR_COULOMB_DISABLED) != 0;
+    const bool geometric = cfg.combining_rule == MDX_COMBINE_GEOMETRIC;
+    const float sqrt_ke = std::sqrt(cfg.coulomb_k);
+    std::vector<unsigned char>& up = run.up;
+    up.assign(lay.up_end, 0);
+    float* gq = (float*)(up.data() + lay.q);
+    float2* glj = (float2*)(up.data() + lay.lj);
+    Pose14* p14 = (Pose14*)(up.data() + lay.p14);
+    float* xyz = (float*)(up.data() + lay.xyz);
+    guest_slots(run.shapes, run.pstart, c, run.slots);
+    guest_records(run.shapes, run.slots, (PoseRec*)(up.data() + lay.rec), (uint32_t*)(up.data() + lay.ligof));
+    std::vector<uint8_t> cls;
+    for (const GuestSlot& s : run.slots) {
+        const mdx_guest_ligand& g = ligs[s.m];
+        const uint32_t cnt = g.count;
+        // rows and records as mdx_create makes a resident atom's: the overrides zero eps and charge first
+        std::vector<float2> raw(cnt);
+        std::vector<float> q(cnt);
+        for (uint32_t i = 0; i < cnt; ++i) {
+            raw[i] = make_float2(g.lj_sigma[i], lj_off ? 0.f : g.lj_eps[i]);
+            q[i] = coul_off ? 0.f : g.charge[i];
+            gq[s.atom + i] = q[i] * sqrt_ke;
+            glj[s.atom + i] = mdx_pack_lj(geometric, raw[i].x, raw[i].y);
+        }
+        (void)guest_class_map(g, cls);
+        std::memcpy(up.data() + lay.cls + s.cls, cls.data(), cls.size());
+        for (uint32_t k = 0; k < s.n14; ++k) {      // (0 with the bonded terms disabled)
+            const uint32_t i = g.pairs14[2 * (size_t)k], j = g.pairs14[2 * (size_t)k + 1];
+            const float4 prm = mdx_pair14_params(cfg, raw[i], raw[j], q[i], q[j]);
+            p14[s.p14 + k] = Pose14{i, j, prm.x, prm.y, prm.z};
+        }
+        std::memcpy(xyz + s.xyz, g.poses + 3 * (size_t)cnt * s.l0, sizeof(float) * 3 * cnt * (s.l1 - s.l0));
+    }
+    unsigned char* blk = (unsigned char*)h->d.gs_blk;
+    HIP_TRY(hipMemcpyAsync(blk, up.data(), lay.up_end, hipMemcpyHostToDevice, h->stream));
+    PoseArgs& a = run.a;
+    a.count = c.max_count;
+    a.rec = (const PoseRec*)(blk + lay.rec);
+    a.gq = (const float*)(blk + lay.q); a.glj = (const float2*)(blk + lay.lj);
+    a.cls = blk + lay.cls; a.p14 = (const Pose14*)(blk + lay.p14);
+    a.poses = (const float*)(blk + lay.xyz);
+    a.slab = (double*)(blk + lay.slab);
+    a.fslab = (double*)(blk + lay.fslab);
+    return MDX_OK;
+}
+
+// mdx_screen_ligands (forces == nullptr: the energy flavour) and mdx_guest_forces (the force flavour; rows_out / rigid may be null)
+static int guest_run(mdx_handle* h, const std::string& who, bool force, uint32_t n_ligands, const mdx_guest_ligand* ligs, float* rows_out,
+                     uint32_t n_groups, float* forces, float* rigid, uint32_t* best_pose, double* best_score) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_ligands == 0) return MDX_OK;
+    if (!ligs) FAIL(MDX_EPARAM, "null argument");
+    const int gmode = force ? GUEST_FORCES : GUEST_ROWS;
+    GuestRun run;
+    MDX_TRY(guest_check(h, who, n_ligands, ligs, n_groups, run));
+    const size_t total = run.total;
+    if (total == 0) return MDX_OK;
+    if (force ? !forces : !rows_out) FAIL(MDX_EPARAM, "null argument");
+    const bool want_best = best_pose || best_score;
+    MDX_TRY(guest_ready(h, n_ligands, gmode, want_best, run));
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t W = h->n_grp + 1u;
+    size_t nxyz = 0;
+    for (const GuestChunk& c : run.chunks) nxyz += c.nxyz;
+    std::vector<float> res(total * W), fres(force ? nxyz : 0), rres(force ? 6u * total : 0);
+    std::vector<double> rows((size_t)std::min<size_t>(total, POSE_CHUNK) * W);
+    unsigned char* blk = (unsigned char*)d.gs_blk;
+    size_t x0 = 0;      // first float of the chunk in `forces`
+    for (const GuestChunk& c : run.chunks) {
+        const GuestLayout lay = guest_layout(c, W, gmode);
+        MDX_TRY(guest_stage(h, ligs, c, lay, run));
+        const PoseArgs& a = run.a;
+        double* drows = (double*)(blk + lay.rows);
+        mdx_prof_begin(h, 0);
+        pose_launch(h, a, run.mode, run.geom, c.n, force, false, true);
+        hipLaunchKernelGGL(pose_sum_kernel, dim3((c.n * W + 255u) / 256u), dim3(256), 0, st, c.n, W, a.slab, drows);
+        if (force)
+            hipLaunchKernelGGL(guest_force_sum_kernel, dim3(c.n), dim3(256), 0, st, a.rec, a.poses, a.fslab, (float*)(blk + lay.fout),
+                               (float*)(blk + lay.rigid));
+        if (want_best)
+            hipLaunchKernelGGL(guest_best_kernel, dim3((c.n + 255u) / 256u), dim3(256), 0, st, c.n, W, drows, (const uint2*)(blk + lay.ligof),
+                               (GuestBest*)d.gs_best);
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rows.data(), drows, sizeof(double) * (size_t)c.n * W, hipMemcpyDeviceToHost, st));
+        if (force) {
+            HIP_TRY(hipMemcpyAsync(fres.data() + x0, blk + lay.fout, sizeof(float) * c.nxyz, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(rres.data() + 6u * c.p0, blk + lay.rigid, sizeof(float) * 6u * c.n, hipMemcpyDeviceToHost, st));
+        }
+        if (want_best && &c == &run.chunks.back())
+            HIP_TRY(hipMemcpyAsync(run.best.data(), d.gs_best, sizeof(GuestBest) * run.best.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t k = 0; force && k < c.nxyz; ++k)
+            if (!std::isfinite(fres[x0 + k])) FAIL(MDX_ENAN, who + ": non-finite force");
+        for (size_t k = 0; force && k < 6u * (size_t)c.n; ++k)
+            if (!std::isfinite(rres[6u * c.p0 + k])) FAIL(MDX_ENAN, who + ": non-finite net force or torque");
+        for (size_t k = 0; k < (size_t)c.n * W; ++k) {
+            if (!std::isfinite(rows[k])) FAIL(MDX_ENAN, who + ": non-finite energy in a row");
+            res[c.p0 * W + k] = (float)rows[k];
+        }
+        x0 += c.nxyz;
+    }
+    if (rows_out) std::memcpy(rows_out, res.data(), sizeof(float) * res.size());
+    if (force) std::memcpy(forces, fres.data(), sizeof(float) * fres.size());
+    if (force && rigid) std::memcpy(rigid, rres.data(), sizeof(float) * rres.size());
+    for (uint32_t m = 0; want_best && m < n_ligands; ++m) {
+        if (best_pose) best_pose[m] = run.best[m].pose;
+        if (best_score) best_score[m] = run.best[m].score;
+    }
+    return MDX_OK;
+}
+
+extern "C" int mdx_screen_ligands(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, float* rows_out, uint32_t n_groups,
+                                  uint32_t* best_pose, double* best_score) {
+    return guest_run(h, "mdx_screen_ligands", false, n_ligands, ligs, rows_out, n_groups, nullptr, nullptr, best_pose, best_score);
+}
+
+extern "C" int mdx_guest_forces(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, float* rows_or_null, uint32_t n_groups,
+                                float* forces, float* rigid_or_null) {
+    return guest_run(h, "mdx_guest_forces", true, n_ligands, ligs, rows_or_null, n_groups, forces, rigid_or_null, nullptr, nullptr);
+}
+
+// The loop of refine_chunks over the chunks of a library: per chunk one upload, the frozen words and records zeroed, max_evals x (the
+// GUEST REFINE force pass, guest_refine_step_kernel), the best kernel on the accepted rows, one read-back, one wait.  The staged
+// coordinates are the stage buffer: the step kernel writes the next trial where the force pass reads the pose.
+extern "C" int mdx_refine_guests(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_refine_opts* opts, float* poses_out,
+                                 float* rows_out_or_null, uint32_t n_groups, float* rigid_out_or_null, float* xform_out_or_null,
+                                 uint32_t* status_out_or_null, uint32_t* evals_out_or_null, uint32_t* best_pose_or_null,
+                                 double* best_score_or_null) {
+    const std::string who = "mdx_refine_guests";
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_ligands == 0) return MDX_OK;
+    if (!ligs || !opts) FAIL(MDX_EPARAM, "null argument");
+    mdx_fx_opts o{};
+    MDX_TRY(refine_opts_check(who, mdx_flex_opts{opts->max_evals, opts->f_tol, opts->tau_tol, 0.f, opts->h_start, opts->h_max, 0u}, o));
+    GuestRun run;
+    MDX_TRY(guest_check(h, who, n_ligands, ligs, n_groups, run));
+    const size_t total = run.total;
+    if (total == 0) return MDX_OK;
+    if (!poses_out) FAIL(MDX_EPARAM, "null argument");
+    const bool want_best = best_pose_or_null || best_score_or_null;
+    MDX_TRY(guest_ready(h, n_ligands, GUEST_REFINE, want_best, run));
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t W = h->n_grp + 1u;
+    size_t nxyz = 0;
+    for (const GuestChunk& c : run.chunks) nxyz += c.nxyz;
+    std::vector<float> yres(nxyz), rres(total * W), gres(6u * total), xres(7u * total);
+    std::vector<uint32_t> sres(total), eres(total);
+    std::vector<unsigned char> back;
+    unsigned char* blk = (unsigned char*)d.gs_blk;
+    size_t x0 = 0;      // first float of the chunk in poses_out
+    for (const GuestChunk& c : run.chunks) {
+        const GuestLayout lay = guest_layout(c, W, GUEST_REFINE);
+        const StepLayout sl(c.n, c.nxyz, W, sizeof(mdx_rf_state), 0u);
+        MDX_TRY(guest_stage(h, ligs, c, lay, run));
+        PoseArgs& a = run.a;
+        unsigned char* sb = blk + lay.step;
+        StepArgs r = step_args(h, a, sb, 0u, W, false, 0u, 0u, sl, o);
+        r.rec = a.rec;
+        a.frozen = r.frozen;
+        HIP_TRY(hipMemsetAsync(sb, 0, sl.y, st));
+        mdx_prof_begin(h, 0);
+        for (uint32_t k = 0; k < opts->max_evals; ++k) step_evaluate<false>(h, a, run.mode, run.geom, c.n, r);
+        if (want_best)
+            hipLaunchKernelGGL(guest_best_refined_kernel, dim3((c.n + 255u) / 256u), dim3(256), 0, st, c.n, W, (const float*)r.row,
+                               (const uint2*)(blk + lay.ligof), (const mdx_rf_state*)r.st, (GuestBest*)d.gs_best);
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        back.resize(sl.x0 - sl.state);
+        HIP_TRY(hipMemcpyAsync(back.data(), sb + sl.state, back.size(), hipMemcpyDeviceToHost, st));
+        if (want_best && &c == &run.chunks.back())
+            HIP_TRY(hipMemcpyAsync(run.best.data(), d.gs_best, sizeof(GuestBest) * run.best.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const unsigned char* b0 = back.data() - sl.state;
+        std::memcpy(yres.data() + x0, b0 + sl.y, sizeof(float) * c.nxyz);
+        std::memcpy(rres.data() + c.p0 * W, b0 + sl.row, sizeof(float) * (size_t)W * c.n);
+        std::memcpy(gres.data() + 6u * c.p0, b0 + sl.rigid, sizeof(float) * 6u * c.n);
+        for (uint32_t k = 0; k < c.n; ++k) {
+            mdx_rf_state s;
+            std::memcpy(&s, b0 + sl.state + sizeof(s) * k, sizeof(s));
+            const size_t p = c.p0 + k;
+            refine_unpack(s, &sres[p], &eres[p], xres.data() + 7u * p);
+        }
+        x0 += c.nxyz;
+    }
+    std::memcpy(poses_out, yres.data(), sizeof(float) * yres.size());
+    if (rows_out_or_null) std::memcpy(rows_out_or_null, rres.data(), sizeof(float) * rres.size());
+    if (rigid_out_or_null) std::memcpy(rigid_out_or_null, gres.data(), sizeof(float) * gres.size());
+    if (xform_out_or_null) std::memcpy(xform_out_or_null, xres.data(), sizeof(float) * xres.size());
+    if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
+    if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
+    for (uint32_t m = 0; want_best && m < n_ligands; ++m) {
+        if (best_pose_or_null) best_pose_or_null[m] = run.best[m].pose;
+        if (best_score_or_null) best_score_or_null[m] = run.best[m].score;
+    }
     return MDX_OK;
 }

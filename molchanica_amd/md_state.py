@@ -19,7 +19,7 @@ import numpy as np
 
 from ._abi import (CCommDiag, CFlexOpts, CGuestLigand, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
                    CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, FUSED_TRIAD_INFO_ARGTYPES, POSE_RMSD_ARGTYPES,
-                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, SCREEN_LIGANDS_ARGTYPES, VEL, GuestLigand,
+                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, GUEST_FORCES_ARGTYPES, REFINE_GUESTS_ARGTYPES, SCREEN_LIGANDS_ARGTYPES, VEL, GuestLigand,
                    MdConfig, MdSystem, CSolubility, SET_SOLUTE_COPIES_ARGTYPES, SNAPSHOT_READ_SOLUBILITY_ARGTYPES, SOLUBILITY_MIXING_ARGTYPES,
                    SOLUTE_MAX_COPIES)
 
@@ -184,6 +184,8 @@ def load_library():
     lib.mdx_pose_rmsd.argtypes = POSE_RMSD_ARGTYPES
     lib.mdx_cluster_poses.argtypes = CLUSTER_POSES_ARGTYPES
     lib.mdx_screen_ligands.argtypes = SCREEN_LIGANDS_ARGTYPES
+    lib.mdx_guest_forces.argtypes = GUEST_FORCES_ARGTYPES
+    lib.mdx_refine_guests.argtypes = REFINE_GUESTS_ARGTYPES
     lib.mdx_set_solute_copies.argtypes = SET_SOLUTE_COPIES_ARGTYPES
     lib.mdx_solubility_mixing.argtypes = SOLUBILITY_MIXING_ARGTYPES
     lib.mdx_snapshot_read_solubility.argtypes = SNAPSHOT_READ_SOLUBILITY_ARGTYPES
@@ -304,12 +306,9 @@ class MdState:
         _check(lib.mdx_score_poses(self._h, int(first), a.shape[1], a.shape[0], a.ctypes.data_as(_fp), out.ctypes.data_as(_fp), n))
         return out[:, :n] if n else out[:, :0]
 
-    def screen_ligands(self, ligands, best=False):
-        """`mdx_screen_ligands`: a library of guest ligands - `GuestLigand`s, none of them part of the handle - against the resident
-        atoms.  -> a list with one float32 array [P_m, n_groups + 1] per ligand: the columns of score_poses() against every resident
-        group (no group is skipped), then the ligand's own pairs.  best=True: also (best_pose uint32 [M], best_score float64 [M]) - per
-        ligand the pose with the smallest row sum (lowest index on a tie) and that sum, picked on the device; 0xFFFFFFFF and inf for a
-        ligand without poses.  The handle is left as it is."""
+    def _guest_records(self, who, ligands):
+        """The `mdx_guest_ligand` records of a library of `GuestLigand`s -> (M, records, poses per ligand, (atoms per ligand, the arrays
+        the records point into: keep them alive across the call))."""
         ligands = list(ligands)
         M = len(ligands)
         recs = (CGuestLigand * max(M, 1))()
@@ -319,17 +318,17 @@ class MdState:
             try:
                 a = np.ascontiguousarray(a, dtype=dtype).reshape(shape)
             except (TypeError, ValueError):
-                raise ParamError(f"screen_ligands: ligand {m}: {what} has the wrong shape or type") from None
+                raise ParamError(f"{who}: ligand {m}: {what} has the wrong shape or type") from None
             keep.append(a)
             return a
 
-        counts = []
+        counts, sizes = [], []
         for m, g in enumerate(ligands):
             if not isinstance(g, GuestLigand):
-                raise ParamError("screen_ligands: ligands must be GuestLigand objects")
+                raise ParamError(f"{who}: ligands must be GuestLigand objects")
             n = g.count
             if not 1 <= n <= POSE_MAX_ATOMS:
-                raise ParamError(f"screen_ligands: ligand {m}: count must be in 1..{POSE_MAX_ATOMS}")
+                raise ParamError(f"{who}: ligand {m}: count must be in 1..{POSE_MAX_ATOMS}")
             q, sg, ep = (arr(v, np.float32, (n,), w, m) for v, w in ((g.charge, "charge"), (g.lj_sigma, "lj_sigma"), (g.lj_eps, "lj_eps")))
             ex = arr(g.excl_pairs, np.uint32, (-1, 2), "excl_pairs", m)
             p14 = arr(g.pairs14, np.uint32, (-1, 2), "pairs14", m)
@@ -340,6 +339,16 @@ class MdState:
             r.n_pairs14, r.pairs14 = p14.shape[0], p14.ctypes.data_as(_u32p) if p14.size else None
             r.n_poses, r.poses = ps.shape[0], ps.ctypes.data_as(_fp) if ps.size else None
             counts.append(ps.shape[0])
+            sizes.append(n)
+        return M, recs, counts, (sizes, keep)
+
+    def screen_ligands(self, ligands, best=False):
+        """`mdx_screen_ligands`: a library of guest ligands - `GuestLigand`s, none of them part of the handle - against the resident
+        atoms.  -> a list with one float32 array [P_m, n_groups + 1] per ligand: the columns of score_poses() against every resident
+        group (no group is skipped), then the ligand's own pairs.  best=True: also (best_pose uint32 [M], best_score float64 [M]) - per
+        ligand the pose with the smallest row sum (lowest index on a tie) and that sum, picked on the device; 0xFFFFFFFF and inf for a
+        ligand without poses.  The handle is left as it is."""
+        M, recs, counts, _keep = self._guest_records("screen_ligands", ligands)
         lib = load_library()
         G = int(lib.mdx_energy_group_count(self._h))
         out = np.zeros((max(sum(counts), 1), G + 1), dtype=np.float32)
@@ -350,6 +359,69 @@ class MdState:
         edges = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         rows = [out[edges[m]:edges[m + 1]].copy() for m in range(M)]
         return (rows, (bp[:M], bs[:M])) if best else rows
+
+    @staticmethod
+    def _per_ligand(flat, counts, sizes=None):
+        """A flat per-pose result cut into one array per ligand; sizes: coordinate-shaped, per ligand [P_m, count, 3]."""
+        out, at = [], 0
+        for m, p in enumerate(counts):
+            if sizes is None:
+                out.append(flat[at:at + p].copy())
+                at += p
+            else:
+                n = 3 * sizes[m] * p
+                out.append(flat[at:at + n].reshape(p, sizes[m], 3).copy())
+                at += n
+        return out
+
+    def guest_forces(self, ligands, rows=True, rigid=False):
+        """`mdx_guest_forces`: pose_forces() for a library of guest ligands - none of them part of the handle.  Per pose the force on
+        every ligand atom: minus the gradient of the sum of the pose's screen_ligands() row, the ligand's own pairs included.
+        -> (forces[, rows - the bits of screen_ligands()][, rigid: net force, torque about the pose's centroid]), each a list with one
+        float32 array per ligand: [P_m, count, 3], [P_m, n_groups + 1], [P_m, 6]; rows / rigid false or None leave the entry out.
+        The handle is left as it is."""
+        M, recs, counts, (sizes, _keep) = self._guest_records("guest_forces", ligands)
+        lib = load_library()
+        G = int(lib.mdx_energy_group_count(self._h))
+        P = sum(counts)
+        f = np.zeros(max(sum(3 * n * p for n, p in zip(sizes, counts)), 1), dtype=np.float32)
+        r = np.zeros((max(P, 1), G + 1), dtype=np.float32) if rows else None
+        t = np.zeros((max(P, 1), 6), dtype=np.float32) if rigid else None
+        _check(lib.mdx_guest_forces(self._h, M, recs, None if r is None else r.ctypes.data_as(_fp), G, f.ctypes.data_as(_fp),
+                                    None if t is None else t.ctypes.data_as(_fp)))
+        out = (self._per_ligand(f, counts, sizes),)
+        if r is not None:
+            out += (self._per_ligand(r, counts),)
+        if t is not None:
+            out += (self._per_ligand(t, counts),)
+        return out
+
+    def refine_guests(self, ligands, max_evals: int, f_tol: float, tau_tol: float, h_start: float = 0.0, h_max: float = 0.0, best=False):
+        """`mdx_refine_guests`: refine_poses() for a library of guest ligands - a rigid-body steepest descent of every pose of every
+        ligand on the device, evaluated as guest_forces() does (include/mdx.h states the stepper).
+        -> (poses_out, rows - the bits of screen_ligands(poses_out) -, rigid, xform, status, evals), each a list with one array per
+        ligand: [P_m, count, 3], [P_m, n_groups + 1], [P_m, 6], [P_m, 7] f32, [P_m], [P_m] u32, all of the accepted state.  best=True:
+        also (best_pose uint32 [M], best_score float64 [M]) - per ligand the accepted pose with the smallest row sum (lowest index on a
+        tie; a REFINE_NONFINITE pose never wins), picked on the device; 0xFFFFFFFF and inf for a ligand without a finite pose.  The
+        handle is left as it is."""
+        M, recs, counts, (sizes, _keep) = self._guest_records("refine_guests", ligands)
+        lib = load_library()
+        G = int(lib.mdx_energy_group_count(self._h))
+        P = max(sum(counts), 1)
+        opts = CRefineOpts(int(max_evals), float(f_tol), float(tau_tol), float(h_start), float(h_max))
+        y = np.zeros(max(sum(3 * n * p for n, p in zip(sizes, counts)), 1), dtype=np.float32)
+        r = np.zeros((P, G + 1), dtype=np.float32)
+        t = np.zeros((P, 6), dtype=np.float32)
+        x = np.zeros((P, 7), dtype=np.float32)
+        st = np.zeros(P, dtype=np.uint32)
+        ev = np.zeros(P, dtype=np.uint32)
+        bp = np.full(max(M, 1), 0xFFFFFFFF, np.uint32)
+        bs = np.full(max(M, 1), np.inf, np.float64)
+        _check(lib.mdx_refine_guests(self._h, M, recs, C.byref(opts), y.ctypes.data_as(_fp), r.ctypes.data_as(_fp), G, t.ctypes.data_as(_fp),
+                                     x.ctypes.data_as(_fp), st.ctypes.data_as(_u32p), ev.ctypes.data_as(_u32p),
+                                     bp.ctypes.data_as(_u32p) if best else None, bs.ctypes.data_as(C.POINTER(C.c_double)) if best else None))
+        out = (self._per_ligand(y, counts, sizes),) + tuple(self._per_ligand(v, counts) for v in (r, t, x, st, ev))
+        return out + ((bp[:M], bs[:M]),) if best else out
 
     def pose_forces(self, first: int, poses, rows=True, rigid=False):
         """`mdx_pose_forces`: the force on every atom of each of P alternative placements of the atoms [first, first + count) - minus
