@@ -703,7 +703,8 @@ int      mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_
  * for bit like one that did not make the call.  A (ligand, pose) gives the same bits alone, in a library of any size and order, at any
  * place in it.  n_ligands == 0, or a library without a single pose, succeeds and does nothing.  Decomposed handles and active
  * alchemical windows are refused.  Per chunk of 256 poses of the library the refinement enqueues max_evals x (force pass, step kernel)
- * and waits once.  Not built for guests: torsional refinement and search. */
+ * and waits once.  Torsional refinement of guests is mdx_refine_guests_flex, below mdx_search_poses.  Not built for guests: the pose
+ * search (mdx_search_poses for a library). */
 int      mdx_guest_forces(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs,
                           float* rows_or_null /* [sum n_poses][n_groups + 1] */, uint32_t n_groups,
                           float* forces /* per ligand [n_poses][count][3] */, float* rigid_or_null /* [sum n_poses][6] */);
@@ -808,6 +809,52 @@ int      mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_
                           uint32_t n_groups, double* best_score_out_or_null /* [n_walkers]: S */, float* best_dih_out_or_null /* [n_walkers] */,
                           uint32_t* best_round_out_or_null /* [n_walkers] */,
                           uint32_t* stats_out_or_null /* [n_walkers][4]: rounds accepted, accepted uphill, non-finite rounds, evaluations in total */);
+
+/* ---- guest ligands, flexible: mdx_refine_poses_flex for a library of mdx_guest_ligand ----------------------------------------------------
+ * The library of mdx_refine_guests with, parallel to it, one mdx_guest_flex per ligand: what a guest lacks for torsions - its bond graph,
+ * the root and the torsion bonds, its dihedral terms.  mdx_guest_ligand itself is unchanged.
+ *
+ * The stepper is that of mdx_refine_poses_flex, word for word - coords, evaluation, direction, convergence, next trial, the defaults,
+ * the status values, MDX_REFINE_MAX_EVALS_CAP - with the evaluation of mdx_guest_forces: r = the row (n_groups + 1 columns), f^nb and rigid
+ * = the fp32 bits mdx_guest_forces returns, S = the sum over the columns in column order of (double) r[b], plus (double) E_dih.
+ *   torsions   the ligand's bond graph is `bonds` (list the constraints with them); torsion k names a bond of it, and the moving sets
+ *              are made as mdx_refine_poses_flex makes them, with the same refusals.  n_torsions may differ from ligand to ligand.
+ *   dihedrals  E_dih and f^dih of the ligand's listed terms, summed in list order, phi, the guards and the minimum image (the handle's
+ *              box) as stated at mdx_refine_poses_flex.  They are taken with MDX_FLEX_DIHEDRALS and without MDX_OVR_BONDED_DISABLED
+ *              only; otherwise both are 0 (the list is validated all the same).
+ * Outputs of the accepted state, in the library's pose order as in mdx_refine_guests: poses_out (ligand-major), rows_out[p] (the bits
+ * mdx_screen_ligands returns for poses_out[p]), rigid_out[p] (the bits mdx_guest_forces returns for it), status, evals; dih_out[p] =
+ * E_dih.  xform_out and tgrad_out are ligand-major with the ligand's OWN width: per ligand [n_poses][7 + n_torsions] (q, t, theta) and
+ * [n_poses][n_torsions], the ligands one behind the other.  With n_torsions == 0 for every ligand and flags == 0 every shared output,
+ * best pose and best score among them, is bit for bit what mdx_refine_guests returns.
+ * best_pose_or_null[m] / best_score_or_null[m]: picked on the device by the rule of mdx_refine_guests with S including E_dih - a strictly
+ * smaller S wins, the lowest ligand-local index wins a tie, a MDX_REFINE_NONFINITE pose never wins; 0xFFFFFFFF and +infinity for a
+ * ligand with no pose or none finite.
+ * The handle is not changed.  A (ligand, pose) gives the same bits alone, in a library of any size and order, at any place in it.  Per
+ * chunk of 256 poses of the library the call enqueues max_evals x (force pass, step kernel) and waits once.  n_ligands == 0, or a
+ * library without a single pose, succeeds and writes nothing.
+ * MDX_EPARAM (mdx_last_error names the ligand and, where there is one, the torsion, bond or term; nothing is written): everything
+ * mdx_refine_guests refuses; flex == NULL; a bond index >= count or a bond of an atom with itself; every torsion refusal of
+ * mdx_refine_poses_flex (root >= count; an index >= count; the same atom twice; the pair is not in `bonds`; a bond listed twice; a ring
+ * bond; a leaf bond; a graph that is not connected where n_torsions > 0; n_torsions > MDX_POSE_MAX_TORSIONS; torsion_bonds NULL with
+ * n_torsions > 0); a dihedral index >= count; v or phase not finite; 2^20 dihedral terms or more; a list pointer NULL with a non-zero
+ * count; tors_tol negative or not finite; unknown flag bits.
+ * Not part of it: bond and angle terms of the guest, ring flexibility, guests above 256 atoms or 32 torsions, decomposed handles,
+ * alchemical windows - and the pose search: mdx_search_poses has no counterpart for guests yet. */
+typedef struct mdx_guest_flex {
+    uint32_t n_bonds;     const uint32_t* bonds;          /* [n_bonds][2] ligand-local: the ligand's bond graph (bonds and constraints) */
+    uint32_t root, n_torsions; const uint32_t* torsion_bonds; /* [n_torsions][2] ligand-local, n_torsions <= MDX_POSE_MAX_TORSIONS */
+    uint32_t n_dihedrals; const uint32_t* dihedral_idx;   /* [n_dihedrals][4] ligand-local, list order = summation order */
+    const float* dihedral_v; const float* dihedral_phase; const int32_t* dihedral_n;   /* [n_dihedrals], as mdx_system's */
+} mdx_guest_flex;
+int      mdx_refine_guests_flex(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_guest_flex* flex /* [n_ligands] */,
+                                const mdx_flex_opts* opts, float* poses_out /* per ligand [n_poses][count][3] */,
+                                float* rows_out_or_null /* [sum n_poses][n_groups + 1] */, uint32_t n_groups,
+                                float* rigid_out_or_null /* [sum n_poses][6] */,
+                                float* xform_out_or_null /* per ligand [n_poses][7 + n_torsions] */, float* dih_out_or_null /* [sum n_poses] */,
+                                float* tgrad_out_or_null /* per ligand [n_poses][n_torsions] */, uint32_t* status_out_or_null /* [sum n_poses] */,
+                                uint32_t* evals_out_or_null /* [sum n_poses] */, uint32_t* best_pose_or_null /* [n_ligands] */,
+                                double* best_score_or_null /* [n_ligands] */);
 
 /* ---- pose distances and clustering: symmetry-aware RMSD in the receptor's frame, greedy leader clustering by it --------------------------
  * What follows a search: rank the poses by score, keep a pose only if it is further than an RMSD cutoff from every pose already kept,

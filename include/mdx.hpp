@@ -216,6 +216,30 @@ public:
                                 r.status.data(), r.evals.data(), r.best_pose.data(), r.best_score.data()));
         return r;
     }
+    /// mdx_refine_guests_flex: refine_poses_flex for a library of guest ligands, flex[m] beside ligs[m]; xform and tgrad are laid out
+    /// per ligand with its own width, [n_poses][7 + n_torsions] and [n_poses][n_torsions].
+    struct RefinedGuestsFlex {
+        std::vector<float> poses, rows, rigid, xform, dih, tgrad;
+        std::vector<uint32_t> status, evals;               ///< [sum n_poses]
+        std::vector<uint32_t> best_pose;                   ///< [n_ligands], 0xFFFFFFFF: no pose, or none finite
+        std::vector<double> best_score;                    ///< [n_ligands]: row sum + E_dih
+    };
+    RefinedGuestsFlex refine_guests_flex(const std::vector<mdx_guest_ligand>& ligs, const std::vector<mdx_guest_flex>& flex, const mdx_flex_opts& opts) {
+        if (flex.size() != ligs.size()) throw std::invalid_argument("refine_guests_flex: one mdx_guest_flex per ligand");
+        const uint32_t g = mdx_energy_group_count(h_);
+        size_t n = 0, nx = 0, nt = 0;
+        for (size_t m = 0; m < ligs.size(); ++m) {
+            n += ligs[m].n_poses; nx += 3 * (size_t)ligs[m].count * ligs[m].n_poses; nt += (size_t)flex[m].n_torsions * ligs[m].n_poses;
+        }
+        RefinedGuestsFlex r;
+        r.poses.assign(nx, 0.f); r.rows.assign(n * ((size_t)g + 1), 0.f); r.rigid.assign(n * 6, 0.f); r.xform.assign(n * 7 + nt, 0.f);
+        r.dih.assign(n, 0.f); r.tgrad.assign(nt, 0.f); r.status.assign(n, 0u); r.evals.assign(n, 0u);
+        r.best_pose.assign(ligs.size(), 0xFFFFFFFFu); r.best_score.assign(ligs.size(), std::numeric_limits<double>::infinity());
+        check(mdx_refine_guests_flex(h_, (uint32_t)ligs.size(), ligs.data(), flex.data(), &opts, r.poses.data(), r.rows.data(), g, r.rigid.data(),
+                                     r.xform.data(), r.dih.data(), r.tgrad.data(), r.status.data(), r.evals.data(), r.best_pose.data(),
+                                     r.best_score.data()));
+        return r;
+    }
     /// mdx_pose_forces: forces [n_poses][count][3] kcal/mol/A on the atoms of every pose (minus the gradient of the sum of its row);
     /// rows (if not null) receives the rows of score_poses, rigid (if not null) [n_poses][6]: net force, torque about the pose's centroid.
     std::vector<float> pose_forces(uint32_t first, uint32_t count, const std::vector<float>& poses, std::vector<float>* rows = nullptr,

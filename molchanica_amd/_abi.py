@@ -132,6 +132,19 @@ REFINE_GUESTS_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), C.POI
                           _u32p, C.POINTER(C.c_double)]
 
 
+class CGuestFlex(C.Structure):
+    """mdx_guest_flex"""
+    _fields_ = [("n_bonds", C.c_uint32), ("bonds", _u32p), ("root", C.c_uint32), ("n_torsions", C.c_uint32), ("torsion_bonds", _u32p),
+                ("n_dihedrals", C.c_uint32), ("dihedral_idx", _u32p), ("dihedral_v", _fp), ("dihedral_phase", _fp),
+                ("dihedral_n", C.POINTER(C.c_int32))]
+
+
+# mdx_refine_guests_flex(h, n_ligands, ligs, flex, opts, poses_out, rows_out_or_null, n_groups, rigid_out_or_null, xform_out_or_null,
+#                        dih_out_or_null, tgrad_out_or_null, status_out_or_null, evals_out_or_null, best_pose_or_null, best_score_or_null)
+REFINE_GUESTS_FLEX_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), C.POINTER(CGuestFlex), C.POINTER(CFlexOpts), _fp, _fp, C.c_uint32,
+                               _fp, _fp, _fp, _fp, _u32p, _u32p, _u32p, C.POINTER(C.c_double)]
+
+
 class CEnergies(C.Structure):
     _fields_ = [(n, C.c_double) for n in (
         "kinetic", "potential", "potential_nonbonded", "potential_bonded",
@@ -441,3 +454,45 @@ class GuestLigand:
         ex = ex[~np.isin(ex[:, 0] * n + ex[:, 1], p14[:, 0] * n + p14[:, 1])]
         return cls(charge=sys.charge[lo:hi].copy(), lj_sigma=sys.lj_sigma[t].astype(np.float32), lj_eps=sys.lj_eps[t].astype(np.float32),
                    excl_pairs=ex.astype(np.uint32), pairs14=p14.astype(np.uint32), poses=poses)
+
+
+@dataclass
+class GuestFlex:
+    """What `MdState.refine_guests_flex` needs of a guest beside its `GuestLigand` (`mdx_guest_flex`): the ligand's bond graph, the root
+    and the torsion bonds, and its dihedral terms in summation order - all in ligand-local indices."""
+    bonds: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.uint32))             # [B, 2]: bonds and constraints
+    root: int = 0
+    torsion_bonds: np.ndarray = field(default_factory=lambda: np.zeros((0, 2), np.uint32))     # [T, 2], T <= POSE_MAX_TORSIONS
+    dihedral_idx: np.ndarray = field(default_factory=lambda: np.zeros((0, 4), np.uint32))      # [D, 4]
+    dihedral_v: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float32))            # [D] kcal/mol
+    dihedral_phase: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float32))        # [D] rad
+    dihedral_n: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int32))              # [D] periodicity
+
+    @property
+    def n_torsions(self) -> int:
+        return int(np.asarray(self.torsion_bonds).reshape(-1, 2).shape[0])
+
+    @classmethod
+    def from_system(cls, sys: MdSystem, lo: int, hi: int, root: int = 0, torsion_bonds=None) -> "GuestFlex":
+        """The molecule [lo, hi) of an MdSystem: its bonds, then its constraints, inside the range (the graph mdx_refine_poses_flex takes
+        for a resident range), and the dihedral terms wholly inside it in the system's list order.  torsion_bonds None: every rotatable
+        bond (topology.rotatable_bonds), at most the first POSE_MAX_TORSIONS.  Raises ValueError on a dihedral term that straddles the
+        range."""
+        sys.normalise()
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= sys.n_atoms:
+            raise ValueError("GuestFlex.from_system: atom range out of bounds")
+        b = np.concatenate([np.asarray(sys.bond_idx, np.int64).reshape(-1, 2), np.asarray(sys.constraint_idx, np.int64).reshape(-1, 2)])
+        b = b[((b >= lo) & (b < hi)).all(1)] - lo
+        d = np.asarray(sys.dihedral_idx, np.int64).reshape(-1, 4)
+        inside = ((d >= lo) & (d < hi)).sum(1)
+        if ((inside != 0) & (inside != 4)).any():
+            raise ValueError("GuestFlex.from_system: a dihedral term links the range to an atom outside it")
+        keep = inside == 4
+        if torsion_bonds is None:
+            from .topology import rotatable_bonds      # (topology imports this module)
+            torsion_bonds = rotatable_bonds(hi - lo, b, int(root))[:POSE_MAX_TORSIONS]
+        return cls(bonds=b.astype(np.uint32), root=int(root), torsion_bonds=np.asarray(torsion_bonds, np.uint32).reshape(-1, 2),
+                   dihedral_idx=(d[keep] - lo).astype(np.uint32), dihedral_v=np.asarray(sys.dihedral_v, np.float32)[keep].copy(),
+                   dihedral_phase=np.asarray(sys.dihedral_phase, np.float32)[keep].copy(),
+                   dihedral_n=np.asarray(sys.dihedral_n)[keep].astype(np.int32))

@@ -5,6 +5,8 @@
 //   GuestLayout  the block of one chunk of guest poses: what the host stages, then what the kernels write
 //   guest_plan   the chunks of a library (POSE_CHUNK consecutive poses each) and, per chunk, the ligands it holds poses of
 //   guest_slots  where every such ligand's tables and poses lie in the chunk; guest_records makes the per-pose records from them
+//   (the flexible guest refinement: per ligand the torsion table, the dihedral terms and their gather tables - FlexRec per pose,
+//   guest_flex_records - and per pose its own stretch of the terms' energies and forces)
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -22,6 +24,13 @@ struct Pose14 { uint32_t a, b; float sig, e4, qq; };      // ligand-local atoms;
 // accepted coordinates, input poses; the pose's partial forces start at double (POSE_UNITS + 1) x xyz of the force slab.
 struct PoseRec { uint32_t atom, count, cls, p14, n14, xyz; };
 
+// What a guest pose adds for the flexible refinement, parallel to PoseRec: its ligand's torsion table (first mdx_fx_torsion of the chunk's
+// and T), its dihedral terms (first mdx_fx_dihedral and n_terms), the gather tables (first word of aoff [count + 1] and of aent
+// [4 n_terms]), and the pose's own first term of the chunk's eterm [terms of all poses][FLEX_TERM_WORDS].
+struct FlexRec { uint32_t tor, T, dih, n_terms, aoff, aent, eterm, pad; };
+#define GUEST_TOR_BYTES 48u     // sizeof(mdx_fx_torsion), sizeof(mdx_fx_dihedral) (mdx_flex_step.h; mdx_poses.hip asserts both)
+#define GUEST_DIH_BYTES 40u
+
 // The refinement's device block of a chunk of n poses with nxyz coordinates in all (n x count x 3 of a resident ligand): [frozen words |
 // state records | accepted coordinates | rows | rigid | input poses | the dihedral terms' energies and forces]; the first two are
 // zeroed at the start of the chunk, records .. rigid come back in one copy at its end.  W is the width of a row; state_bytes is
@@ -38,16 +47,32 @@ struct StepLayout {
         eterm = ((x0 + sizeof(float) * nxyz + 15u) / 16u) * 16u;
         end = eterm + sizeof(double) * FLEX_TERM_WORDS * (size_t)n_terms * n;
     }
+    // a chunk of guest poses: every pose has its ligand's number of terms, `terms` in all
+    static StepLayout guest(uint32_t n, size_t nxyz, uint32_t W, size_t state_bytes, size_t terms) {
+        StepLayout l(n, nxyz, W, state_bytes, 0u);
+        l.end = l.eterm + sizeof(double) * FLEX_TERM_WORDS * terms;
+        return l;
+    }
 };
 
-enum GuestMode { GUEST_ROWS = 0, GUEST_FORCES = 1, GUEST_REFINE = 2 };      // mdx_screen_ligands, mdx_guest_forces, mdx_refine_guests
+// mdx_screen_ligands, mdx_guest_forces, mdx_refine_guests, mdx_refine_guests_flex
+enum GuestMode { GUEST_ROWS = 0, GUEST_FORCES = 1, GUEST_REFINE = 2, GUEST_FLEX = 3 };
+
+// the flexible tables of a chunk, in elements: torsions, dihedral terms (every ligand's rounded up to an even number: its table starts
+// on 16 bytes), words of aoff (every ligand's count + 1 rounded up to 4) and the terms of all poses (eterm)
+struct GuestFlexSums { size_t tor = 0, dih = 0, aoff = 0, terms = 0; };
+inline size_t guest_dih_room(uint32_t n_terms) { return ((size_t)n_terms + 1u) / 2u * 2u; }
+inline size_t guest_aoff_room(uint32_t count) { return ((size_t)count + 1u + 3u) / 4u * 4u; }
 
 // The device block of one chunk of n guest poses: what the host stages ([0, up_end): records, (ligand, pose) words, charge and LJ rows
 // of the chunk's ligands, their 1-4 records, the coordinates, the class maps), then the units' slab and the summed rows; with forces
 // the units' force slab, the summed forces and rigid; for a refinement the force slab and a StepLayout at `step` (state_bytes > 0).
+// GUEST_FLEX stages, behind the class maps, the FlexRec records and the ligands' flexible tables (fx), each on 16 bytes, and its
+// StepLayout ends with the terms of all poses.
 struct GuestLayout {
-    size_t rec, ligof, q, lj, p14, xyz, cls, up_end, slab, rows, fslab, fout, rigid, step, end;
-    GuestLayout(size_t n, size_t atoms, size_t n14, size_t nxyz, size_t ncls, uint32_t W, int mode = GUEST_ROWS, size_t state_bytes = 0) {
+    size_t rec, ligof, q, lj, p14, xyz, cls, frec, tor, dih, aoff, aent, up_end, slab, rows, fslab, fout, rigid, step, end;
+    GuestLayout(size_t n, size_t atoms, size_t n14, size_t nxyz, size_t ncls, uint32_t W, int mode = GUEST_ROWS, size_t state_bytes = 0,
+                const GuestFlexSums& fx = GuestFlexSums()) {
         auto al = [](size_t x) { return (x + 15u) / 16u * 16u; };
         rec = 0;
         ligof = al(rec + sizeof(PoseRec) * n);
@@ -57,6 +82,15 @@ struct GuestLayout {
         xyz = al(p14 + sizeof(Pose14) * n14);
         cls = al(xyz + sizeof(float) * nxyz);
         up_end = cls + ncls;
+        frec = tor = dih = aoff = aent = up_end;
+        if (mode == GUEST_FLEX) {
+            frec = al(up_end);
+            tor = al(frec + sizeof(FlexRec) * n);
+            dih = al(tor + GUEST_TOR_BYTES * fx.tor);
+            aoff = al(dih + GUEST_DIH_BYTES * fx.dih);
+            aent = al(aoff + sizeof(uint32_t) * fx.aoff);
+            up_end = aent + sizeof(uint32_t) * 4u * fx.dih;
+        }
         slab = al(up_end);
         rows = slab + sizeof(double) * n * (POSE_UNITS + 1u) * W;
         end = rows + sizeof(double) * n * W;
@@ -66,15 +100,18 @@ struct GuestLayout {
         fout = fslab + sizeof(double) * (POSE_UNITS + 1u) * nxyz;
         rigid = fout + sizeof(float) * nxyz;
         step = al(rigid + sizeof(float) * 6u * n);
-        end = mode == GUEST_REFINE ? step + StepLayout((uint32_t)n, nxyz, W, state_bytes, 0u).end : step;
+        end = step;
+        if (mode == GUEST_REFINE) end = step + StepLayout((uint32_t)n, nxyz, W, state_bytes, 0u).end;
+        if (mode == GUEST_FLEX) end = step + StepLayout::guest((uint32_t)n, nxyz, W, state_bytes, fx.terms).end;
     }
 };
 
-struct GuestShape { uint32_t count, n_poses, n14; };      // a ligand as the planner sees it; n14: the 1-4 records it stages
+// a ligand as the planner sees it; n14: the 1-4 records it stages; T, n_terms: its torsions and dihedral terms (flexible refinement)
+struct GuestShape { uint32_t count, n_poses, n14, T, n_terms; };
 
 // POSE_CHUNK consecutive poses of the library: p0, n; the ligands it holds poses of (m0 .. m1; empty ligands between them are skipped);
 // the sums its layout is made from, and its largest ligand (the force flavour's dynamic LDS)
-struct GuestChunk { size_t p0; uint32_t n, m0, m1; size_t atoms, n14, nxyz, ncls; uint32_t max_count; };
+struct GuestChunk { size_t p0; uint32_t n, m0, m1; size_t atoms, n14, nxyz, ncls; uint32_t max_count; GuestFlexSums fx; };
 
 // -> pstart [n_ligands + 1] (first pose of every ligand in the library's pose order) and the chunks, in order
 inline void guest_plan(const std::vector<GuestShape>& ligs, std::vector<size_t>& pstart, std::vector<GuestChunk>& chunks) {
@@ -85,7 +122,7 @@ inline void guest_plan(const std::vector<GuestShape>& ligs, std::vector<size_t>&
     chunks.clear();
     uint32_t m = 0;
     for (size_t p0 = 0; p0 < total; p0 += POSE_CHUNK) {
-        GuestChunk c{p0, (uint32_t)std::min<size_t>(POSE_CHUNK, total - p0), 0, 0, 0, 0, 0, 0, 0};
+        GuestChunk c{p0, (uint32_t)std::min<size_t>(POSE_CHUNK, total - p0), 0, 0, 0, 0, 0, 0, 0, GuestFlexSums()};
         while (pstart[m + 1] <= p0) ++m;
         c.m0 = m;
         for (uint32_t k = m; k < M && pstart[k] < p0 + c.n; ++k) {
@@ -93,24 +130,29 @@ inline void guest_plan(const std::vector<GuestShape>& ligs, std::vector<size_t>&
             const size_t cnt = ligs[k].count, np = std::min(pstart[k + 1], p0 + c.n) - std::max(pstart[k], p0);
             c.m1 = k; c.atoms += cnt; c.ncls += cnt * cnt; c.nxyz += 3 * cnt * np; c.n14 += ligs[k].n14;
             c.max_count = std::max(c.max_count, ligs[k].count);
+            c.fx.tor += ligs[k].T; c.fx.dih += guest_dih_room(ligs[k].n_terms); c.fx.aoff += guest_aoff_room(ligs[k].count);
+            c.fx.terms += (size_t)ligs[k].n_terms * np;
         }
         chunks.push_back(c);
     }
 }
 
 // A ligand with poses in a chunk: its first rows in the chunk's tables, its poses [l0, l1) (ligand-local) as the chunk's poses
-// p .. p + (l1 - l0), the first of them at float xyz of the coordinates
-struct GuestSlot { uint32_t m, atom, cls, p14, n14, p, xyz; size_t l0, l1; };
+// p .. p + (l1 - l0), the first of them at float xyz of the coordinates; its flexible tables (tor, dih, aoff; aent starts at word
+// 4 dih) and the first term of its first pose in the chunk's eterm
+struct GuestSlot { uint32_t m, atom, cls, p14, n14, p, xyz; size_t l0, l1; uint32_t tor, dih, aoff, eterm; };
 
 inline void guest_slots(const std::vector<GuestShape>& ligs, const std::vector<size_t>& pstart, const GuestChunk& c, std::vector<GuestSlot>& slots) {
     slots.clear();
-    uint32_t atom = 0, n14 = 0, nx = 0, ncls = 0, p = 0;
+    uint32_t atom = 0, n14 = 0, nx = 0, ncls = 0, p = 0, tor = 0, dih = 0, aoff = 0, eterm = 0;
     for (uint32_t m = c.m0; m <= c.m1; ++m) {
         const GuestShape& g = ligs[m];
         if (g.n_poses == 0) continue;
         const size_t l0 = std::max(pstart[m], c.p0) - pstart[m], l1 = std::min(pstart[m + 1], c.p0 + c.n) - pstart[m];
-        slots.push_back(GuestSlot{m, atom, ncls, n14, g.n14, p, nx, l0, l1});
+        slots.push_back(GuestSlot{m, atom, ncls, n14, g.n14, p, nx, l0, l1, tor, dih, aoff, eterm});
         atom += g.count; ncls += g.count * g.count; n14 += g.n14;
+        tor += g.T; dih += (uint32_t)guest_dih_room(g.n_terms); aoff += (uint32_t)guest_aoff_room(g.count);
+        eterm += g.n_terms * (uint32_t)(l1 - l0);
         p += (uint32_t)(l1 - l0); nx += 3u * g.count * (uint32_t)(l1 - l0);
     }
 }
@@ -124,5 +166,14 @@ inline void guest_records(const std::vector<GuestShape>& ligs, const std::vector
             rec[p] = PoseRec{s.atom, cnt, s.cls, s.p14, s.n14, s.xyz + 3u * cnt * (uint32_t)(l - s.l0)};
             ligof[2u * p] = s.m; ligof[2u * p + 1u] = (uint32_t)l;
         }
+    }
+}
+
+// the flexible records of the chunk's poses: frec [c.n]
+inline void guest_flex_records(const std::vector<GuestShape>& ligs, const std::vector<GuestSlot>& slots, FlexRec* frec) {
+    for (const GuestSlot& s : slots) {
+        const GuestShape& g = ligs[s.m];
+        for (size_t l = s.l0; l < s.l1; ++l)
+            frec[s.p + (uint32_t)(l - s.l0)] = FlexRec{s.tor, g.T, s.dih, g.n_terms, s.aoff, 4u * s.dih, s.eterm + g.n_terms * (uint32_t)(l - s.l0), 0u};
     }
 }

@@ -69,6 +69,13 @@
 // coordinate-shaped buffer through it (guest_force_sum_kernel, guest_refine_step_kernel: further plain kernels over the one body),
 // the stage buffer is the chunk's coordinate block, rows are G + 1 wide, and guest_best reads the accepted fp32 rows.
 //
+// mdx_refine_guests_flex: the flexible refinement for guests - the GUEST REFINE force pass as it is, then guest_flex_step_kernel,
+// pose_step<true, true>.  A pose's torsion table, dihedral terms, gather tables and its stretch of the terms' energies and forces come
+// from a FlexRec beside its PoseRec (StepTables<GUEST> is to them what StepLigand is to the coordinates): T and n_terms differ from
+// ligand to ligand within one launch, the tables are staged once per ligand of the chunk behind its class map, and eterm is as long as
+// the chunk's poses have terms.  guest_best_flex_kernel is guest_best over the flexible records: S with the accepted E_dih.  The body of
+// the step kernels stands in mdx_pose_step_dev.h and the new kernel in mdx_guest_flex.hip, for the reason given there.
+//
 // What is written once: the unit-order sum of a slab (pose_units_sum: the four kernels that add the 17 units take it from there, which
 // is why rows_out / rigid_out of a refinement are the bits mdx_score_poses / mdx_pose_forces return), the stages of an evaluation
 // (step_gather, step_store, step_max_speed; centroid, rigid and inertia stand once in pose_step), the B(theta) loop
@@ -82,6 +89,7 @@
 #include "mdx_flex_step.h"
 #include "mdx_search_step.h"
 #include "mdx_pose_plan.h"
+#include "mdx_pose_step_dev.h"
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -377,51 +385,12 @@ __global__ __launch_bounds__(256) void pose_score_kernel(PoseArgs a) {
         }
 }
 
-// one element of a pose's slab, its POSE_UNITS + 1 partial sums added in unit order: the only place that order is written
-__device__ __forceinline__ double pose_units_sum(const double* s, size_t stride) {
-    double v = 0.0;
-    for (uint32_t u = 0; u <= POSE_UNITS; ++u) v += s[(size_t)u * stride];
-    return v;
-}
-
 __global__ __launch_bounds__(256) void pose_sum_kernel(uint32_t n, uint32_t G, const double* __restrict__ slab, double* __restrict__ rows) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * G) return;
     const uint32_t pose = i / G, b = i - pose * G;
     rows[i] = pose_units_sum(slab + (size_t)pose * (POSE_UNITS + 1u) * G + b, G);
 }
-
-// component k of (sum_i f_i, sum_i (x_i - c) x f_i), atoms in order: the one statement both kernels below take rigid from
-__device__ __forceinline__ double pose_rigid_component(uint32_t k, uint32_t count, const double (*s_x)[3], const double (*s_v)[3], const double* s_c) {
-    const uint32_t d = k % 3u, d1 = (d + 1u) % 3u, d2 = (d + 2u) % 3u;
-    double v = 0.0;
-    for (uint32_t i = 0; i < count; ++i)
-        v += k < 3u ? s_v[i][d] : (s_x[i][d1] - s_c[d1]) * s_v[i][d2] - (s_x[i][d2] - s_c[d2]) * s_v[i][d1];
-    return v;
-}
-
-// The ligand of a pose as the kernels behind the force pass see it - PoseLigand's counterpart there: its size, where atom i lies in
-// every buffer shaped like the coordinates (the staged trial, forces, accepted and input coordinates: at(i), in floats) and where its
-// POSE_UNITS + 1 partial forces start in the force slab (units).  Resident: n atoms, the same for every pose.  GUEST: the pose's record,
-// uniform over the workgroup and kept in scalar registers; the blocks of partial forces start at double (POSE_UNITS + 1) x xyz.
-template <bool GUEST>
-struct StepLigand {
-    uint32_t count, pose, xoff;
-    __device__ __forceinline__ StepLigand(const PoseRec* rec, uint32_t n, uint32_t p) : count(n), pose(p), xoff(0u) {
-        if constexpr (GUEST) {
-            count = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec[p].count);
-            xoff = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec[p].xyz);
-        }
-    }
-    __device__ __forceinline__ size_t at(uint32_t i) const {
-        if constexpr (GUEST) return (size_t)xoff + i * 3u;
-        else return ((size_t)pose * count + i) * 3u;
-    }
-    __device__ __forceinline__ const double* units(const double* fslab, uint32_t i) const {
-        if constexpr (GUEST) return fslab + (size_t)(POSE_UNITS + 1u) * xoff + i * 3u;
-        else return fslab + ((size_t)pose * (POSE_UNITS + 1u) * count + i) * 3u;
-    }
-};
 
 // forces[pose][atom] = the units' partial forces added in unit order (fp64, rounded once); rigid[pose] = (sum_i f_i, sum_i (x_i - c) x f_i),
 // c the unweighted mean of the pose's coordinates as the caller gave them - fp64, atom order, of the unrounded forces.
@@ -460,270 +429,13 @@ __global__ __launch_bounds__(256) void guest_force_sum_kernel(const PoseRec* __r
     pose_force_sum<true>(rec, 0u, poses, fslab, forces, rigid);
 }
 
-// The step kernel's arguments, every instantiation; the rigid ones leave T, n_terms, eterm and the table pointers zero.  G is the width
-// of a row.  Guests (rec != null): G is the groups + 1, count is unused, and "[..][count][3]" reads "as the chunk's coordinates lie"
-// (StepLigand).
-struct StepArgs {
-    uint32_t count, G, T, n_terms;
-    float* stage;                  // [poses of the chunk][count][3]: the trial the force flavour evaluated; receives the next one
-    const double* slab; const double* fslab;
-    uint32_t* frozen; void* st;    // st: [poses of the chunk] mdx_rf_state (rigid) or mdx_fx_state (flexible)
-    float* x0;                     // [..][count][3] the input poses (kept at evaluation 0)
-    float* y; float* row; float* rigid;      // the accepted state: coordinates [..][count][3], row [..][G], rigid [..][6]
-    double* eterm;                 // [poses of the chunk][n_terms][13]: energy and the four atoms' forces of every term at this evaluation
-    const mdx_fx_torsion* tor; const mdx_fx_dihedral* dih; const uint32_t* aoff; const uint32_t* aent;
-    double box[3];                 // periodic axes (0: none), as the force pass has them
-    mdx_fx_opts o;
-    const PoseRec* rec;            // guests: [poses of the chunk] (last: the resident kernels read their arguments where they always did)
-};
-
-__device__ __forceinline__ mdx_rf_state& rf_of(mdx_rf_state& s) { return s; }
-__device__ __forceinline__ mdx_rf_state& rf_of(mdx_fx_state& s) { return s.rf; }
-
-// ---- the stages of one evaluation (LDS arrays are the caller's) ----
-// Rows and forces of the 17 units added in unit order and rounded where pose_sum_kernel / pose_run and pose_force_sum_kernel round
-// them, the staged trial in fp64; WITH_F (flexible): s_f takes the fp32 force mdx_pose_forces returns - what a host loop has.
-// A non-finite value raises *s_bad.  Ends with a barrier.
-template <bool WITH_F, bool GUEST>
-__device__ __forceinline__ void step_gather(const StepArgs& a, const StepLigand<GUEST>& lig, uint32_t pose, uint32_t tid, float* s_row,
-                                            double (*s_v)[3], double (*s_x)[3], double (*s_f)[3], uint32_t* s_bad) {
-    const uint32_t count = lig.count;
-    bool bad = false;
-    if (tid < a.G) {
-        const float r = (float)pose_units_sum(a.slab + (size_t)pose * (POSE_UNITS + 1u) * a.G + tid, a.G);
-        s_row[tid] = r;
-        bad = !isfinite(r);
-    }
-    if (tid < count) {
-        const double* s = lig.units(a.fslab, tid);
-        const size_t at = lig.at(tid);
-        for (uint32_t c = 0; c < 3u; ++c) {
-            const double v = pose_units_sum(s + c, (size_t)count * 3u);
-            s_v[tid][c] = v; s_x[tid][c] = (double)a.stage[at + c];
-            if constexpr (WITH_F) s_f[tid][c] = (double)(float)v;
-            bad = bad || !isfinite((float)v);
-        }
-    }
-    if (bad) *s_bad = 1u;      // (every writer stores the same word)
-    __syncthreads();
-}
-
-// the accepted state leaves for the chunk's block: coordinates, row and rigid of a stored trial; the input pose at evaluation 1
-template <bool GUEST>
-__device__ __forceinline__ void step_store(const StepArgs& a, const StepLigand<GUEST>& lig, uint32_t pose, uint32_t tid, uint32_t fl, bool first,
-                                           const float* s_row, const float* s_rigid) {
-    const size_t at = lig.at(tid);
-    if (fl & MDX_RF_STORE) {
-        if (tid < lig.count)
-            for (uint32_t c = 0; c < 3u; ++c) a.y[at + c] = a.stage[at + c];
-        if (tid < a.G) a.row[(size_t)pose * a.G + tid] = s_row[tid];
-        if (tid < 6u) a.rigid[(size_t)pose * 6u + tid] = s_rigid[tid];
-    }
-    if (first && tid < lig.count)
-        for (uint32_t c = 0; c < 3u; ++c) a.x0[at + c] = a.stage[at + c];
-}
-
-// the largest atom speed of the new direction (a maximum: exact in any order) from every thread's m; thread 0 hands it to
-// rf_set_speed.  Two barriers; returns the flags with rf_set_speed's.
-__device__ __forceinline__ uint32_t step_max_speed(double m, uint32_t tid, uint32_t fl, mdx_rf_state& rf, double* s_m, uint32_t* s_flags) {
-#pragma unroll
-    for (int k = 32; k > 0; k >>= 1) { const double o = __shfl_xor(m, k); m = o > m ? o : m; }
-    if ((tid & 63u) == 0u) s_m[tid >> 6] = m;
-    __syncthreads();
-    if (tid == 0u) {
-        double mm = s_m[0];
-        for (int k = 1; k < 4; ++k) mm = s_m[k] > mm ? s_m[k] : mm;
-        *s_flags = fl | rf_set_speed(rf, mm);
-    }
-    __syncthreads();
-    return *s_flags;
-}
-
-// B(theta) in place: s_x holds the pose in fp64; the torsions in order, each a rotation of its moving set about its axis as the
-// coordinates then stand (fx_build with the atoms over the threads).  One barrier per non-zero torsion: the axis of torsion k depends on
-// the rotations before it, and the axis atoms are not written in their own round.  tor may lie in LDS or in global memory.
-__device__ __forceinline__ void pose_build_torsions(double (*s_x)[3], const mdx_fx_torsion* tor, const double* th, const double* cs,
-                                                    const double* sn, uint32_t T, uint32_t count, uint32_t tid) {
-    for (uint32_t k = 0; k < T; ++k) {
-        if (th[k] == 0.0) continue;      // (uniform over the workgroup)
-        const mdx_fx_torsion& t = tor[k];
-        double u[3];
-        const bool turns = fx_axis(&s_x[0][0], t, u);
-        if (turns && tid < count && tid != t.b && fx_member(t.mask, tid)) {
-            const double b[3] = {s_x[t.b][0], s_x[t.b][1], s_x[t.b][2]};
-            fx_rotate(u, b, cs[k], sn[k], s_x[tid]);
-        }
-        __syncthreads();
-    }
-}
-
-// One evaluation of every live pose ends here: gather, frame, then the stepper of mdx_refine_step.h (FLEX: mdx_flex_step.h).  Thread 0
-// takes the decisions (a few dozen fp64 operations); the sums over atoms run one component per thread, in atom order.
-// FLEX adds the dihedral terms (thread t: term t, its energy and four forces through eterm; one thread adds the energies in list order
-// while thread i gathers the forces of the terms that name atom i, in list order), g_k / J_k (thread k, members in atom order), the
-// torsion part of the atom field, and the trial builder: B(theta) in LDS from the input pose, then the rigid image of it.  The rigid
-// instantiation names none of the FLEX arrays (they take no LDS there) and forms the next trial from x0 by rf_coords.
-template <bool FLEX, bool GUEST = false>
-__device__ __forceinline__ void pose_step(const StepArgs& a) {
-    static_assert(!(FLEX && GUEST), "guest ligands: the rigid refinement only");
-    using State = typename std::conditional<FLEX, mdx_fx_state, mdx_rf_state>::type;
-    // s_f, s_g .. s_bc, s_edih and s_tor are FLEX only.  The rigid instantiation must read and write none of them (s_f is handed to
-    // step_gather<false>, which does not touch it): an array nobody uses takes no LDS, and that is all that keeps the rigid kernel at
-    // 13,752 B and 8 workgroups per CU.  After a change here, read "LDS Size" of both instantiations in the
-    // -Rpass-analysis=kernel-resource-usage remarks (13,752 / 26,088 B).  The order of the declarations is the LDS layout's.
-    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_v[MDX_POSE_MAX_ATOMS][3], s_f[MDX_POSE_MAX_ATOMS][3], s_c[3], s_I[6], s_R[9], s_m[4];
-    __shared__ double s_g[MDX_FX_MAX_TORSIONS], s_J[MDX_FX_MAX_TORSIONS], s_A[MDX_FX_MAX_TORSIONS][3], s_u[MDX_FX_MAX_TORSIONS][3],
-                      s_sh[MDX_FX_MAX_TORSIONS][3], s_wk[MDX_FX_MAX_TORSIONS], s_cs[MDX_FX_MAX_TORSIONS], s_sn[MDX_FX_MAX_TORSIONS], s_bc[3];
-    __shared__ float s_row[256], s_rigid[6], s_edih;
-    __shared__ State s_st;
-    __shared__ mdx_fx_torsion s_tor[MDX_FX_MAX_TORSIONS];
-    __shared__ uint32_t s_bad, s_flags;
-    const uint32_t tid = threadIdx.x, pose = blockIdx.x, T = a.T;
-    if (a.frozen[pose] != 0u) return;      // (uniform over the workgroup, before any barrier)
-    const StepLigand<GUEST> lig(a.rec, a.count, pose);
-    const uint32_t count = lig.count;
-    uint32_t* const rec = (uint32_t*)((State*)a.st + pose);
-    for (uint32_t i = tid; i < sizeof(State) / 4u; i += 256u) ((uint32_t*)&s_st)[i] = rec[i];
-    if constexpr (FLEX)
-        for (uint32_t i = tid; i < T * (uint32_t)(sizeof(mdx_fx_torsion) / 4u); i += 256u) ((uint32_t*)s_tor)[i] = ((const uint32_t*)a.tor)[i];
-    if (tid == 0u) s_bad = 0u;
-    __syncthreads();
-    mdx_rf_state& rf = rf_of(s_st);
-    step_gather<FLEX>(a, lig, pose, tid, s_row, s_v, s_x, s_f, &s_bad);      // (s_f: written under FLEX only)
-    // centroid | barrier | rigid by the statement of pose_force_sum_kernel beside the six inertia sums on a wave of their own; the
-    // FLEX parts share those two intervals, so the three statements stand here and not in a helper
-    if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
-    double* eterm = nullptr;
-    if constexpr (FLEX) {
-        // the ligand's dihedral terms, one term per thread: its energy and its four forces go through eterm
-        eterm = a.eterm + (size_t)pose * a.n_terms * FLEX_TERM_WORDS;
-        const double box[3] = {a.box[0], a.box[1], a.box[2]};
-        for (uint32_t t = tid; t < a.n_terms; t += 256u) {
-            double f[4][3];
-            double* o = eterm + (size_t)t * FLEX_TERM_WORDS;
-            o[0] = fx_dihedral(&s_x[0][0], a.dih[t], box, f);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { o[1 + 3 * r] = f[r][0]; o[2 + 3 * r] = f[r][1]; o[3 + 3 * r] = f[r][2]; }
-        }
-    }
-    __syncthreads();
-    if (tid < 6u) s_rigid[tid] = (float)pose_rigid_component(tid, count, s_x, s_v, s_c);
-    if (tid >= 64u && tid < 70u) s_I[tid - 64u] = rf_inertia(&s_x[0][0], count, s_c, tid - 64u);
-    if constexpr (FLEX) {
-        if (tid == 128u) {      // the energies in list order
-            double e = 0.0;
-            for (uint32_t t = 0; t < a.n_terms; ++t) e += eterm[(size_t)t * FLEX_TERM_WORDS];
-            s_edih = (float)e;
-        }
-        if (tid < count && a.n_terms) {
-            // thread i: the forces of the terms that name atom i, in list order - the atom-owned gather
-            double f0 = 0.0, f1 = 0.0, f2 = 0.0;
-            for (uint32_t e = a.aoff[tid]; e < a.aoff[tid + 1u]; ++e) {
-                const uint32_t w = a.aent[e];
-                const double* o = eterm + (size_t)(w >> 2) * FLEX_TERM_WORDS + 1u + 3u * (w & 3u);
-                f0 += o[0]; f1 += o[1]; f2 += o[2];
-            }
-            if (!isfinite(f0) || !isfinite(f1) || !isfinite(f2)) s_bad = 1u;
-            s_f[tid][0] += f0; s_f[tid][1] += f1; s_f[tid][2] += f2;
-        }
-        __syncthreads();
-        if (tid < T) {
-            const double n = (double)count;
-            const double v[3] = {(double)s_rigid[0] / n, (double)s_rigid[1] / n, (double)s_rigid[2] / n};
-            fx_gradient(&s_x[0][0], &s_f[0][0], count, v, s_tor[tid], s_u[tid], s_g[tid], s_J[tid], s_A[tid]);
-        }
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        bool finite = s_bad == 0u;
-        for (int k = 0; k < 6; ++k) finite = finite && isfinite(s_rigid[k]);
-        double S = 0.0;
-        for (uint32_t b = 0; b < a.G; ++b) S += (double)s_row[b];
-        uint32_t fl;
-        if constexpr (FLEX) {
-            double gmax = 0.0;
-            finite = finite && isfinite(s_edih);      // (here: read ahead of the row sum, the evaluation measured 0.3 us slower)
-            S += (double)s_edih;
-            for (uint32_t k = 0; k < T; ++k) {
-                const double g = fabs(s_g[k]);
-                finite = finite && isfinite(g);
-                gmax = g > gmax ? g : gmax;
-            }
-            if (rf.evals == 0u) fx_start(s_st, s_c, a.o.rf.h_start);      // (the record was zeroed: the trial is the input pose)
-            fl = fx_decide(s_st, a.o, T, S, finite, s_rigid, gmax);
-            if (fl & MDX_RF_STORE) {
-                s_st.edih = s_edih;
-                for (uint32_t k = 0; k < T; ++k) s_st.g[k] = s_g[k];
-            }
-        } else {
-            if (rf.evals == 0u) rf_start(rf, s_c, a.o.rf.h_start);        // (likewise)
-            fl = rf_decide(rf, a.o.rf, S, finite, s_rigid);
-        }
-        if (fl == MDX_RF_STORE) rf_direction(rf, count, s_rigid, s_I);
-        s_flags = fl;
-    }
-    if constexpr (FLEX)
-        if (tid >= 64u && tid < 64u + T) {      // (a wave beside thread 0's: used only if the trial is stored and the pose goes on)
-            const uint32_t k = tid - 64u;
-            s_wk[k] = fx_omega(s_g[k], s_J[k]);
-            fx_shift(s_wk[k], s_A[k], count, s_sh[k]);
-        }
-    __syncthreads();
-    if constexpr (FLEX)
-        if (s_flags == MDX_RF_STORE && tid < T) s_st.wk[tid] = s_wk[tid];      // (read again only after the next barrier)
-    uint32_t fl = s_flags;
-    step_store(a, lig, pose, tid, fl, rf.evals == 1u, s_row, s_rigid);
-    if (fl == MDX_RF_STORE) {
-        double m = 0.0;
-        if (tid < count) {
-            if constexpr (FLEX) m = fx_speed(rf.v, rf.w, s_c, &s_x[0][0], tid, T, s_tor, s_u, s_wk, s_sh);
-            else {
-                const double r[3] = {s_x[tid][0] - s_c[0], s_x[tid][1] - s_c[1], s_x[tid][2] - s_c[2]};
-                m = rf_speed(rf.v, rf.w, r);
-            }
-        }
-        fl = step_max_speed(m, tid, fl, rf, s_m, &s_flags);
-    }
-    const size_t at = lig.at(tid);
-    if (!(fl & MDX_RF_FROZEN)) {
-        if (tid == 0u) {
-            if constexpr (FLEX) fx_trial(s_st, T); else rf_trial(rf);
-            rf_rotation(rf.qt, s_R);
-        }
-        if constexpr (FLEX) {
-            // B(theta_try) from the input pose: s_x is free now
-            if (tid < count)
-                for (uint32_t c = 0; c < 3u; ++c) s_x[tid][c] = (double)a.x0[at + c];
-            __syncthreads();
-            if (tid < T) { s_cs[tid] = cos(s_st.tht[tid]); s_sn[tid] = sin(s_st.tht[tid]); }
-            __syncthreads();
-            pose_build_torsions(s_x, s_tor, s_st.tht, s_cs, s_sn, T, count, tid);
-            if (tid < 3u) s_bc[tid] = rf_mean(&s_x[0][0], count, tid);
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < sizeof(State) / 4u; i += 256u) rec[i] = ((const uint32_t*)&s_st)[i];
-    if (fl & MDX_RF_FROZEN) {
-        if (tid == 0u) a.frozen[pose] = 1u;
-        return;
-    }
-    if (tid < count) {
-        float y[3];
-        if constexpr (FLEX) fx_coords(rf.c0, rf.tt, s_R, s_x[tid], s_bc, y);
-        else {
-            const float x0[3] = {a.x0[at], a.x0[at + 1u], a.x0[at + 2u]};
-            rf_coords(rf.c0, rf.tt, s_R, x0, y);
-        }
-        for (uint32_t c = 0; c < 3u; ++c) a.stage[at + c] = y[c];
-    }
-}
-
 // The two step kernels: one body, two plain kernels under the names they had as separate copies.  (A kernel template
 // pose_step_kernel<FLEX> gave the same instructions but left its instantiations behind the 24 pose_score_kernel ones in the code
 // object; it measured 0.5 % slower in the flexible arm and no cause was found in the instructions - DESIGN.md 7h.)
 __global__ __launch_bounds__(256) void pose_refine_step_kernel(StepArgs a) { pose_step<false>(a); }
 __global__ __launch_bounds__(256) void pose_flex_step_kernel(StepArgs a) { pose_step<true>(a); }
 __global__ __launch_bounds__(256) void guest_refine_step_kernel(StepArgs a) { pose_step<false, true>(a); }
+// (guest_flex_step_kernel, pose_step<true, true>, stands in mdx_guest_flex.hip: see mdx_pose_step_dev.h)
 
 template <int COUL>
 static void launch_poses(mdx_handle* h, const PoseArgs& a, bool geom, uint32_t n, bool force, bool refine = false, bool guest = false) {
@@ -1004,11 +716,12 @@ static StepArgs step_args(mdx_handle* h, const PoseArgs& a, unsigned char* blk, 
     return r;
 }
 
-// one evaluation of a chunk: the REFINE force pass, then the step kernel (guests: r.rec is set, and the refinement is the rigid one)
+// one evaluation of a chunk: the REFINE force pass, then the step kernel (guests: r.rec is set)
 template <bool FLEX>
 static void step_evaluate(mdx_handle* h, const PoseArgs& a, int mode, bool geom, uint32_t n, const StepArgs& r) {
     pose_launch(h, a, mode, geom, n, true, true, r.rec != nullptr);
-    if (r.rec) hipLaunchKernelGGL(guest_refine_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
+    if (r.rec && FLEX) mdx_launch_guest_flex_step(h->stream, n, r);
+    else if (r.rec) hipLaunchKernelGGL(guest_refine_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
     else if (FLEX) hipLaunchKernelGGL(pose_flex_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
     else hipLaunchKernelGGL(pose_refine_step_kernel, dim3(n), dim3(256), 0, h->stream, r);
 }
@@ -1103,17 +816,13 @@ extern "C" int mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, u
 
 // ---- the flexible refinement's own: the torsion list and its table -----------------------------------------------------------------------
 
-// What can be refused of a torsion list on the host's copy of the topology alone: the range's bonds, the moving sides.  tor: [n_torsions]
-static int flex_graph(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t root, uint32_t n_torsions,
+// The moving sides of a torsion list over a ligand-local bond graph, with the refusals in words - what does not depend on where the
+// graph comes from (the handle's topology: flex_graph; the caller's: guest_check).  tor: [MDX_FX_MAX_TORSIONS]
+static int flex_sides(const std::string& who, uint32_t count, uint32_t n_bonds, const uint32_t* bonds, uint32_t root, uint32_t n_torsions,
                       const uint32_t* tb, std::vector<mdx_fx_torsion>& tor) {
-    std::vector<uint32_t> bonds;
-    for (size_t k = 0; k + 1 < h->h_bond_pairs.size(); k += 2) {
-        const uint32_t p = h->h_bond_pairs[k], q = h->h_bond_pairs[k + 1];
-        if (p >= first && p - first < count && q >= first && q - first < count) { bonds.push_back(p - first); bonds.push_back(q - first); }
-    }
     tor.assign(MDX_FX_MAX_TORSIONS, mdx_fx_torsion{});
     uint32_t bad = 0;
-    const int rc = fx_moving_sides(count, (uint32_t)(bonds.size() / 2), bonds.data(), root, n_torsions, tb, tor.data(), &bad);
+    const int rc = fx_moving_sides(count, n_bonds, bonds, root, n_torsions, tb, tor.data(), &bad);
     const std::string t = who + ": torsion " + std::to_string(bad);
     switch (rc) {
     case MDX_FX_OK: return MDX_OK;
@@ -1126,6 +835,30 @@ static int flex_graph(mdx_handle* h, const std::string& who, uint32_t first, uin
     case MDX_FX_E_LEAF: FAIL(MDX_EPARAM, t + ": one side of the bond is a single atom (a leaf bond: the torsion moves nothing)");
     default: FAIL(MDX_EPARAM, who + ": the bond graph of the range is not connected");
     }
+}
+
+// What can be refused of a torsion list on the host's copy of the topology alone: the range's bonds, the moving sides
+static int flex_graph(mdx_handle* h, const std::string& who, uint32_t first, uint32_t count, uint32_t root, uint32_t n_torsions,
+                      const uint32_t* tb, std::vector<mdx_fx_torsion>& tor) {
+    std::vector<uint32_t> bonds;
+    for (size_t k = 0; k + 1 < h->h_bond_pairs.size(); k += 2) {
+        const uint32_t p = h->h_bond_pairs[k], q = h->h_bond_pairs[k + 1];
+        if (p >= first && p - first < count && q >= first && q - first < count) { bonds.push_back(p - first); bonds.push_back(q - first); }
+    }
+    return flex_sides(who, count, (uint32_t)(bonds.size() / 2), bonds.data(), root, n_torsions, tb, tor);
+}
+
+// the atom-owned gather of a ligand's terms: aoff [count + 1], aent [4 n_terms] = per atom the (term << 2 | role) words that name it, in
+// list order
+static void flex_gather(uint32_t count, const std::vector<mdx_fx_dihedral>& dih, std::vector<uint32_t>& aoff, std::vector<uint32_t>& aent) {
+    const uint32_t n_terms = (uint32_t)dih.size();
+    aoff.assign(count + 1u, 0u); aent.assign(4u * (size_t)n_terms, 0u);
+    for (const mdx_fx_dihedral& t : dih)
+        for (int r = 0; r < 4; ++r) aoff[t.at[r] + 1u]++;
+    for (uint32_t i = 0; i < count; ++i) aoff[i + 1u] += aoff[i];
+    std::vector<uint32_t> cur(aoff.begin(), aoff.end() - 1);
+    for (uint32_t k = 0; k < n_terms; ++k)
+        for (uint32_t r = 0; r < 4u; ++r) aent[cur[dih[k].at[r]]++] = (k << 2) | r;
 }
 
 // The table on the device, once per (range, group epoch, root, torsion list, flags)
@@ -1149,13 +882,8 @@ static int flex_table(mdx_handle* h, const std::string& who, uint32_t first, uin
     }
     const uint32_t n_terms = (uint32_t)dih.size();
     if (n_terms >= (1u << 30)) FAIL(MDX_EPARAM, who + ": too many dihedral terms in the range");
-    std::vector<uint32_t> aoff(count + 1u, 0u), aent(4u * (size_t)n_terms);
-    for (const mdx_fx_dihedral& t : dih)
-        for (int r = 0; r < 4; ++r) aoff[t.at[r] + 1u]++;
-    for (uint32_t i = 0; i < count; ++i) aoff[i + 1u] += aoff[i];
-    std::vector<uint32_t> cur(aoff.begin(), aoff.end() - 1);
-    for (uint32_t k = 0; k < n_terms; ++k)
-        for (uint32_t r = 0; r < 4u; ++r) aent[cur[dih[k].at[r]]++] = (k << 2) | r;
+    std::vector<uint32_t> aoff, aent;
+    flex_gather(count, dih, aoff, aent);
     const FlexTable lay(count, n_terms);
     std::vector<unsigned char> img(lay.end, 0);
     std::memcpy(img.data() + lay.tor, tor.data(), sizeof(mdx_fx_torsion) * MDX_FX_MAX_TORSIONS);
@@ -1393,30 +1121,39 @@ struct GuestBest { double score; uint32_t pose, pad; };      // smallest row sum
 // (lig_of[p] = (ligand, ligand-local pose); a ligand's poses are consecutive), S = the fp32-rounded row added in column order in fp64 -
 // what a host gets from the returned rows - and a strictly smaller S replaces the carried one: the lowest index wins a tie, also
 // across chunks.  One writer per ligand, no atomics.  Row: double (the summed rows of mdx_screen_ligands) or float (the accepted rows
-// of a refinement; st: its state records - a pose that ended MDX_REFINE_NONFINITE is passed over whatever its row holds).
-template <class Row>
+// of a refinement; st: its state records - a pose that ended MDX_REFINE_NONFINITE is passed over whatever its row holds; the flexible
+// refinement's records add their accepted E_dih behind the columns).
+__device__ __forceinline__ const mdx_rf_state& rf_of(const mdx_rf_state& s) { return s; }
+__device__ __forceinline__ const mdx_rf_state& rf_of(const mdx_fx_state& s) { return s.rf; }
+template <class Row, class State>
 __device__ __forceinline__ void guest_best(uint32_t n, uint32_t W, const Row* __restrict__ rows, const uint2* __restrict__ lig_of,
-                                           const mdx_rf_state* __restrict__ st, GuestBest* __restrict__ best) {
+                                           const State* __restrict__ st, GuestBest* __restrict__ best) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const uint32_t m = lig_of[p].x;
     if (p > 0u && lig_of[p - 1u].x == m) return;
     GuestBest b = best[m];
     for (uint32_t k = p; k < n && lig_of[k].x == m; ++k) {
-        if (st && st[k].frozen != 0u && st[k].status == MDX_RF_NONFINITE) continue;
+        if (st && rf_of(st[k]).frozen != 0u && rf_of(st[k]).status == MDX_RF_NONFINITE) continue;
         double S = 0.0;
         for (uint32_t c = 0; c < W; ++c) S += (double)(float)rows[(size_t)k * W + c];
+        if constexpr (std::is_same<State, mdx_fx_state>::value) S += (double)st[k].edih;
         if (S < b.score) { b.score = S; b.pose = lig_of[k].y; }
     }
     best[m] = b;
 }
 __global__ __launch_bounds__(256) void guest_best_kernel(uint32_t n, uint32_t W, const double* __restrict__ rows, const uint2* __restrict__ lig_of,
                                                          GuestBest* __restrict__ best) {
-    guest_best(n, W, rows, lig_of, nullptr, best);
+    guest_best(n, W, rows, lig_of, (const mdx_rf_state*)nullptr, best);
 }
 __global__ __launch_bounds__(256) void guest_best_refined_kernel(uint32_t n, uint32_t W, const float* __restrict__ rows,
                                                                  const uint2* __restrict__ lig_of, const mdx_rf_state* __restrict__ st,
                                                                  GuestBest* __restrict__ best) {
+    guest_best(n, W, rows, lig_of, st, best);
+}
+__global__ __launch_bounds__(256) void guest_best_flex_kernel(uint32_t n, uint32_t W, const float* __restrict__ rows,
+                                                              const uint2* __restrict__ lig_of, const mdx_fx_state* __restrict__ st,
+                                                              GuestBest* __restrict__ best) {
     guest_best(n, W, rows, lig_of, st, best);
 }
 
@@ -1440,8 +1177,41 @@ static const char* guest_class_map(const mdx_guest_ligand& g, std::vector<uint8_
     return nullptr;
 }
 
+// What mdx_guest_flex adds to a ligand, as the kernels take it: the torsions with their moving sets, the terms that count (none without
+// MDX_FLEX_DIHEDRALS or under MDX_OVR_BONDED_DISABLED) and their gather tables
+struct GuestFlexTables { std::vector<mdx_fx_torsion> tor; std::vector<mdx_fx_dihedral> dih; std::vector<uint32_t> aoff, aent; };
+
+// the refusals of one ligand's mdx_guest_flex (who: the call and the ligand), then its tables
+static int guest_flex_check(const std::string& who, uint32_t count, const mdx_guest_flex& f, bool dihedrals, GuestFlexTables& t) {
+    if (f.n_torsions > MDX_POSE_MAX_TORSIONS) FAIL(MDX_EPARAM, who + ": n_torsions exceeds MDX_POSE_MAX_TORSIONS (32)");
+    if ((f.n_bonds && !f.bonds) || (f.n_torsions && !f.torsion_bonds) ||
+        (f.n_dihedrals && (!f.dihedral_idx || !f.dihedral_v || !f.dihedral_phase || !f.dihedral_n)))
+        FAIL(MDX_EPARAM, who + ": null argument (a list of the flexible record with a non-zero count)");
+    if (f.n_dihedrals >= (1u << 20)) FAIL(MDX_EPARAM, who + ": too many dihedral terms");
+    for (uint32_t k = 0; k < f.n_bonds; ++k) {
+        const uint32_t a = f.bonds[2 * (size_t)k], b = f.bonds[2 * (size_t)k + 1];
+        if (a >= count || b >= count) FAIL(MDX_EPARAM, who + ": bond " + std::to_string(k) + " names an atom index >= count");
+        if (a == b) FAIL(MDX_EPARAM, who + ": bond " + std::to_string(k) + " names the same atom twice");
+    }
+    MDX_TRY(flex_sides(who, count, f.n_bonds, f.bonds, f.root, f.n_torsions, f.torsion_bonds, t.tor));
+    t.tor.resize(f.n_torsions);
+    t.dih.clear();
+    for (uint32_t k = 0; k < f.n_dihedrals; ++k) {
+        const uint32_t* at = f.dihedral_idx + 4 * (size_t)k;
+        for (int r = 0; r < 4; ++r)
+            if (at[r] >= count) FAIL(MDX_EPARAM, who + ": dihedral term " + std::to_string(k) + " names an atom index >= count");
+        if (!std::isfinite(f.dihedral_v[k]) || !std::isfinite(f.dihedral_phase[k]))
+            FAIL(MDX_EPARAM, who + ": dihedral term " + std::to_string(k) + ": v or phase is not finite");
+        if (dihedrals)
+            t.dih.push_back(mdx_fx_dihedral{{at[0], at[1], at[2], at[3]}, (double)f.dihedral_v[k], (double)f.dihedral_phase[k], (double)f.dihedral_n[k]});
+    }
+    flex_gather(count, t.dih, t.aoff, t.aent);
+    return MDX_OK;
+}
+
 // A call on a library: its plan, the kernel arguments, the staging buffer
 struct GuestRun {
+    std::vector<GuestFlexTables> fx;      // mdx_refine_guests_flex: [n_ligands]
     std::vector<GuestShape> shapes;
     std::vector<size_t> pstart;
     std::vector<GuestChunk> chunks;
@@ -1453,8 +1223,9 @@ struct GuestRun {
     int mode = 0; bool geom = false;
 };
 
-// the refusals that need no device, then the plan
-static int guest_check(mdx_handle* h, const std::string& who, uint32_t n_ligands, const mdx_guest_ligand* ligs, uint32_t n_groups, GuestRun& run) {
+// the refusals that need no device, then the plan; flex (mdx_refine_guests_flex alone): the ligands' flexible records under `flags`
+static int guest_check(mdx_handle* h, const std::string& who, uint32_t n_ligands, const mdx_guest_ligand* ligs, uint32_t n_groups, GuestRun& run,
+                       const mdx_guest_flex* flex = nullptr, uint32_t flags = 0u) {
     const uint32_t G = h->n_grp;
     if (!G) FAIL(MDX_EPARAM, "no energy groups are set (mdx_set_energy_groups)");
     if (n_groups != G) FAIL(MDX_EPARAM, "n_groups must be the number of groups (mdx_energy_group_count)");
@@ -1463,6 +1234,7 @@ static int guest_check(mdx_handle* h, const std::string& who, uint32_t n_ligands
     const bool skip14 = (h->cfg.overrides & MDX_OVR_BONDED_DISABLED) != 0;
     std::vector<uint8_t> cls;
     run.shapes.resize(n_ligands);
+    run.fx.resize(flex ? n_ligands : 0u);
     for (uint32_t m = 0; m < n_ligands; ++m) {
         const mdx_guest_ligand& g = ligs[m];
         const std::string lig = who + ": ligand " + std::to_string(m) + ": ";
@@ -1478,7 +1250,11 @@ static int guest_check(mdx_handle* h, const std::string& who, uint32_t n_ligands
         const size_t nx = 3 * (size_t)g.count * g.n_poses;
         for (size_t k = 0; k < nx; ++k)
             if (!std::isfinite(g.poses[k])) FAIL(MDX_EPARAM, lig + "non-finite pose coordinate");
-        run.shapes[m] = GuestShape{g.count, g.n_poses, skip14 ? 0u : g.n_pairs14};
+        run.shapes[m] = GuestShape{g.count, g.n_poses, skip14 ? 0u : g.n_pairs14, 0u, 0u};
+        if (flex) {
+            MDX_TRY(guest_flex_check(who + ": ligand " + std::to_string(m), g.count, flex[m], (flags & MDX_FLEX_DIHEDRALS) != 0u && !skip14, run.fx[m]));
+            run.shapes[m].T = (uint32_t)run.fx[m].tor.size(); run.shapes[m].n_terms = (uint32_t)run.fx[m].dih.size();
+        }
     }
     guest_plan(run.shapes, run.pstart, run.chunks);
     run.total = run.pstart[n_ligands];
@@ -1486,7 +1262,7 @@ static int guest_check(mdx_handle* h, const std::string& who, uint32_t n_ligands
 }
 
 static GuestLayout guest_layout(const GuestChunk& c, uint32_t W, int gmode) {
-    return GuestLayout(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W, gmode, sizeof(mdx_rf_state));
+    return GuestLayout(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W, gmode, gmode == GUEST_FLEX ? sizeof(mdx_fx_state) : sizeof(mdx_rf_state), c.fx);
 }
 
 // the device side of a call that has work: the list of the current state, the block (it follows the largest chunk), the carried best
@@ -1534,6 +1310,8 @@ static int guest_stage(mdx_handle* h, const mdx_guest_ligand* ligs, const GuestC
     float* xyz = (float*)(up.data() + lay.xyz);
     guest_slots(run.shapes, run.pstart, c, run.slots);
     guest_records(run.shapes, run.slots, (PoseRec*)(up.data() + lay.rec), (uint32_t*)(up.data() + lay.ligof));
+    const bool flex = !run.fx.empty();      // (the layout is GUEST_FLEX's then)
+    if (flex) guest_flex_records(run.shapes, run.slots, (FlexRec*)(up.data() + lay.frec));
     std::vector<uint8_t> cls;
     for (const GuestSlot& s : run.slots) {
         const mdx_guest_ligand& g = ligs[s.m];
@@ -1555,6 +1333,15 @@ static int guest_stage(mdx_handle* h, const mdx_guest_ligand* ligs, const GuestC
             p14[s.p14 + k] = Pose14{i, j, prm.x, prm.y, prm.z};
         }
         std::memcpy(xyz + s.xyz, g.poses + 3 * (size_t)cnt * s.l0, sizeof(float) * 3 * cnt * (s.l1 - s.l0));
+        if (flex) {      // the ligand's flexible tables, once, as its rows above
+            const GuestFlexTables& t = run.fx[s.m];
+            if (!t.tor.empty()) std::memcpy(up.data() + lay.tor + sizeof(mdx_fx_torsion) * s.tor, t.tor.data(), sizeof(mdx_fx_torsion) * t.tor.size());
+            if (!t.dih.empty()) {
+                std::memcpy(up.data() + lay.dih + sizeof(mdx_fx_dihedral) * s.dih, t.dih.data(), sizeof(mdx_fx_dihedral) * t.dih.size());
+                std::memcpy(up.data() + lay.aent + sizeof(uint32_t) * 4u * s.dih, t.aent.data(), sizeof(uint32_t) * t.aent.size());
+            }
+            std::memcpy(up.data() + lay.aoff + sizeof(uint32_t) * s.aoff, t.aoff.data(), sizeof(uint32_t) * t.aoff.size());
+        }
     }
     unsigned char* blk = (unsigned char*)h->d.gs_blk;
     HIP_TRY(hipMemcpyAsync(blk, up.data(), lay.up_end, hipMemcpyHostToDevice, h->stream));
@@ -1646,51 +1433,64 @@ extern "C" int mdx_guest_forces(mdx_handle* h, uint32_t n_ligands, const mdx_gue
     return guest_run(h, "mdx_guest_forces", true, n_ligands, ligs, rows_or_null, n_groups, forces, rigid_or_null, nullptr, nullptr);
 }
 
-// The loop of refine_chunks over the chunks of a library: per chunk one upload, the frozen words and records zeroed, max_evals x (the
-// GUEST REFINE force pass, guest_refine_step_kernel), the best kernel on the accepted rows, one read-back, one wait.  The staged
-// coordinates are the stage buffer: the step kernel writes the next trial where the force pass reads the pose.
-extern "C" int mdx_refine_guests(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_refine_opts* opts, float* poses_out,
-                                 float* rows_out_or_null, uint32_t n_groups, float* rigid_out_or_null, float* xform_out_or_null,
-                                 uint32_t* status_out_or_null, uint32_t* evals_out_or_null, uint32_t* best_pose_or_null,
-                                 double* best_score_or_null) {
-    const std::string who = "mdx_refine_guests";
-    if (!h) FAIL(MDX_EPARAM, "null handle");
-    if (n_ligands == 0) return MDX_OK;
-    if (!ligs || !opts) FAIL(MDX_EPARAM, "null argument");
+// The loop of refine_chunks over the chunks of a library, State = mdx_rf_state (mdx_refine_guests: flex == null) or mdx_fx_state
+// (mdx_refine_guests_flex): per chunk one upload, the frozen words and records zeroed, max_evals x (the GUEST REFINE force pass, the guest
+// step kernel of the state), the best kernel on the accepted rows, one read-back, one wait.  The staged coordinates are the stage
+// buffer: the step kernel writes the next trial where the force pass reads the pose.  xform and tgrad have the ligand's own width.
+template <class State>
+static int guest_refine(mdx_handle* h, const std::string& who, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_guest_flex* flex,
+                        const mdx_flex_opts& fo, uint32_t n_groups, const RefineOut& out, uint32_t* best_pose_or_null, double* best_score_or_null) {
+    constexpr bool FLEX = std::is_same<State, mdx_fx_state>::value;
+    constexpr int gmode = FLEX ? GUEST_FLEX : GUEST_REFINE;
     mdx_fx_opts o{};
-    MDX_TRY(refine_opts_check(who, mdx_flex_opts{opts->max_evals, opts->f_tol, opts->tau_tol, 0.f, opts->h_start, opts->h_max, 0u}, o));
+    MDX_TRY(refine_opts_check(who, fo, o));
     GuestRun run;
-    MDX_TRY(guest_check(h, who, n_ligands, ligs, n_groups, run));
+    MDX_TRY(guest_check(h, who, n_ligands, ligs, n_groups, run, flex, fo.flags));
     const size_t total = run.total;
     if (total == 0) return MDX_OK;
-    if (!poses_out) FAIL(MDX_EPARAM, "null argument");
+    if (!out.poses) FAIL(MDX_EPARAM, "null argument");
     const bool want_best = best_pose_or_null || best_score_or_null;
-    MDX_TRY(guest_ready(h, n_ligands, GUEST_REFINE, want_best, run));
+    MDX_TRY(guest_ready(h, n_ligands, gmode, want_best, run));
     DeviceState& d = h->d;
     hipStream_t st = h->stream;
     const uint32_t W = h->n_grp + 1u;
     size_t nxyz = 0;
     for (const GuestChunk& c : run.chunks) nxyz += c.nxyz;
-    std::vector<float> yres(nxyz), rres(total * W), gres(6u * total), xres(7u * total);
+    // where pose p's (q, t, theta) and g start: the ligands one behind the other, each with its own width
+    std::vector<size_t> xat(total + 1, 0), tat(total + 1, 0);
+    std::vector<uint32_t> Tof(total, 0);
+    for (uint32_t m = 0; m < n_ligands; ++m)
+        for (size_t p = run.pstart[m]; p < run.pstart[m + 1]; ++p) Tof[p] = run.shapes[m].T;
+    for (size_t p = 0; p < total; ++p) { xat[p + 1] = xat[p] + 7u + Tof[p]; tat[p + 1] = tat[p] + Tof[p]; }
+    std::vector<float> yres(nxyz), rres(total * W), gres(6u * total), xres(xat[total]), dres(FLEX ? total : 0u), tres(tat[total]);
     std::vector<uint32_t> sres(total), eres(total);
     std::vector<unsigned char> back;
     unsigned char* blk = (unsigned char*)d.gs_blk;
     size_t x0 = 0;      // first float of the chunk in poses_out
     for (const GuestChunk& c : run.chunks) {
-        const GuestLayout lay = guest_layout(c, W, GUEST_REFINE);
-        const StepLayout sl(c.n, c.nxyz, W, sizeof(mdx_rf_state), 0u);
+        const GuestLayout lay = guest_layout(c, W, gmode);
+        const StepLayout sl = StepLayout::guest(c.n, c.nxyz, W, sizeof(State), c.fx.terms);
         MDX_TRY(guest_stage(h, ligs, c, lay, run));
         PoseArgs& a = run.a;
         unsigned char* sb = blk + lay.step;
         StepArgs r = step_args(h, a, sb, 0u, W, false, 0u, 0u, sl, o);
         r.rec = a.rec;
+        if constexpr (FLEX) {
+            r.frec = (const FlexRec*)(blk + lay.frec);
+            r.eterm = (double*)(sb + sl.eterm);
+            r.tor = (const mdx_fx_torsion*)(blk + lay.tor); r.dih = (const mdx_fx_dihedral*)(blk + lay.dih);
+            r.aoff = (const uint32_t*)(blk + lay.aoff); r.aent = (const uint32_t*)(blk + lay.aent);
+        }
         a.frozen = r.frozen;
         HIP_TRY(hipMemsetAsync(sb, 0, sl.y, st));
         mdx_prof_begin(h, 0);
-        for (uint32_t k = 0; k < opts->max_evals; ++k) step_evaluate<false>(h, a, run.mode, run.geom, c.n, r);
-        if (want_best)
-            hipLaunchKernelGGL(guest_best_refined_kernel, dim3((c.n + 255u) / 256u), dim3(256), 0, st, c.n, W, (const float*)r.row,
-                               (const uint2*)(blk + lay.ligof), (const mdx_rf_state*)r.st, (GuestBest*)d.gs_best);
+        for (uint32_t k = 0; k < fo.max_evals; ++k) step_evaluate<FLEX>(h, a, run.mode, run.geom, c.n, r);
+        if (want_best) {
+            const dim3 g((c.n + 255u) / 256u), b(256);
+            const uint2* ligof = (const uint2*)(blk + lay.ligof);
+            if constexpr (FLEX) hipLaunchKernelGGL(guest_best_flex_kernel, g, b, 0, st, c.n, W, (const float*)r.row, ligof, (const mdx_fx_state*)r.st, (GuestBest*)d.gs_best);
+            else hipLaunchKernelGGL(guest_best_refined_kernel, g, b, 0, st, c.n, W, (const float*)r.row, ligof, (const mdx_rf_state*)r.st, (GuestBest*)d.gs_best);
+        }
         mdx_prof_end(h);
         HIP_TRY(hipGetLastError());
         back.resize(sl.x0 - sl.state);
@@ -1703,22 +1503,53 @@ extern "C" int mdx_refine_guests(mdx_handle* h, uint32_t n_ligands, const mdx_gu
         std::memcpy(rres.data() + c.p0 * W, b0 + sl.row, sizeof(float) * (size_t)W * c.n);
         std::memcpy(gres.data() + 6u * c.p0, b0 + sl.rigid, sizeof(float) * 6u * c.n);
         for (uint32_t k = 0; k < c.n; ++k) {
-            mdx_rf_state s;
+            State s;
             std::memcpy(&s, b0 + sl.state + sizeof(s) * k, sizeof(s));
             const size_t p = c.p0 + k;
-            refine_unpack(s, &sres[p], &eres[p], xres.data() + 7u * p);
+            if constexpr (FLEX) refine_unpack(s, Tof[p], &sres[p], &eres[p], xres.data() + xat[p], &dres[p], tres.data() + tat[p]);
+            else refine_unpack(s, &sres[p], &eres[p], xres.data() + xat[p]);
         }
         x0 += c.nxyz;
     }
-    std::memcpy(poses_out, yres.data(), sizeof(float) * yres.size());
-    if (rows_out_or_null) std::memcpy(rows_out_or_null, rres.data(), sizeof(float) * rres.size());
-    if (rigid_out_or_null) std::memcpy(rigid_out_or_null, gres.data(), sizeof(float) * gres.size());
-    if (xform_out_or_null) std::memcpy(xform_out_or_null, xres.data(), sizeof(float) * xres.size());
-    if (status_out_or_null) std::memcpy(status_out_or_null, sres.data(), sizeof(uint32_t) * sres.size());
-    if (evals_out_or_null) std::memcpy(evals_out_or_null, eres.data(), sizeof(uint32_t) * eres.size());
+    std::memcpy(out.poses, yres.data(), sizeof(float) * yres.size());
+    if (out.rows) std::memcpy(out.rows, rres.data(), sizeof(float) * rres.size());
+    if (out.rigid) std::memcpy(out.rigid, gres.data(), sizeof(float) * gres.size());
+    if (out.xform) std::memcpy(out.xform, xres.data(), sizeof(float) * xres.size());
+    if (out.dih) std::memcpy(out.dih, dres.data(), sizeof(float) * dres.size());
+    if (out.tgrad && !tres.empty()) std::memcpy(out.tgrad, tres.data(), sizeof(float) * tres.size());
+    if (out.status) std::memcpy(out.status, sres.data(), sizeof(uint32_t) * sres.size());
+    if (out.evals) std::memcpy(out.evals, eres.data(), sizeof(uint32_t) * eres.size());
     for (uint32_t m = 0; want_best && m < n_ligands; ++m) {
         if (best_pose_or_null) best_pose_or_null[m] = run.best[m].pose;
         if (best_score_or_null) best_score_or_null[m] = run.best[m].score;
     }
     return MDX_OK;
+}
+
+extern "C" int mdx_refine_guests(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_refine_opts* opts, float* poses_out,
+                                 float* rows_out_or_null, uint32_t n_groups, float* rigid_out_or_null, float* xform_out_or_null,
+                                 uint32_t* status_out_or_null, uint32_t* evals_out_or_null, uint32_t* best_pose_or_null,
+                                 double* best_score_or_null) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_ligands == 0) return MDX_OK;
+    if (!ligs || !opts) FAIL(MDX_EPARAM, "null argument");
+    return guest_refine<mdx_rf_state>(h, "mdx_refine_guests", n_ligands, ligs, nullptr,
+                                      mdx_flex_opts{opts->max_evals, opts->f_tol, opts->tau_tol, 0.f, opts->h_start, opts->h_max, 0u}, n_groups,
+                                      RefineOut{poses_out, rows_out_or_null, rigid_out_or_null, xform_out_or_null, nullptr, nullptr,
+                                                status_out_or_null, evals_out_or_null},
+                                      best_pose_or_null, best_score_or_null);
+}
+
+extern "C" int mdx_refine_guests_flex(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_guest_flex* flex,
+                                      const mdx_flex_opts* opts, float* poses_out, float* rows_out_or_null, uint32_t n_groups,
+                                      float* rigid_out_or_null, float* xform_out_or_null, float* dih_out_or_null, float* tgrad_out_or_null,
+                                      uint32_t* status_out_or_null, uint32_t* evals_out_or_null, uint32_t* best_pose_or_null,
+                                      double* best_score_or_null) {
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_ligands == 0) return MDX_OK;
+    if (!ligs || !flex || !opts) FAIL(MDX_EPARAM, "null argument");
+    return guest_refine<mdx_fx_state>(h, "mdx_refine_guests_flex", n_ligands, ligs, flex, *opts, n_groups,
+                                      RefineOut{poses_out, rows_out_or_null, rigid_out_or_null, xform_out_or_null, dih_out_or_null,
+                                                tgrad_out_or_null, status_out_or_null, evals_out_or_null},
+                                      best_pose_or_null, best_score_or_null);
 }

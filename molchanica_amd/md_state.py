@@ -17,9 +17,9 @@ import os
 
 import numpy as np
 
-from ._abi import (CCommDiag, CFlexOpts, CGuestLigand, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
+from ._abi import (CCommDiag, CFlexOpts, CGuestFlex, CGuestLigand, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
                    CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, FUSED_TRIAD_INFO_ARGTYPES, POSE_RMSD_ARGTYPES,
-                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, GUEST_FORCES_ARGTYPES, REFINE_GUESTS_ARGTYPES, SCREEN_LIGANDS_ARGTYPES, VEL, GuestLigand,
+                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, GUEST_FORCES_ARGTYPES, REFINE_GUESTS_ARGTYPES, REFINE_GUESTS_FLEX_ARGTYPES, SCREEN_LIGANDS_ARGTYPES, VEL, GuestFlex, GuestLigand,
                    MdConfig, MdSystem, CSolubility, SET_SOLUTE_COPIES_ARGTYPES, SNAPSHOT_READ_SOLUBILITY_ARGTYPES, SOLUBILITY_MIXING_ARGTYPES,
                    SOLUTE_MAX_COPIES)
 
@@ -186,6 +186,7 @@ def load_library():
     lib.mdx_screen_ligands.argtypes = SCREEN_LIGANDS_ARGTYPES
     lib.mdx_guest_forces.argtypes = GUEST_FORCES_ARGTYPES
     lib.mdx_refine_guests.argtypes = REFINE_GUESTS_ARGTYPES
+    lib.mdx_refine_guests_flex.argtypes = REFINE_GUESTS_FLEX_ARGTYPES
     lib.mdx_set_solute_copies.argtypes = SET_SOLUTE_COPIES_ARGTYPES
     lib.mdx_solubility_mixing.argtypes = SOLUBILITY_MIXING_ARGTYPES
     lib.mdx_snapshot_read_solubility.argtypes = SNAPSHOT_READ_SOLUBILITY_ARGTYPES
@@ -421,6 +422,96 @@ class MdState:
                                      x.ctypes.data_as(_fp), st.ctypes.data_as(_u32p), ev.ctypes.data_as(_u32p),
                                      bp.ctypes.data_as(_u32p) if best else None, bs.ctypes.data_as(C.POINTER(C.c_double)) if best else None))
         out = (self._per_ligand(y, counts, sizes),) + tuple(self._per_ligand(v, counts) for v in (r, t, x, st, ev))
+        return out + ((bp[:M], bs[:M]),) if best else out
+
+    @staticmethod
+    def _guest_flex_records(who, flex, sizes):
+        """The `mdx_guest_flex` records parallel to a library's -> (records, torsions per ligand, the arrays they point into)."""
+        flex = list(flex)
+        if len(flex) != len(sizes):
+            raise ParamError(f"{who}: flex must hold one GuestFlex per ligand")
+        recs = (CGuestFlex * max(len(flex), 1))()
+        keep, T = [], []
+
+        def arr(a, dtype, shape, what, m):
+            try:
+                a = np.asarray(a)
+                if a.size and a.dtype.kind not in "iuf" or (np.dtype(dtype).kind in "iu" and a.dtype.kind == "f"):
+                    raise TypeError
+                if np.dtype(dtype).kind == "u" and a.size and (a < 0).any():
+                    raise ValueError
+                a = np.ascontiguousarray(a, dtype=dtype).reshape(shape)
+            except (TypeError, ValueError):
+                raise ParamError(f"{who}: ligand {m}: {what} has the wrong shape or type") from None
+            keep.append(a)
+            return a
+
+        i32p = C.POINTER(C.c_int32)
+        for m, f in enumerate(flex):
+            if not isinstance(f, GuestFlex):
+                raise ParamError(f"{who}: flex must hold GuestFlex objects")
+            b = arr(f.bonds, np.uint32, (-1, 2), "bonds", m)
+            tb = arr(f.torsion_bonds, np.uint32, (-1, 2), "torsion_bonds", m)
+            di = arr(f.dihedral_idx, np.uint32, (-1, 4), "dihedral_idx", m)
+            D = di.shape[0]
+            dv, dp = (arr(v, np.float32, (D,), w, m) for v, w in ((f.dihedral_v, "dihedral_v"), (f.dihedral_phase, "dihedral_phase")))
+            dn = arr(f.dihedral_n, np.int32, (D,), "dihedral_n", m)
+            if tb.shape[0] > POSE_MAX_TORSIONS:
+                raise ParamError(f"{who}: ligand {m}: more than {POSE_MAX_TORSIONS} torsions")
+            if not 0 <= int(f.root) < sizes[m]:
+                raise ParamError(f"{who}: ligand {m}: root must be an atom of the ligand")
+            r = recs[m]
+            r.n_bonds, r.bonds = b.shape[0], b.ctypes.data_as(_u32p) if b.size else None
+            r.root, r.n_torsions, r.torsion_bonds = int(f.root), tb.shape[0], tb.ctypes.data_as(_u32p) if tb.size else None
+            r.n_dihedrals, r.dihedral_idx = D, di.ctypes.data_as(_u32p) if D else None
+            r.dihedral_v, r.dihedral_phase = (dv.ctypes.data_as(_fp) if D else None), (dp.ctypes.data_as(_fp) if D else None)
+            r.dihedral_n = dn.ctypes.data_as(i32p) if D else None
+            T.append(tb.shape[0])
+        return recs, T, keep
+
+    def refine_guests_flex(self, ligands, flex, max_evals: int, f_tol: float, tau_tol: float, tors_tol: float, h_start: float = 0.0,
+                           h_max: float = 0.0, dihedrals: bool = True, best=False):
+        """`mdx_refine_guests_flex`: refine_poses_flex() for a library of guest ligands - refine_guests() with every ligand's torsion
+        angles as further coordinates.  flex: one `GuestFlex` per ligand (bond graph, root, torsion bonds, dihedral terms); dihedrals:
+        the listed terms are part of the objective and the gradient.
+        -> (poses_out, rows - the bits of screen_ligands(poses_out) -, rigid, xform, dih, tgrad, status, evals), each a list with one
+        array per ligand: [P_m, count, 3], [P_m, n_groups + 1], [P_m, 6], [P_m, 7 + T_m] (quaternion, translation, torsion angles),
+        [P_m] (the dihedral energy), [P_m, T_m] (-dS/dtheta) f32, [P_m], [P_m] u32, all of the accepted state.  best=True: also
+        (best_pose uint32 [M], best_score float64 [M]) - per ligand the accepted pose with the smallest row sum + dihedral energy
+        (lowest index on a tie; a REFINE_NONFINITE pose never wins), picked on the device.  The handle is left as it is."""
+        who = "refine_guests_flex"
+        M, recs, counts, (sizes, _keep) = self._guest_records(who, ligands)
+        frecs, T, _fkeep = self._guest_flex_records(who, flex, sizes)
+        lib = load_library()
+        G = int(lib.mdx_energy_group_count(self._h))
+        P = max(sum(counts), 1)
+        opts = CFlexOpts(int(max_evals), float(f_tol), float(tau_tol), float(tors_tol), float(h_start), float(h_max),
+                         FLEX_DIHEDRALS if dihedrals else 0)
+        y = np.zeros(max(sum(3 * n * p for n, p in zip(sizes, counts)), 1), dtype=np.float32)
+        r = np.zeros((P, G + 1), dtype=np.float32)
+        t = np.zeros((P, 6), dtype=np.float32)
+        x = np.zeros(max(sum((7 + k) * p for k, p in zip(T, counts)), 1), dtype=np.float32)
+        e = np.zeros(P, dtype=np.float32)
+        g = np.zeros(max(sum(k * p for k, p in zip(T, counts)), 1), dtype=np.float32)
+        st = np.zeros(P, dtype=np.uint32)
+        ev = np.zeros(P, dtype=np.uint32)
+        bp = np.full(max(M, 1), 0xFFFFFFFF, np.uint32)
+        bs = np.full(max(M, 1), np.inf, np.float64)
+        _check(lib.mdx_refine_guests_flex(self._h, M, recs, frecs, C.byref(opts), y.ctypes.data_as(_fp), r.ctypes.data_as(_fp), G,
+                                          t.ctypes.data_as(_fp), x.ctypes.data_as(_fp), e.ctypes.data_as(_fp), g.ctypes.data_as(_fp),
+                                          st.ctypes.data_as(_u32p), ev.ctypes.data_as(_u32p), bp.ctypes.data_as(_u32p) if best else None,
+                                          bs.ctypes.data_as(C.POINTER(C.c_double)) if best else None))
+
+        def ragged(flat, width):
+            out, at = [], 0
+            for m, p in enumerate(counts):
+                out.append(flat[at:at + p * width[m]].reshape(p, width[m]).copy())
+                at += p * width[m]
+            return out
+
+        rows, rigid = self._per_ligand(r, counts), self._per_ligand(t, counts)
+        out = (self._per_ligand(y, counts, sizes), rows, rigid, ragged(x, [7 + k for k in T]), self._per_ligand(e, counts), ragged(g, T),
+               self._per_ligand(st, counts), self._per_ligand(ev, counts))
         return out + ((bp[:M], bs[:M]),) if best else out
 
     def pose_forces(self, first: int, poses, rows=True, rigid=False):

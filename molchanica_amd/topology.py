@@ -97,6 +97,49 @@ def pairs_from_csr(offsets: np.ndarray, idx: np.ndarray, lo: int, hi: int) -> np
     return np.unique(pairs, axis=0).reshape(-1, 2)
 
 
+def _side_of(count: int, adj: list[list[int]], start: int, skip) -> np.ndarray:
+    """The atoms reachable from `start` without crossing the bond `skip` -> bool [count]."""
+    seen = np.zeros(count, bool)
+    seen[start] = True
+    stack = [start]
+    while stack:
+        i = stack.pop()
+        for j in adj[i]:
+            if seen[j] or (skip is not None and {i, j} == skip):
+                continue
+            seen[j] = True
+            stack.append(j)
+    return seen
+
+
+def rotatable_bonds(count: int, bonds, root: int = 0) -> np.ndarray:
+    """The bonds of a ligand that `MdState.refine_poses_flex` / `refine_guests_flex` accept as a torsion, in bond order: removing the bond
+    splits the ligand in two parts of at least two atoms each (no ring bond, no leaf bond), in a bond graph that is connected.
+    bonds: integer [B, 2], ligand-local.  -> uint32 [T, 2], each pair as it is listed.  A listed pair with an index outside
+    0 .. count-1 and a pair of an atom with itself are left out; with root outside the ligand there is none."""
+    count, root = int(count), int(root)
+    b = np.asarray(bonds, np.int64).reshape(-1, 2)
+    if not 0 <= root < count:
+        return np.zeros((0, 2), np.uint32)
+    ok = ((b >= 0) & (b < count)).all(1)
+    adj: list[list[int]] = [[] for _ in range(count)]
+    for p, q in b[ok]:
+        adj[int(p)].append(int(q))
+        adj[int(q)].append(int(p))
+    out = []
+    if b.shape[0] and _side_of(count, adj, root, None).all():
+        for k, (p, q) in enumerate(b):
+            p, q = int(p), int(q)
+            if not ok[k] or p == q:
+                continue
+            fixed = _side_of(count, adj, root, {p, q})
+            n_fixed = int(fixed.sum())
+            if (fixed[p] and fixed[q]) or n_fixed == 1 or count - n_fixed == 1:
+                continue
+            out.append((p, q))
+    return np.array(out, np.uint32).reshape(-1, 2)
+
+
 def ligand_automorphisms(n: int, bonds, keys, mask=None, cap: int = CLUSTER_MAX_PERMS) -> np.ndarray:
     """The symmetry images `MdState.pose_rmsd` / `cluster_poses` take: the automorphisms of the bond graph on n atoms that preserve the
     per-atom `keys` (e.g. the LJ type index), the identity first, de-duplicated by their action on the atoms of `mask` ([n] booleans,
