@@ -704,7 +704,7 @@ int      mdx_refine_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_
  * place in it.  n_ligands == 0, or a library without a single pose, succeeds and does nothing.  Decomposed handles and active
  * alchemical windows are refused.  Per chunk of 256 poses of the library the refinement enqueues max_evals x (force pass, step kernel)
  * and waits once.  Torsional refinement of guests is mdx_refine_guests_flex, below mdx_search_poses.  Not built for guests: the pose
- * search (mdx_search_poses for a library). */
+ * search inside these two calls - they descend from the poses they are given; exploring from them is mdx_search_guests, further below. */
 int      mdx_guest_forces(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs,
                           float* rows_or_null /* [sum n_poses][n_groups + 1] */, uint32_t n_groups,
                           float* forces /* per ligand [n_poses][count][3] */, float* rigid_or_null /* [sum n_poses][6] */);
@@ -840,7 +840,8 @@ int      mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_
  * n_torsions > 0); a dihedral index >= count; v or phase not finite; 2^20 dihedral terms or more; a list pointer NULL with a non-zero
  * count; tors_tol negative or not finite; unknown flag bits.
  * Not part of it: bond and angle terms of the guest, ring flexibility, guests above 256 atoms or 32 torsions, decomposed handles,
- * alchemical windows - and the pose search: mdx_search_poses has no counterpart for guests yet. */
+ * alchemical windows - and the pose search: when this call was added mdx_search_poses had no counterpart for guests yet; it is
+ * mdx_search_guests, below. */
 typedef struct mdx_guest_flex {
     uint32_t n_bonds;     const uint32_t* bonds;          /* [n_bonds][2] ligand-local: the ligand's bond graph (bonds and constraints) */
     uint32_t root, n_torsions; const uint32_t* torsion_bonds; /* [n_torsions][2] ligand-local, n_torsions <= MDX_POSE_MAX_TORSIONS */
@@ -855,6 +856,47 @@ int      mdx_refine_guests_flex(mdx_handle* h, uint32_t n_ligands, const mdx_gue
                                 float* tgrad_out_or_null /* per ligand [n_poses][n_torsions] */, uint32_t* status_out_or_null /* [sum n_poses] */,
                                 uint32_t* evals_out_or_null /* [sum n_poses] */, uint32_t* best_pose_or_null /* [n_ligands] */,
                                 double* best_score_or_null /* [n_ligands] */);
+
+/* ---- guest ligands, pose search: mdx_search_poses for a library of mdx_guest_ligand ------------------------------------------------------
+ * What a host loop of one mdx_refine_guests_flex call per round with the move and the decision of mdx_search_poses would produce,
+ * without its round trips.  The library and its flexible records are those of mdx_refine_guests_flex.
+ *   walkers    every pose of every ligand is a walker: ligand m's `poses` are its start poses.  Per-walker outputs follow the library's
+ *              pose order; coordinate-shaped outputs are ligand-major, as in mdx_refine_guests_flex.
+ *   the rule   that of mdx_search_poses, word for word: the stream of (seed, stream id, round), the 51 draws at their fixed places, round
+ *              0 without a move, the move, the new start, the decision and the best record.  The refinement of a round is exactly what
+ *              mdx_refine_guests_flex does to the new start with opts->refine; S = the sum over the n_groups + 1 columns in column order
+ *              of (double) row[b], plus (double) E_dih.  Every ligand moves with its own torsion table and is scored with its own
+ *              dihedral terms; n_choices counts the ligand's own torsions.
+ *   stream id  streams[p], p in the library's pose order; with streams == NULL the walker's LIGAND-LOCAL pose index.
+ * Independence.  A (ligand, walker) with a given stream id gives the same bits alone, in a library of any size and order, at any place
+ * in it - which is why the default id is ligand-local.  A search of R rounds and one of R' > R rounds agree on every round < R.  With
+ * n_rounds == 1, best_out, best_rows_out and best_dih_out are poses_out, rows_out and dih_out of mdx_refine_guests_flex bit for bit, and
+ * best_walker / best_ligand_score its best_pose / best_score.
+ * Outputs, of every walker's best round, as in mdx_search_poses: best_out its Y, best_rows_out its row, best_score_out S_best (fp64;
+ * +inf if no round was finite), best_dih_out, best_round_out, stats_out = (rounds >= 1 accepted, of those uphill, non-finite rounds,
+ * evaluations of all rounds).  A walker without a finite round keeps what round 0 left, as there: best_out is its start pose, with
+ * whatever row and E_dih were computed.
+ * best_walker_or_null[m] / best_ligand_score_or_null[m]: picked on the device over the ligand's walkers in
+ * order - a strictly smaller S_best wins, the lowest ligand-local index wins a tie, a walker whose S_best is +inf never wins; 0xFFFFFFFF
+ * and +infinity for a ligand with no walker or none finite.  best_ligand_score[m] is bit for bit best_score_out of the winning walker.
+ * The handle is not changed (positions, lists, caches, snapshots, the tables of the resident pose calls) and continues bit for bit like
+ * one that made no such call.  n_ligands == 0, or a library without a single pose, succeeds and writes nothing.
+ * Cost.  Per chunk of 256 walkers of the library: one upload (the chunk's tables and poses; its stream ids, 8 bytes per walker, follow
+ * it), n_rounds x (1 + 2 max_evals) + 1 launches plus the pick, one read-back and one wait.
+ * MDX_EPARAM (mdx_last_error names the call and, where there is one, the ligand; nothing is written): everything mdx_refine_guests_flex
+ * refuses, with opts->refine as its options; opts or flex NULL; best_out NULL in a library that has a walker; n_rounds == 0 or
+ * > MDX_SEARCH_MAX_ROUNDS; n_rounds x max_evals > 65536; trans_amp, rot_amp, tors_amp or kT negative or not finite; tors_amp > pi; no move enabled for a ligand that has poses (every
+ * amplitude 0, or only tors_amp > 0 and the ligand has no torsion).
+ * Not part of it: receptor or ring flexibility, exchange between walkers, continuing a search across calls, clustering inside the call
+ * (mdx_cluster_poses takes one ligand's block of best_out as it is), decomposed handles, alchemical windows, guests above 256 atoms or
+ * 32 torsions. */
+int      mdx_search_guests(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_guest_flex* flex /* [n_ligands] */,
+                           const uint64_t* streams_or_null /* [sum n_poses] */, const mdx_search_opts* opts,
+                           float* best_out /* per ligand [n_poses][count][3] */,
+                           float* best_rows_out_or_null /* [sum n_poses][n_groups + 1] */, uint32_t n_groups,
+                           double* best_score_out_or_null /* [sum n_poses] */, float* best_dih_out_or_null /* [sum n_poses] */,
+                           uint32_t* best_round_out_or_null /* [sum n_poses] */, uint32_t* stats_out_or_null /* [sum n_poses][4] */,
+                           uint32_t* best_walker_or_null /* [n_ligands] */, double* best_ligand_score_or_null /* [n_ligands] */);
 
 /* ---- pose distances and clustering: symmetry-aware RMSD in the receptor's frame, greedy leader clustering by it --------------------------
  * What follows a search: rank the poses by score, keep a pose only if it is further than an RMSD cutoff from every pose already kept,

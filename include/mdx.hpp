@@ -313,6 +313,31 @@ public:
                                r.best_round.data(), r.stats.data()));
         return r;
     }
+    /// mdx_search_guests: search_poses for a library of guest ligands, flex[m] beside ligs[m]: every pose of every ligand is a walker.
+    /// streams: empty (a walker draws from the stream of its ligand-local pose index) or one id per walker in the library's pose order.
+    struct SearchedGuests {
+        std::vector<float> poses, rows, dih;               ///< per ligand [n_poses][count][3], [sum n_poses][n_groups + 1], [sum n_poses] - of the best round
+        std::vector<double> score;                         ///< [sum n_poses] S = the row's sum + the dihedral energy
+        std::vector<uint32_t> best_round, stats;           ///< [sum n_poses], [sum n_poses][4]
+        std::vector<uint32_t> best_walker;                 ///< [n_ligands], 0xFFFFFFFF: no walker, or none finite
+        std::vector<double> best_ligand_score;             ///< [n_ligands]: score of that walker
+    };
+    SearchedGuests search_guests(const std::vector<mdx_guest_ligand>& ligs, const std::vector<mdx_guest_flex>& flex,
+                                 const std::vector<uint64_t>& streams, const mdx_search_opts& opts) {
+        if (flex.size() != ligs.size()) throw std::invalid_argument("search_guests: one mdx_guest_flex per ligand");
+        const uint32_t g = mdx_energy_group_count(h_);
+        size_t n = 0, nx = 0;
+        for (const mdx_guest_ligand& l : ligs) { n += l.n_poses; nx += 3 * (size_t)l.count * l.n_poses; }
+        if (!streams.empty() && streams.size() != n) throw std::invalid_argument("search_guests: streams must be empty or hold one id per walker");
+        SearchedGuests r;
+        r.poses.assign(nx, 0.f); r.rows.assign(n * ((size_t)g + 1), 0.f); r.dih.assign(n, 0.f); r.score.assign(n, 0.0);
+        r.best_round.assign(n, 0u); r.stats.assign(n * 4, 0u);
+        r.best_walker.assign(ligs.size(), 0xFFFFFFFFu); r.best_ligand_score.assign(ligs.size(), std::numeric_limits<double>::infinity());
+        check(mdx_search_guests(h_, (uint32_t)ligs.size(), ligs.data(), flex.data(), streams.empty() ? nullptr : streams.data(), &opts,
+                                r.poses.data(), r.rows.data(), g, r.score.data(), r.dih.data(), r.best_round.data(), r.stats.data(),
+                                r.best_walker.data(), r.best_ligand_score.data()));
+        return r;
+    }
 
     /// mdx_pose_rmsd: the symmetry-aware RMSD, in the receptor's frame, of every pose of a against every pose of b (b empty: of a) - the
     /// minimum over the symmetry images `perms` ([n_perms][count], the identity first; empty: the identity only) of the root mean square

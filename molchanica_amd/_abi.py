@@ -143,6 +143,10 @@ class CGuestFlex(C.Structure):
 #                        dih_out_or_null, tgrad_out_or_null, status_out_or_null, evals_out_or_null, best_pose_or_null, best_score_or_null)
 REFINE_GUESTS_FLEX_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), C.POINTER(CGuestFlex), C.POINTER(CFlexOpts), _fp, _fp, C.c_uint32,
                                _fp, _fp, _fp, _fp, _u32p, _u32p, _u32p, C.POINTER(C.c_double)]
+# mdx_search_guests(h, n_ligands, ligs, flex, streams_or_null, opts, best_out, best_rows_out_or_null, n_groups, best_score_out_or_null,
+#                   best_dih_out_or_null, best_round_out_or_null, stats_out_or_null, best_walker_or_null, best_ligand_score_or_null)
+SEARCH_GUESTS_ARGTYPES = [C.c_void_p, C.c_uint32, C.POINTER(CGuestLigand), C.POINTER(CGuestFlex), C.POINTER(C.c_uint64), C.POINTER(CSearchOpts),
+                          _fp, _fp, C.c_uint32, C.POINTER(C.c_double), _fp, _u32p, _u32p, _u32p, C.POINTER(C.c_double)]
 
 
 class CEnergies(C.Structure):

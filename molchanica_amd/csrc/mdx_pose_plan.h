@@ -2,6 +2,7 @@
 // lies.  Plain C++ (no device code, no runtime call): mdx_poses.hip lays its chunks out with it, and a stand-alone program can call it
 // (tests/cpp/guest_plan_driver.cpp).
 //   StepLayout   the refinement's block of a chunk (mdx_refine_poses, mdx_refine_poses_flex, mdx_search_poses, mdx_refine_guests)
+//   SearchLayout the search's block of a chunk behind it (mdx_search_poses, mdx_search_guests): one struct, two forms
 //   GuestLayout  the block of one chunk of guest poses: what the host stages, then what the kernels write
 //   guest_plan   the chunks of a library (POSE_CHUNK consecutive poses each) and, per chunk, the ligands it holds poses of
 //   guest_slots  where every such ligand's tables and poses lie in the chunk; guest_records makes the per-pose records from them
@@ -55,8 +56,35 @@ struct StepLayout {
     }
 };
 
-// mdx_screen_ligands, mdx_guest_forces, mdx_refine_guests, mdx_refine_guests_flex
-enum GuestMode { GUEST_ROWS = 0, GUEST_FORCES = 1, GUEST_REFINE = 2, GUEST_FLEX = 3 };
+// The search block of a chunk of n walkers with nxyz coordinates in all and rows W wide: [records | best coordinates | best rows | best
+// rigid | current coordinates | stream ids], every part on 16 bytes; records .. best rigid come back in one copy at the chunk's end.
+// A walker's stretch of the best and the current coordinates is its stretch of the refinement's coordinate-shaped buffers (resident:
+// walker x count x 3; guests: PoseRec.xyz).  The resident form takes the ligand's per_pose = 3 count floats.
+#define SEARCH_REC_BYTES 40u    // sizeof(mdx_sr_record) (mdx_search_step.h; mdx_pose_search_dev.h asserts it)
+struct SearchLayout {
+    size_t rec, best_y, best_row, best_rigid, cur_y, streams, end;
+    SearchLayout(uint32_t n, size_t per_pose, uint32_t G) { lay(n, per_pose * n, G); }
+    static SearchLayout guest(uint32_t n, size_t nxyz, uint32_t W) {
+        SearchLayout l;
+        l.lay(n, nxyz, W);
+        return l;
+    }
+private:
+    SearchLayout() {}
+    void lay(uint32_t n, size_t nxyz, uint32_t W) {
+        auto al = [](size_t x) { return (x + 15u) / 16u * 16u; };
+        rec = 0;
+        best_y = al(SEARCH_REC_BYTES * (size_t)n);
+        best_row = al(best_y + sizeof(float) * nxyz);
+        best_rigid = al(best_row + sizeof(float) * (size_t)W * n);
+        cur_y = al(best_rigid + sizeof(float) * 6u * n);
+        streams = al(cur_y + sizeof(float) * nxyz);
+        end = streams + sizeof(uint64_t) * n;
+    }
+};
+
+// mdx_screen_ligands, mdx_guest_forces, mdx_refine_guests, mdx_refine_guests_flex, mdx_search_guests
+enum GuestMode { GUEST_ROWS = 0, GUEST_FORCES = 1, GUEST_REFINE = 2, GUEST_FLEX = 3, GUEST_SEARCH = 4 };
 
 // the flexible tables of a chunk, in elements: torsions, dihedral terms (every ligand's rounded up to an even number: its table starts
 // on 16 bytes), words of aoff (every ligand's count + 1 rounded up to 4) and the terms of all poses (eterm)
@@ -68,9 +96,9 @@ inline size_t guest_aoff_room(uint32_t count) { return ((size_t)count + 1u + 3u)
 // of the chunk's ligands, their 1-4 records, the coordinates, the class maps), then the units' slab and the summed rows; with forces
 // the units' force slab, the summed forces and rigid; for a refinement the force slab and a StepLayout at `step` (state_bytes > 0).
 // GUEST_FLEX stages, behind the class maps, the FlexRec records and the ligands' flexible tables (fx), each on 16 bytes, and its
-// StepLayout ends with the terms of all poses.
+// StepLayout ends with the terms of all poses.  GUEST_SEARCH is GUEST_FLEX with a SearchLayout at `search` behind the step block.
 struct GuestLayout {
-    size_t rec, ligof, q, lj, p14, xyz, cls, frec, tor, dih, aoff, aent, up_end, slab, rows, fslab, fout, rigid, step, end;
+    size_t rec, ligof, q, lj, p14, xyz, cls, frec, tor, dih, aoff, aent, up_end, slab, rows, fslab, fout, rigid, step, end, search;
     GuestLayout(size_t n, size_t atoms, size_t n14, size_t nxyz, size_t ncls, uint32_t W, int mode = GUEST_ROWS, size_t state_bytes = 0,
                 const GuestFlexSums& fx = GuestFlexSums()) {
         auto al = [](size_t x) { return (x + 15u) / 16u * 16u; };
@@ -83,7 +111,7 @@ struct GuestLayout {
         cls = al(xyz + sizeof(float) * nxyz);
         up_end = cls + ncls;
         frec = tor = dih = aoff = aent = up_end;
-        if (mode == GUEST_FLEX) {
+        if (mode == GUEST_FLEX || mode == GUEST_SEARCH) {
             frec = al(up_end);
             tor = al(frec + sizeof(FlexRec) * n);
             dih = al(tor + GUEST_TOR_BYTES * fx.tor);
@@ -94,7 +122,7 @@ struct GuestLayout {
         slab = al(up_end);
         rows = slab + sizeof(double) * n * (POSE_UNITS + 1u) * W;
         end = rows + sizeof(double) * n * W;
-        fslab = fout = rigid = step = end;
+        fslab = fout = rigid = step = search = end;
         if (mode == GUEST_ROWS) return;
         fslab = end;
         fout = fslab + sizeof(double) * (POSE_UNITS + 1u) * nxyz;
@@ -102,7 +130,12 @@ struct GuestLayout {
         step = al(rigid + sizeof(float) * 6u * n);
         end = step;
         if (mode == GUEST_REFINE) end = step + StepLayout((uint32_t)n, nxyz, W, state_bytes, 0u).end;
-        if (mode == GUEST_FLEX) end = step + StepLayout::guest((uint32_t)n, nxyz, W, state_bytes, fx.terms).end;
+        if (mode == GUEST_FLEX || mode == GUEST_SEARCH) end = step + StepLayout::guest((uint32_t)n, nxyz, W, state_bytes, fx.terms).end;
+        search = end;
+        if (mode == GUEST_SEARCH) {
+            search = al(end);
+            end = search + SearchLayout::guest((uint32_t)n, nxyz, W).end;
+        }
     }
 };
 

@@ -76,6 +76,12 @@
 // the chunk's poses have terms.  guest_best_flex_kernel is guest_best over the flexible records: S with the accepted E_dih.  The body of
 // the step kernels stands in mdx_pose_step_dev.h and the new kernel in mdx_guest_flex.hip, for the reason given there.
 //
+// mdx_search_guests: the search for guests - the loop of mdx_refine_guests_flex run n_rounds times per chunk with guest_search_kernel
+// between two of them: pose_search<true>, the body of pose_search_kernel (mdx_pose_search_dev.h) with the walker's size and stretch of
+// the coordinates from its PoseRec and its torsion table from its FlexRec; the kernel stands in mdx_guest_search.hip.  The chunk's
+// search block (SearchLayout, the same struct for both tracks) lies behind its step block in gs_blk (GUEST_SEARCH), the stream ids go
+// up with the chunk, and guest_best_search_kernel is guest_best over the walkers' search records: S_best as it is.
+//
 // What is written once: the unit-order sum of a slab (pose_units_sum: the four kernels that add the 17 units take it from there, which
 // is why rows_out / rigid_out of a refinement are the bits mdx_score_poses / mdx_pose_forces return), the stages of an evaluation
 // (step_gather, step_store, step_max_speed; centroid, rigid and inertia stand once in pose_step), the B(theta) loop
@@ -90,6 +96,7 @@
 #include "mdx_search_step.h"
 #include "mdx_pose_plan.h"
 #include "mdx_pose_step_dev.h"
+#include "mdx_pose_search_dev.h"
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -934,100 +941,43 @@ extern "C" int mdx_refine_poses_flex(mdx_handle* h, uint32_t first, uint32_t cou
 }
 
 // ---- mdx_search_poses: an iterated local search per walker around the loop above (mdx_search_step.h) ------------------------------------
-// The search block of a chunk of n walkers: [records | best coordinates | best rows | best rigid | current coordinates | stream ids];
-// records .. best rigid come back in one copy at the chunk's end.
-struct SearchLayout {
-    size_t rec, best_y, best_row, best_rigid, cur_y, streams, end;
-    SearchLayout(uint32_t n, size_t per_pose, uint32_t G) {
-        rec = 0;
-        best_y = sizeof(mdx_sr_record) * n;
-        best_row = best_y + sizeof(float) * per_pose * n;
-        best_rigid = best_row + sizeof(float) * (size_t)G * n;
-        cur_y = best_rigid + sizeof(float) * 6u * n;
-        streams = ((cur_y + sizeof(float) * per_pose * n + 15u) / 16u) * 16u;
-        end = streams + sizeof(uint64_t) * n;
-    }
-};
+// (SearchLayout - the search block of a chunk - stands in mdx_pose_plan.h; SearchArgs and the body of the search kernels, pose_search,
+// in mdx_pose_search_dev.h: one body, two plain kernels - this one and guest_search_kernel of mdx_guest_search.hip)
+__global__ __launch_bounds__(256) void pose_search_kernel(SearchArgs a, uint32_t r) { pose_search<false>(a, r); }
 
-struct SearchArgs {
-    uint32_t count, G, T, pad;
-    float* stage; uint32_t* frozen; mdx_fx_state* st;              // what the refinement starts from: staged pose, frozen word, state record
-    const float* y; const float* row; const float* rigid;          // what it ended with: its accepted coordinates, row and rigid
-    const mdx_fx_torsion* tor;
-    const uint64_t* streams; mdx_sr_record* rec;
-    float* cur_y; float* best_y; float* best_row; float* best_rigid;
-    mdx_sr_opts o;
-};
-
-// Launched with round index r between two refinements, one workgroup per walker: it decides round r - 1 (r >= 1) from what the
-// refinement left - thread 0 takes the decision, the threads copy the accepted coordinates (and, for a new best, row and rigid) into the
-// walker's search record - and, for r < n_rounds, starts round r: thread 0 draws the move and forms (dq, dt), B(dtheta) is built in LDS
-// from the current pose by pose_build_torsions, the loop pose_flex_step_kernel builds a trial with, every thread writes its atom of
-// X0' into the staging buffer, and the walker's state record and frozen word are zeroed ("evaluation 0: the trial is the input").
-// Round 0 has no move: the staged pose is the caller's.  Plain stores only.
-__global__ __launch_bounds__(256) void pose_search_kernel(SearchArgs a, uint32_t r) {
-    __shared__ double s_x[MDX_POSE_MAX_ATOMS][3], s_c[3], s_bc[3], s_R[9], s_t[3], s_th[MDX_FX_MAX_TORSIONS], s_cs[MDX_FX_MAX_TORSIONS],
-                      s_sn[MDX_FX_MAX_TORSIONS];
-    __shared__ uint32_t s_fl;
-    const uint32_t tid = threadIdx.x, walker = blockIdx.x, count = a.count, T = a.T;
-    const size_t at = ((size_t)walker * count + tid) * 3u;
-    uint32_t fl = 0u;
-    if (r >= 1u) {
-        if (tid == 0u) {
-            const mdx_fx_state* s = a.st + walker;
-            mdx_sr_record rec = a.rec[walker];
-            const bool finite = !(s->rf.frozen != 0u && s->rf.status == MDX_RF_NONFINITE);
-            s_fl = sr_decide(rec, a.o, r - 1u, s->rf.S, finite, s->edih, s->rf.evals, sr_stream(a.o.seed, a.streams[walker], r - 1u));
-            a.rec[walker] = rec;
-        }
-        __syncthreads();
-        fl = s_fl;
-        if (fl & MDX_SR_BEST) {
-            if (tid < count)
-                for (uint32_t c = 0; c < 3u; ++c) a.best_y[at + c] = a.y[at + c];
-            if (tid < a.G) a.best_row[(size_t)walker * a.G + tid] = a.row[(size_t)walker * a.G + tid];
-            if (tid < 6u) a.best_rigid[(size_t)walker * 6u + tid] = a.rigid[(size_t)walker * 6u + tid];
-        }
-    }
-    if (r >= a.o.n_rounds) {      // (uniform over the grid: the last launch only decides)
-        if ((fl & MDX_SR_ACCEPT) && tid < count)
-            for (uint32_t c = 0; c < 3u; ++c) a.cur_y[at + c] = a.y[at + c];
-        return;
-    }
-    if (r >= 1u) {
-        // the current pose: the round just accepted, or the record's
-        const float* src = (fl & MDX_SR_ACCEPT) ? a.y : a.cur_y;
-        if (tid < count)
-            for (uint32_t c = 0; c < 3u; ++c) {
-                const float v = src[at + c];
-                s_x[tid][c] = (double)v;
-                if (fl & MDX_SR_ACCEPT) a.cur_y[at + c] = v;
-            }
-        if (tid < MDX_FX_MAX_TORSIONS) s_th[tid] = 0.0;
-        __syncthreads();
-        if (tid < 3u) s_c[tid] = rf_mean(&s_x[0][0], count, tid);
-        if (tid == 64u) {      // (a wave beside the centroid's)
-            mdx_sr_move mv;
-            double q[4];
-            sr_move(a.o, T, sr_stream(a.o.seed, a.streams[walker], r), mv);
-            sr_xform(mv, q, s_t);
-            rf_rotation(q, s_R);
-            if (mv.kind == MDX_SR_TORSION) { s_th[mv.torsion] = mv.dtheta; s_cs[mv.torsion] = cos(mv.dtheta); s_sn[mv.torsion] = sin(mv.dtheta); }
-        }
-        __syncthreads();
-        pose_build_torsions(s_x, a.tor, s_th, s_cs, s_sn, T, count, tid);      // (the table where it lies: at most one torsion turns per round)
-        if (tid < 3u) s_bc[tid] = rf_mean(&s_x[0][0], count, tid);
-        __syncthreads();
-        if (tid < count) {
-            float y[3];
-            fx_coords(s_c, s_t, s_R, s_x[tid], s_bc, y);
-            for (uint32_t c = 0; c < 3u; ++c) a.stage[at + c] = y[c];
-        }
-    }
-    uint32_t* dst = (uint32_t*)(a.st + walker);
-    for (uint32_t i = tid; i < sizeof(mdx_fx_state) / 4u; i += 256u) dst[i] = 0u;
-    if (tid == 0u) a.frozen[walker] = 0u;
+// The search kernel's arguments for a chunk whose refinement runs with r and whose search block lies at sb, laid out by sl (W: the width
+// of a row; resident: count and T of the call, guests: 0 - the records say)
+static SearchArgs search_args(const StepArgs& r, unsigned char* sb, const SearchLayout& sl, uint32_t count, uint32_t W, uint32_t T, const mdx_sr_opts& so) {
+    SearchArgs s{};
+    s.count = count; s.G = W; s.T = T; s.stage = r.stage; s.frozen = r.frozen; s.st = (mdx_fx_state*)r.st; s.y = r.y; s.row = r.row; s.rigid = r.rigid;
+    s.tor = r.tor; s.streams = (const uint64_t*)(sb + sl.streams); s.rec = (mdx_sr_record*)(sb + sl.rec);
+    s.cur_y = (float*)(sb + sl.cur_y); s.best_y = (float*)(sb + sl.best_y); s.best_row = (float*)(sb + sl.best_row);
+    s.best_rigid = (float*)(sb + sl.best_rigid);
+    s.o = so;
+    return s;
 }
+
+// What a search returns per walker beside coordinates and rows, on the host until every chunk has run: take() reads the n records of a
+// chunk as they came back (walkers p0 ..), write() fills the caller's optional outputs
+struct SearchOut {
+    std::vector<double> score; std::vector<float> dih; std::vector<uint32_t> round, stats;
+    explicit SearchOut(size_t n) : score(n), dih(n), round(n), stats(4u * n) {}
+    void take(const unsigned char* recs, uint32_t n, size_t p0) {
+        for (uint32_t k = 0; k < n; ++k) {
+            mdx_sr_record rec;
+            std::memcpy(&rec, recs + sizeof(mdx_sr_record) * k, sizeof(rec));
+            score[p0 + k] = rec.S_best; dih[p0 + k] = rec.edih_best; round[p0 + k] = rec.best_round;
+            uint32_t* c = stats.data() + 4u * (p0 + k);
+            c[0] = rec.accepted; c[1] = rec.uphill; c[2] = rec.nonfinite; c[3] = rec.evals;
+        }
+    }
+    void write(double* score_out, float* dih_out, uint32_t* round_out, uint32_t* stats_out) const {
+        if (score_out) std::memcpy(score_out, score.data(), sizeof(double) * score.size());
+        if (dih_out) std::memcpy(dih_out, dih.data(), sizeof(float) * dih.size());
+        if (round_out) std::memcpy(round_out, round.data(), sizeof(uint32_t) * round.size());
+        if (stats_out) std::memcpy(stats_out, stats.data(), sizeof(uint32_t) * stats.size());
+    }
+};
 
 extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, uint32_t n_walkers, const float* starts,
                                 const uint64_t* streams_or_null, uint32_t root, uint32_t n_torsions, const uint32_t* torsion_bonds,
@@ -1056,9 +1006,8 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
     const size_t per_pose = 3 * (size_t)count;
     MDX_TRY(pose_grow(&d.ps_flex, h->ps_cap_flex, StepLayout(POSE_CHUNK, per_pose * POSE_CHUNK, G, sizeof(mdx_fx_state), n_terms).end));
     MDX_TRY(pose_grow(&d.ps_search, h->ps_cap_search, SearchLayout(POSE_CHUNK, per_pose, G).end));
-    std::vector<float> yres(per_pose * n_walkers), rres((size_t)n_walkers * G), dres(n_walkers);
-    std::vector<double> scres(n_walkers);
-    std::vector<uint32_t> brres(n_walkers), stres(4u * (size_t)n_walkers);
+    std::vector<float> yres(per_pose * n_walkers), rres((size_t)n_walkers * G);
+    SearchOut res(n_walkers);
     std::vector<uint64_t> ids(std::min(n_walkers, POSE_CHUNK));
     std::vector<unsigned char> back;
     for (uint32_t p0 = 0; p0 < n_walkers; p0 += POSE_CHUNK) {
@@ -1068,12 +1017,7 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
         unsigned char* sb = (unsigned char*)d.ps_search;
         const StepArgs r = step_args(h, a, (unsigned char*)d.ps_flex, count, G, true, T, n_terms, lay, o);
         a.frozen = r.frozen;
-        SearchArgs s{};
-        s.count = count; s.G = G; s.T = T; s.stage = d.ps_stage; s.frozen = r.frozen; s.st = (mdx_fx_state*)r.st; s.y = r.y; s.row = r.row; s.rigid = r.rigid;
-        s.tor = r.tor; s.streams = (const uint64_t*)(sb + sl.streams); s.rec = (mdx_sr_record*)(sb + sl.rec);
-        s.cur_y = (float*)(sb + sl.cur_y); s.best_y = (float*)(sb + sl.best_y); s.best_row = (float*)(sb + sl.best_row);
-        s.best_rigid = (float*)(sb + sl.best_rigid);
-        s.o = so;
+        const SearchArgs s = search_args(r, sb, sl, count, G, T, so);      // (r.stage is ps_stage: the force pass reads what the kernels stage)
         for (uint32_t k = 0; k < n; ++k) ids[k] = streams_or_null ? streams_or_null[p0 + k] : (uint64_t)(p0 + k);
         HIP_TRY(hipMemcpyAsync(d.ps_stage, starts + per_pose * p0, sizeof(float) * per_pose * n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(sb + sl.streams, ids.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice, st));
@@ -1091,20 +1035,11 @@ extern "C" int mdx_search_poses(mdx_handle* h, uint32_t first, uint32_t count, u
         const unsigned char* b0 = back.data();
         std::memcpy(yres.data() + per_pose * p0, b0 + sl.best_y, sizeof(float) * per_pose * n);
         std::memcpy(rres.data() + (size_t)p0 * G, b0 + sl.best_row, sizeof(float) * (size_t)G * n);
-        for (uint32_t k = 0; k < n; ++k) {
-            mdx_sr_record rec;
-            std::memcpy(&rec, b0 + sl.rec + sizeof(mdx_sr_record) * k, sizeof(rec));
-            scres[p0 + k] = rec.S_best; dres[p0 + k] = rec.edih_best; brres[p0 + k] = rec.best_round;
-            uint32_t* c = stres.data() + 4u * (size_t)(p0 + k);
-            c[0] = rec.accepted; c[1] = rec.uphill; c[2] = rec.nonfinite; c[3] = rec.evals;
-        }
+        res.take(b0 + sl.rec, n, p0);
     }
     std::memcpy(best_out, yres.data(), sizeof(float) * yres.size());
     if (best_rows_out_or_null) std::memcpy(best_rows_out_or_null, rres.data(), sizeof(float) * rres.size());
-    if (best_score_out_or_null) std::memcpy(best_score_out_or_null, scres.data(), sizeof(double) * scres.size());
-    if (best_dih_out_or_null) std::memcpy(best_dih_out_or_null, dres.data(), sizeof(float) * dres.size());
-    if (best_round_out_or_null) std::memcpy(best_round_out_or_null, brres.data(), sizeof(uint32_t) * brres.size());
-    if (stats_out_or_null) std::memcpy(stats_out_or_null, stres.data(), sizeof(uint32_t) * stres.size());
+    res.write(best_score_out_or_null, best_dih_out_or_null, best_round_out_or_null, stats_out_or_null);
     return MDX_OK;
 }
 
@@ -1122,7 +1057,8 @@ struct GuestBest { double score; uint32_t pose, pad; };      // smallest row sum
 // what a host gets from the returned rows - and a strictly smaller S replaces the carried one: the lowest index wins a tie, also
 // across chunks.  One writer per ligand, no atomics.  Row: double (the summed rows of mdx_screen_ligands) or float (the accepted rows
 // of a refinement; st: its state records - a pose that ended MDX_REFINE_NONFINITE is passed over whatever its row holds; the flexible
-// refinement's records add their accepted E_dih behind the columns).
+// refinement's records add their accepted E_dih behind the columns); or none at all and st the walkers' search records
+// (mdx_search_guests): S is the record's S_best, read as it is.
 __device__ __forceinline__ const mdx_rf_state& rf_of(const mdx_rf_state& s) { return s; }
 __device__ __forceinline__ const mdx_rf_state& rf_of(const mdx_fx_state& s) { return s.rf; }
 template <class Row, class State>
@@ -1134,10 +1070,13 @@ __device__ __forceinline__ void guest_best(uint32_t n, uint32_t W, const Row* __
     if (p > 0u && lig_of[p - 1u].x == m) return;
     GuestBest b = best[m];
     for (uint32_t k = p; k < n && lig_of[k].x == m; ++k) {
-        if (st && rf_of(st[k]).frozen != 0u && rf_of(st[k]).status == MDX_RF_NONFINITE) continue;
         double S = 0.0;
-        for (uint32_t c = 0; c < W; ++c) S += (double)(float)rows[(size_t)k * W + c];
-        if constexpr (std::is_same<State, mdx_fx_state>::value) S += (double)st[k].edih;
+        if constexpr (std::is_same<State, mdx_sr_record>::value) S = st[k].S_best;      // (as it is; +inf - no finite round - never wins)
+        else {
+            if (st && rf_of(st[k]).frozen != 0u && rf_of(st[k]).status == MDX_RF_NONFINITE) continue;
+            for (uint32_t c = 0; c < W; ++c) S += (double)(float)rows[(size_t)k * W + c];
+            if constexpr (std::is_same<State, mdx_fx_state>::value) S += (double)st[k].edih;
+        }
         if (S < b.score) { b.score = S; b.pose = lig_of[k].y; }
     }
     best[m] = b;
@@ -1155,6 +1094,10 @@ __global__ __launch_bounds__(256) void guest_best_flex_kernel(uint32_t n, uint32
                                                               const uint2* __restrict__ lig_of, const mdx_fx_state* __restrict__ st,
                                                               GuestBest* __restrict__ best) {
     guest_best(n, W, rows, lig_of, st, best);
+}
+__global__ __launch_bounds__(256) void guest_best_search_kernel(uint32_t n, const uint2* __restrict__ lig_of, const mdx_sr_record* __restrict__ rec,
+                                                                GuestBest* __restrict__ best) {
+    guest_best(n, 0u, (const float*)nullptr, lig_of, rec, best);
 }
 
 // A guest's own pairs: the class map [count^2] (0 plain, 1 excluded, 2 scaled 1-4) of its two pair lists; null, or why the lists are refused
@@ -1217,6 +1160,7 @@ struct GuestRun {
     std::vector<GuestChunk> chunks;
     std::vector<GuestSlot> slots;
     std::vector<unsigned char> up;
+    std::vector<uint64_t> ids;            // mdx_search_guests: the stream ids of the chunk in flight
     std::vector<GuestBest> best;
     size_t total = 0;
     PoseArgs a{};
@@ -1262,7 +1206,8 @@ static int guest_check(mdx_handle* h, const std::string& who, uint32_t n_ligands
 }
 
 static GuestLayout guest_layout(const GuestChunk& c, uint32_t W, int gmode) {
-    return GuestLayout(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W, gmode, gmode == GUEST_FLEX ? sizeof(mdx_fx_state) : sizeof(mdx_rf_state), c.fx);
+    const bool flex = gmode == GUEST_FLEX || gmode == GUEST_SEARCH;
+    return GuestLayout(c.n, c.atoms, c.n14, c.nxyz, c.ncls, W, gmode, flex ? sizeof(mdx_fx_state) : sizeof(mdx_rf_state), c.fx);
 }
 
 // the device side of a call that has work: the list of the current state, the block (it follows the largest chunk), the carried best
@@ -1296,8 +1241,11 @@ static int guest_ready(mdx_handle* h, uint32_t n_ligands, int gmode, bool want_b
     return MDX_OK;
 }
 
-// a chunk goes up: records, tables and coordinates in one copy; the kernel's arguments point into its block
-static int guest_stage(mdx_handle* h, const mdx_guest_ligand* ligs, const GuestChunk& c, const GuestLayout& lay, GuestRun& run) {
+// a chunk goes up: records, tables and coordinates in one copy; the kernel's arguments point into its block.  search (mdx_search_guests:
+// the layout is GUEST_SEARCH's): the walkers' stream ids follow into the search block - the caller's, in library pose order, or the
+// walker's ligand-local pose index
+static int guest_stage(mdx_handle* h, const mdx_guest_ligand* ligs, const GuestChunk& c, const GuestLayout& lay, GuestRun& run,
+                       bool search = false, const uint64_t* streams_or_null = nullptr) {
     const mdx_config& cfg = h->cfg;
     const bool lj_off = (cfg.overrides & MDX_OVR_LJ_DISABLED) != 0, coul_off = (cfg.overrides & MDX_OVR_COULOMB_DISABLED) != 0;
     const bool geometric = cfg.combining_rule == MDX_COMBINE_GEOMETRIC;
@@ -1310,7 +1258,7 @@ static int guest_stage(mdx_handle* h, const mdx_guest_ligand* ligs, const GuestC
     float* xyz = (float*)(up.data() + lay.xyz);
     guest_slots(run.shapes, run.pstart, c, run.slots);
     guest_records(run.shapes, run.slots, (PoseRec*)(up.data() + lay.rec), (uint32_t*)(up.data() + lay.ligof));
-    const bool flex = !run.fx.empty();      // (the layout is GUEST_FLEX's then)
+    const bool flex = !run.fx.empty();      // (the layout is GUEST_FLEX's or GUEST_SEARCH's then)
     if (flex) guest_flex_records(run.shapes, run.slots, (FlexRec*)(up.data() + lay.frec));
     std::vector<uint8_t> cls;
     for (const GuestSlot& s : run.slots) {
@@ -1345,6 +1293,14 @@ static int guest_stage(mdx_handle* h, const mdx_guest_ligand* ligs, const GuestC
     }
     unsigned char* blk = (unsigned char*)h->d.gs_blk;
     HIP_TRY(hipMemcpyAsync(blk, up.data(), lay.up_end, hipMemcpyHostToDevice, h->stream));
+    if (search) {
+        run.ids.resize(c.n);      // (free again: the chunk before this one has been waited for)
+        for (const GuestSlot& s : run.slots)
+            for (size_t l = s.l0; l < s.l1; ++l)
+                run.ids[s.p + (l - s.l0)] = streams_or_null ? streams_or_null[run.pstart[s.m] + l] : (uint64_t)l;
+        const SearchLayout ssl = SearchLayout::guest(c.n, c.nxyz, h->n_grp + 1u);
+        HIP_TRY(hipMemcpyAsync(blk + lay.search + ssl.streams, run.ids.data(), sizeof(uint64_t) * c.n, hipMemcpyHostToDevice, h->stream));
+    }
     PoseArgs& a = run.a;
     a.count = c.max_count;
     a.rec = (const PoseRec*)(blk + lay.rec);
@@ -1433,6 +1389,23 @@ extern "C" int mdx_guest_forces(mdx_handle* h, uint32_t n_ligands, const mdx_gue
     return guest_run(h, "mdx_guest_forces", true, n_ligands, ligs, rows_or_null, n_groups, forces, rigid_or_null, nullptr, nullptr);
 }
 
+// the step kernel's arguments for a staged chunk of guests (guest_stage has set run.a) whose step block, laid out by sl, lies at
+// lay.step; flex: with the chunk's flexible records and tables.  The force pass's frozen words are the step block's.
+static StepArgs guest_step_args(mdx_handle* h, GuestRun& run, const GuestLayout& lay, const StepLayout& sl, uint32_t W, bool flex, const mdx_fx_opts& o) {
+    unsigned char* blk = (unsigned char*)h->d.gs_blk;
+    unsigned char* sb = blk + lay.step;
+    StepArgs r = step_args(h, run.a, sb, 0u, W, false, 0u, 0u, sl, o);
+    r.rec = run.a.rec;
+    if (flex) {
+        r.frec = (const FlexRec*)(blk + lay.frec);
+        r.eterm = (double*)(sb + sl.eterm);
+        r.tor = (const mdx_fx_torsion*)(blk + lay.tor); r.dih = (const mdx_fx_dihedral*)(blk + lay.dih);
+        r.aoff = (const uint32_t*)(blk + lay.aoff); r.aent = (const uint32_t*)(blk + lay.aent);
+    }
+    run.a.frozen = r.frozen;
+    return r;
+}
+
 // The loop of refine_chunks over the chunks of a library, State = mdx_rf_state (mdx_refine_guests: flex == null) or mdx_fx_state
 // (mdx_refine_guests_flex): per chunk one upload, the frozen words and records zeroed, max_evals x (the GUEST REFINE force pass, the guest
 // step kernel of the state), the best kernel on the accepted rows, one read-back, one wait.  The staged coordinates are the stage
@@ -1473,15 +1446,7 @@ static int guest_refine(mdx_handle* h, const std::string& who, uint32_t n_ligand
         MDX_TRY(guest_stage(h, ligs, c, lay, run));
         PoseArgs& a = run.a;
         unsigned char* sb = blk + lay.step;
-        StepArgs r = step_args(h, a, sb, 0u, W, false, 0u, 0u, sl, o);
-        r.rec = a.rec;
-        if constexpr (FLEX) {
-            r.frec = (const FlexRec*)(blk + lay.frec);
-            r.eterm = (double*)(sb + sl.eterm);
-            r.tor = (const mdx_fx_torsion*)(blk + lay.tor); r.dih = (const mdx_fx_dihedral*)(blk + lay.dih);
-            r.aoff = (const uint32_t*)(blk + lay.aoff); r.aent = (const uint32_t*)(blk + lay.aent);
-        }
-        a.frozen = r.frozen;
+        const StepArgs r = guest_step_args(h, run, lay, sl, W, FLEX, o);
         HIP_TRY(hipMemsetAsync(sb, 0, sl.y, st));
         mdx_prof_begin(h, 0);
         for (uint32_t k = 0; k < fo.max_evals; ++k) step_evaluate<FLEX>(h, a, run.mode, run.geom, c.n, r);
@@ -1552,4 +1517,91 @@ extern "C" int mdx_refine_guests_flex(mdx_handle* h, uint32_t n_ligands, const m
                                       RefineOut{poses_out, rows_out_or_null, rigid_out_or_null, xform_out_or_null, dih_out_or_null,
                                                 tgrad_out_or_null, status_out_or_null, evals_out_or_null},
                                       best_pose_or_null, best_score_or_null);
+}
+
+// ---- mdx_search_guests: the search of mdx_search_poses for a library - the loop of guest_refine<mdx_fx_state> run n_rounds times per
+// chunk with guest_search_kernel between two of them.  Per chunk: one staging (the stream ids with it), the step block's head and the
+// search records zeroed, n_rounds x (search kernel, max_evals x (the GUEST REFINE force pass, guest_flex_step_kernel)), the search kernel
+// once more to decide the last round, guest_best_search_kernel on the records, one read-back of records .. best rigid, one wait.
+extern "C" int mdx_search_guests(mdx_handle* h, uint32_t n_ligands, const mdx_guest_ligand* ligs, const mdx_guest_flex* flex,
+                                 const uint64_t* streams_or_null, const mdx_search_opts* opts, float* best_out, float* best_rows_out_or_null,
+                                 uint32_t n_groups, double* best_score_out_or_null, float* best_dih_out_or_null,
+                                 uint32_t* best_round_out_or_null, uint32_t* stats_out_or_null, uint32_t* best_walker_or_null,
+                                 double* best_ligand_score_or_null) {
+    const std::string who = "mdx_search_guests";
+    if (!h) FAIL(MDX_EPARAM, "null handle");
+    if (n_ligands == 0) return MDX_OK;
+    if (!ligs || !flex || !opts) FAIL(MDX_EPARAM, who + ": null argument");
+    if (opts->n_rounds == 0 || opts->n_rounds > MDX_SEARCH_MAX_ROUNDS) FAIL(MDX_EPARAM, who + ": n_rounds must be in 1..MDX_SEARCH_MAX_ROUNDS (1024)");
+    if ((uint64_t)opts->n_rounds * opts->refine.max_evals > 65536u) FAIL(MDX_EPARAM, who + ": n_rounds x max_evals exceeds 65536");
+    for (float v : {opts->trans_amp, opts->rot_amp, opts->tors_amp, opts->kT})
+        if (!std::isfinite(v) || v < 0.f) FAIL(MDX_EPARAM, who + ": an amplitude or kT is negative or not finite");
+    if (opts->tors_amp > 3.14159265358979323846f) FAIL(MDX_EPARAM, who + ": tors_amp exceeds pi");      // (the fp32 nearest to pi passes)
+    const mdx_sr_opts so{(double)opts->trans_amp, (double)opts->rot_amp, (double)opts->tors_amp, (double)opts->kT, opts->seed, opts->n_rounds, 0u};
+    if (sr_choices(so, MDX_POSE_MAX_TORSIONS) == 0u) FAIL(MDX_EPARAM, who + ": no move is enabled (every amplitude is 0)");
+    const mdx_flex_opts& fo = opts->refine;
+    mdx_fx_opts o{};
+    MDX_TRY(refine_opts_check(who, fo, o));
+    GuestRun run;
+    MDX_TRY(guest_check(h, who, n_ligands, ligs, n_groups, run, flex, fo.flags));
+    for (uint32_t m = 0; m < n_ligands; ++m)
+        if (run.shapes[m].n_poses && sr_choices(so, run.shapes[m].T) == 0u)
+            FAIL(MDX_EPARAM, who + ": ligand " + std::to_string(m) + ": no move is enabled (only tors_amp with no torsion)");
+    const size_t total = run.total;
+    if (total == 0) return MDX_OK;
+    if (!best_out) FAIL(MDX_EPARAM, who + ": null argument");
+    const bool want_best = best_walker_or_null || best_ligand_score_or_null;
+    MDX_TRY(guest_ready(h, n_ligands, GUEST_SEARCH, want_best, run));
+    DeviceState& d = h->d;
+    hipStream_t st = h->stream;
+    const uint32_t W = h->n_grp + 1u;
+    size_t nxyz = 0;
+    for (const GuestChunk& c : run.chunks) nxyz += c.nxyz;
+    std::vector<float> yres(nxyz), rres(total * W);
+    SearchOut res(total);
+    std::vector<unsigned char> back;
+    unsigned char* blk = (unsigned char*)d.gs_blk;
+    size_t x0 = 0;      // first float of the chunk in best_out
+    for (const GuestChunk& c : run.chunks) {
+        const GuestLayout lay = guest_layout(c, W, GUEST_SEARCH);
+        const StepLayout sl = StepLayout::guest(c.n, c.nxyz, W, sizeof(mdx_fx_state), c.fx.terms);
+        const SearchLayout ssl = SearchLayout::guest(c.n, c.nxyz, W);
+        MDX_TRY(guest_stage(h, ligs, c, lay, run, true, streams_or_null));
+        PoseArgs& a = run.a;
+        unsigned char* sb = blk + lay.step;
+        unsigned char* qb = blk + lay.search;
+        const StepArgs r = guest_step_args(h, run, lay, sl, W, true, o);
+        const SearchArgs s = search_args(r, qb, ssl, 0u, W, 0u, so);
+        HIP_TRY(hipMemsetAsync(sb, 0, sl.y, st));
+        HIP_TRY(hipMemsetAsync(qb + ssl.rec, 0, ssl.best_y - ssl.rec, st));
+        mdx_prof_begin(h, 0);
+        for (uint32_t rd = 0; rd < opts->n_rounds; ++rd) {
+            mdx_launch_guest_search(st, c.n, s, rd, a.rec, r.frec);
+            for (uint32_t k = 0; k < fo.max_evals; ++k) step_evaluate<true>(h, a, run.mode, run.geom, c.n, r);
+        }
+        mdx_launch_guest_search(st, c.n, s, opts->n_rounds, a.rec, r.frec);
+        if (want_best)
+            hipLaunchKernelGGL(guest_best_search_kernel, dim3((c.n + 255u) / 256u), dim3(256), 0, st, c.n, (const uint2*)(blk + lay.ligof),
+                               (const mdx_sr_record*)s.rec, (GuestBest*)d.gs_best);
+        mdx_prof_end(h);
+        HIP_TRY(hipGetLastError());
+        back.resize(ssl.cur_y - ssl.rec);
+        HIP_TRY(hipMemcpyAsync(back.data(), qb + ssl.rec, back.size(), hipMemcpyDeviceToHost, st));
+        if (want_best && &c == &run.chunks.back())
+            HIP_TRY(hipMemcpyAsync(run.best.data(), d.gs_best, sizeof(GuestBest) * run.best.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const unsigned char* b0 = back.data();
+        std::memcpy(yres.data() + x0, b0 + ssl.best_y, sizeof(float) * c.nxyz);
+        std::memcpy(rres.data() + c.p0 * W, b0 + ssl.best_row, sizeof(float) * (size_t)W * c.n);
+        res.take(b0 + ssl.rec, c.n, c.p0);
+        x0 += c.nxyz;
+    }
+    std::memcpy(best_out, yres.data(), sizeof(float) * yres.size());
+    if (best_rows_out_or_null) std::memcpy(best_rows_out_or_null, rres.data(), sizeof(float) * rres.size());
+    res.write(best_score_out_or_null, best_dih_out_or_null, best_round_out_or_null, stats_out_or_null);
+    for (uint32_t m = 0; want_best && m < n_ligands; ++m) {
+        if (best_walker_or_null) best_walker_or_null[m] = run.best[m].pose;
+        if (best_ligand_score_or_null) best_ligand_score_or_null[m] = run.best[m].score;
+    }
+    return MDX_OK;
 }

@@ -1,6 +1,6 @@
 // mdx_search_step.h - the rule of mdx_search_poses (include/mdx.h states it): an iterated local search per walker - perturb the
 // accepted pose, refine it with the flexible stepper of mdx_flex_step.h, accept or reject by Metropolis, keep the best.  Plain C++ in
-// fp64, no HIP types: pose_search_kernel (mdx_poses.hip) calls these functions on the device, and a stand-alone host program can include
+// fp64, no HIP types: the search kernels (pose_search of mdx_pose_search_dev.h) call these functions on the device, and a stand-alone host program can include
 // this file and call the same ones (tests/cpp/pose_search_driver.cpp).  Where the rule is a stepper's, the function is that stepper's:
 // the move's rotation and translation are one rf_trial of unit step, the new start is fx_build / fx_coords of the accepted pose.
 //
@@ -27,7 +27,7 @@
 
 struct mdx_sr_opts { double trans_amp, rot_amp, tors_amp, kT; uint64_t seed; uint32_t n_rounds, pad; };
 
-// one walker's search record; its coordinates, best row and best rigid lie beside it (SearchLayout of mdx_poses.hip)
+// one walker's search record; its coordinates, best row and best rigid lie beside it (SearchLayout of mdx_pose_plan.h)
 struct mdx_sr_record {
     double S_cur, S_best;
     float edih_best; uint32_t best_round;

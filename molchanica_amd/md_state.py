@@ -19,7 +19,8 @@ import numpy as np
 
 from ._abi import (CCommDiag, CFlexOpts, CGuestFlex, CGuestLigand, CHBond, CConfig, CEnergies, CLUSTER_MAX_PERMS, CLUSTER_MAX_POSES, CLUSTER_POSES_ARGTYPES, CRefineOpts,
                    CSearchOpts, CStats, CSystem, FLEX_DIHEDRALS, FORCE, FUSED_TRIAD_INFO_ARGTYPES, POSE_RMSD_ARGTYPES,
-                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, GUEST_FORCES_ARGTYPES, REFINE_GUESTS_ARGTYPES, REFINE_GUESTS_FLEX_ARGTYPES, SCREEN_LIGANDS_ARGTYPES, VEL, GuestFlex, GuestLigand,
+                   MDX_EDEVICE, MDX_ENAN, MDX_EOOM, MDX_EPARAM, MDX_OK, POS, POSE_MAX_ATOMS, POSE_MAX_TORSIONS, GUEST_FORCES_ARGTYPES, REFINE_GUESTS_ARGTYPES, REFINE_GUESTS_FLEX_ARGTYPES, SCREEN_LIGANDS_ARGTYPES, SEARCH_GUESTS_ARGTYPES,
+                   SEARCH_MAX_ROUNDS, VEL, GuestFlex, GuestLigand,
                    MdConfig, MdSystem, CSolubility, SET_SOLUTE_COPIES_ARGTYPES, SNAPSHOT_READ_SOLUBILITY_ARGTYPES, SOLUBILITY_MIXING_ARGTYPES,
                    SOLUTE_MAX_COPIES)
 
@@ -187,6 +188,7 @@ def load_library():
     lib.mdx_guest_forces.argtypes = GUEST_FORCES_ARGTYPES
     lib.mdx_refine_guests.argtypes = REFINE_GUESTS_ARGTYPES
     lib.mdx_refine_guests_flex.argtypes = REFINE_GUESTS_FLEX_ARGTYPES
+    lib.mdx_search_guests.argtypes = SEARCH_GUESTS_ARGTYPES
     lib.mdx_set_solute_copies.argtypes = SET_SOLUTE_COPIES_ARGTYPES
     lib.mdx_solubility_mixing.argtypes = SOLUBILITY_MIXING_ARGTYPES
     lib.mdx_snapshot_read_solubility.argtypes = SNAPSHOT_READ_SOLUBILITY_ARGTYPES
@@ -513,6 +515,64 @@ class MdState:
         out = (self._per_ligand(y, counts, sizes), rows, rigid, ragged(x, [7 + k for k in T]), self._per_ligand(e, counts), ragged(g, T),
                self._per_ligand(st, counts), self._per_ligand(ev, counts))
         return out + ((bp[:M], bs[:M]),) if best else out
+
+    def search_guests(self, ligands, flex, n_rounds: int, trans_amp: float, rot_amp: float, tors_amp: float, kT: float, seed: int,
+                      max_evals: int, f_tol: float, tau_tol: float, tors_tol: float, h_start: float = 0.0, h_max: float = 0.0,
+                      dihedrals: bool = True, streams=None, best=False):
+        """`mdx_search_guests`: search_poses() for a library of guest ligands - every pose of every ligand is a walker that starts
+        there; round 0 refines it as refine_guests_flex() does, every later round perturbs the walker's current pose (translation,
+        rotation or one of the ligand's own torsions), refines it with the same options and accepts it by Metropolis at kT
+        (include/mdx.h states the rule; it is search_poses()'s).  flex: one `GuestFlex` per ligand.  streams: None (a walker draws from
+        the stream of its ligand-local pose index, so a ligand searches alike alone and in any library) or unsigned integers
+        [sum of P_m] in the library's pose order; seed: 64 bits.
+        -> (best, rows, score, dih, best_round, stats), each a list with one array per ligand: [P_m, count, 3], [P_m, n_groups + 1]
+        f32, [P_m] f64 (S = sum of the row + the dihedral energy; inf if no round was finite), [P_m] f32, [P_m] u32, [P_m, 4] u32
+        (rounds accepted, accepted uphill, non-finite rounds, evaluations), all of the walker's best round.  best=True: also
+        (best_walker uint32 [M], best_ligand_score float64 [M]) - per ligand the walker with the smallest score (lowest index on a
+        tie), picked on the device; 0xFFFFFFFF and inf for a ligand without a finite walker.  The handle is left as it is."""
+        who = "search_guests"
+        M, recs, counts, (sizes, _keep) = self._guest_records(who, ligands)
+        frecs, T, _fkeep = self._guest_flex_records(who, flex, sizes)
+        total = sum(counts)
+        ids = None
+        if streams is not None:
+            ids = np.asarray(streams)
+            if ids.dtype.kind not in "iu" or ids.shape != (total,) or (ids < 0).any():
+                raise ParamError(f"{who}: streams must be unsigned integers [sum of the ligands' poses]")
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        if not 0 <= int(seed) < 1 << 64:
+            raise ParamError(f"{who}: seed must fit 64 bits")
+        if not 1 <= int(n_rounds) <= SEARCH_MAX_ROUNDS or int(max_evals) < 1 or int(n_rounds) * int(max_evals) > 65536:
+            raise ParamError(f"{who}: n_rounds must be in 1..{SEARCH_MAX_ROUNDS}, max_evals >= 1 and n_rounds x max_evals <= 65536")
+        amps = [float(v) for v in (trans_amp, rot_amp, tors_amp, kT)]
+        if any(not np.isfinite(v) or v < 0.0 for v in amps):
+            raise ParamError(f"{who}: an amplitude or kT is negative or not finite")
+        if np.float32(amps[2]) > np.float32(np.pi):
+            raise ParamError(f"{who}: tors_amp exceeds pi")
+        for m in range(M):
+            if counts[m] and not (amps[0] > 0.0 or amps[1] > 0.0 or (amps[2] > 0.0 and T[m] > 0)):
+                raise ParamError(f"{who}: ligand {m}: no move is enabled (every amplitude is 0, or only tors_amp with no torsion)")
+        lib = load_library()
+        G = int(lib.mdx_energy_group_count(self._h))
+        P = max(total, 1)
+        opts = CSearchOpts(int(n_rounds), amps[0], amps[1], amps[2], amps[3], int(seed),
+                           CFlexOpts(int(max_evals), float(f_tol), float(tau_tol), float(tors_tol), float(h_start), float(h_max),
+                                     FLEX_DIHEDRALS if dihedrals else 0))
+        y = np.zeros(max(sum(3 * n * p for n, p in zip(sizes, counts)), 1), dtype=np.float32)
+        r = np.zeros((P, G + 1), dtype=np.float32)
+        sc = np.zeros(P, dtype=np.float64)
+        e = np.zeros(P, dtype=np.float32)
+        br = np.zeros(P, dtype=np.uint32)
+        stt = np.zeros((P, 4), dtype=np.uint32)
+        bw = np.full(max(M, 1), 0xFFFFFFFF, np.uint32)
+        bs = np.full(max(M, 1), np.inf, np.float64)
+        dp = C.POINTER(C.c_double)
+        _check(lib.mdx_search_guests(self._h, M, recs, frecs, None if ids is None else ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                     C.byref(opts), y.ctypes.data_as(_fp), r.ctypes.data_as(_fp), G, sc.ctypes.data_as(dp),
+                                     e.ctypes.data_as(_fp), br.ctypes.data_as(_u32p), stt.ctypes.data_as(_u32p),
+                                     bw.ctypes.data_as(_u32p) if best else None, bs.ctypes.data_as(dp) if best else None))
+        out = (self._per_ligand(y, counts, sizes),) + tuple(self._per_ligand(v, counts) for v in (r, sc, e, br, stt))
+        return out + ((bw[:M], bs[:M]),) if best else out
 
     def pose_forces(self, first: int, poses, rows=True, rigid=False):
         """`mdx_pose_forces`: the force on every atom of each of P alternative placements of the atoms [first, first + count) - minus
